@@ -7,7 +7,13 @@ update, on a 49-frame 704x1280 latent [48,13,44,80] (L = 11 440 tokens; SURVEY.m
 "49-frame 720p latent" BASELINE.json's metric is quoted on), TI2V-5B dimensions (dim 3072, ffn 14336, 24 heads,
 30 layers), random-init weights (no checkpoints offline), synthetic noise / prompt-embeds resident in HBM.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline line (`ms_per_step` = wall time of one timed step).
+`--dump-outputs DIR` writes what the last timed step returned (the latent, float32) as DIR/<name>.npy; the inputs are seeded, so
+two builds run with the same arguments can be compared output for output. Everything else the line can carry - the self-attention
+roofline pass, UniVid's own entry point, the default and stress shapes, the ranker, the VAE, the vendor-library calibrations, the
+CPU baselines and the host-policy child - runs only with `--full` (each `--no-*` switch then drops one of them).
 
 N > 1: one process per GPU over RCCL (torch.distributed backend "nccl"): every rank denoises its OWN sample (independent
 diffusion samples shard one per GPU, no data-path collective) and the final latents are all-gathered once over xGMI at
@@ -30,7 +36,7 @@ import time
 # (profiles/r06_host_policy.md). `--host-sync auto` (the default): hipDeviceScheduleBlockingSync for every rank, the runtime's own dispatch mode -
 # RCCL has never run under AMD_DIRECT_DISPATCH=0 here (no multi-GPU box in six rounds), and the first N > 1 run must not also be the first run of
 # a dispatch mode; on this pool's 256-thread hosts eight spinning runtime threads cost nothing. `--host-sync blocking` adds AMD_DIRECT_DISPATCH=0
-# (for hosts where the cores matter, once validated there); `default` leaves the runtime alone. Every N = 1 line carries the measurement of the
+# (for hosts where the cores matter, once validated there); `default` leaves the runtime alone. Every N = 1 --full line carries the measurement of the
 # `blocking` policy from a child process (`pipeline_path.host_sync.rank_policy_child`); the parent keeps direct dispatch also because HIP events
 # around an EAGER launch read 5 % long under the command thread (2.857 -> 3.005 ms on the self-attention launch; 2.84 in the rocprofv3 trace
 # either way) and `roofline` is measured exactly so.
@@ -682,11 +688,39 @@ def cpu_baseline(cfg, budget_s=15.0):
                       f"differ the extrapolation assumes the CPU runs attention and GEMMs at the same rate)"}
 
 
+DUMP_BUDGET_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: each array as DIR/<name>.npy (float64 stays float64, anything else is written as float32). One whose share of
+    the 64 MB budget is too small for it is written as a fixed sample instead: its elements at sorted flat indices drawn without
+    replacement by numpy's default_rng(0) - the same indices in every run of the same shape. Returns what was written, for the line."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    share = (DUMP_BUDGET_BYTES - (64 << 10) * len(arrays)) // max(len(arrays), 1)    # (room for the .npy headers)
+    res = {}
+    for name, t in arrays.items():
+        a = t.detach().to("cpu", torch.float64 if t.dtype == torch.float64 else torch.float32).numpy()
+        info = {"file": f"{name}.npy", "shape": list(a.shape), "dtype": str(a.dtype), "sample": None}
+        if a.nbytes > share:
+            n = share // a.itemsize
+            idx = np.sort(np.random.default_rng(0).choice(a.size, n, replace=False))
+            a = a.reshape(-1)[idx]
+            info["sample"] = f"{n} of {t.numel()} elements: flat indices sorted(numpy.random.default_rng(0).choice({t.numel()}, {n}, replace=False))"
+        np.save(os.path.join(dirname, f"{name}.npy"), np.ascontiguousarray(a))
+        res[name] = info
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=6)
+    ap.add_argument("--steps", type=int, default=6, help="timed steps; a run longer than the 50-step schedule uses a schedule of warmup + steps timesteps")
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one returned (the latent; "
+                    "with N > 1 replicas the gathered latents of every rank) as DIR/<name>.npy, at most 64 MB in all")
+    ap.add_argument("--full", action="store_true", help="also run every side measurement (roofline pass, entry-point path, other shapes, ranker, "
+                    "VAE, vendor-library calibrations, CPU baselines, host-policy child); a plain run times the headline only")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--graph", choices=["auto", "on", "off"], default="auto", help="replay the CFG pair's forward from a captured HIP graph (what "
                     "WanTI2V.denoise does for the plain single-process loop): same kernels, same order, bit-identical; the host then issues a handful "
@@ -735,8 +769,10 @@ def main():
         return
     if args.host_probe:
         return host_probe_main()
-    # (before anything below touches the GPU:) the ranks' host policy measured in a child, for the pipeline_path sub-line of the N = 1 run
-    host_probe = run_host_probe_child() if (world == 1 and args.gpus == 1 and args.host_sync == "auto" and not args.no_pipeline_path and not args.layers
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
+    # (before anything below touches the GPU:) the ranks' host policy measured in a child, for the pipeline_path sub-line of the N = 1 --full run
+    host_probe = run_host_probe_child() if (args.full and world == 1 and args.gpus == 1 and args.host_sync == "auto" and not args.no_pipeline_path and not args.layers
                                             and args.shape == "A") else None
     if world != args.gpus:
         raise SystemExit(f"WORLD_SIZE={world} but --gpus {args.gpus}: start one rank per GPU "
@@ -791,10 +827,11 @@ def main():
     ctx = [torch.randn(77, cfg["text_dim"], device=device, generator=g) * 0.1]
     ctx_null = [torch.randn(12, cfg["text_dim"], device=device, generator=g) * 0.1]
     sched = FlowUniPCMultistepScheduler(num_train_timesteps=1000, shift=1)
-    sched.set_timesteps(SAMPLING_STEPS, device="cpu", shift=SHIFT)
+    # the 50-step schedule (inference.py's); --steps is honoured beyond it: warmup + steps > 50 samples a schedule of that many timesteps
+    sched.set_timesteps(max(SAMPLING_STEPS, args.warmup + args.steps), device="cpu", shift=SHIFT)
+    sched.set_begin_index(0)       # step 0 is the schedule's first (what the timestep lookup finds on the 50-step one)
     timesteps = sched.timesteps
     seq_len = L_TOKENS
-    assert args.warmup + args.steps <= len(timesteps)
 
     from univid_amd.wan.textimage2video import _GraphedPair, graph_by_default
     use_graph = (args.graph == "on" or (args.graph == "auto" and graph_by_default(seq_len))) and cfgp is None and not use_sp
@@ -845,20 +882,25 @@ def main():
         mine = {"rank": rank, "ms_per_step": round(ev[0].elapsed_time(ev[1]) / args.steps, 3), "allgather_us": round(ev[1].elapsed_time(ev[2]) * 1e3, 1) if world > 1 else None,
                 "host_cpu_ms_per_step_enqueue": round((cpu1 - cpu0) / args.steps * 1e3, 3),
                 "host_cpu_ms_per_step_incl_wait": round((cpu2 - cpu0) / args.steps * 1e3, 3)}
+        dumped = None
+        if args.dump_outputs and rank == 0:      # what a caller of the timed path receives: the latent (N > 1 replicas: every rank's, gathered)
+            dumped = dump_outputs(args.dump_outputs, {"latent": torch.stack(gathered) if world > 1 and not shared else latent})
         per_rank = [mine]
         if world > 1:
             per_rank = [None] * world
             dist.all_gather_object(per_rank, mine)
-        # Live HIP-event timing of the dominant kernel (self-attention) on the launch stream, in a SEPARATE pass behind the timed region
-        # (round-3 verdict: the timed steps record nothing the product does not): one more forward pair of the same loop = the 30
-        # self-attention launches of a step, each in its real place between the block's other kernels.
-        _lib.PROFILE = {"uv_flash_attn_bf16": []}
-        _lib.PROFILE_ALL = bool(args.kernel_times)
-        runner = None      # (eager launches: HIP events around individual kernels cannot be recorded inside a graph replay)
-        forward_pair(min(args.warmup + args.steps, len(timesteps) - 1), latent)      # the step's two forwards (the sampler update launches no attention)
-        barrier()
-        prof = _lib.PROFILE
-        _lib.PROFILE, _lib.PROFILE_ALL = None, False
+        prof = {}
+        if args.full or args.kernel_times:
+            # Live HIP-event timing of the dominant kernel (self-attention) on the launch stream, in a SEPARATE pass behind the timed region
+            # (round-3 verdict: the timed steps record nothing the product does not): one more forward pair of the same loop = the 30
+            # self-attention launches of a step, each in its real place between the block's other kernels.
+            _lib.PROFILE = {"uv_flash_attn_bf16": []}
+            _lib.PROFILE_ALL = bool(args.kernel_times)
+            runner = None      # (eager launches: HIP events around individual kernels cannot be recorded inside a graph replay)
+            forward_pair(min(args.warmup + args.steps, len(timesteps) - 1), latent)      # the step's two forwards (the sampler update launches no attention)
+            barrier()
+            prof = _lib.PROFILE
+            _lib.PROFILE, _lib.PROFILE_ALL = None, False
 
     tmax = torch.tensor([dt], device=device, dtype=torch.float64)
     if world > 1:
@@ -930,17 +972,21 @@ def main():
                          "host_cpu_ms_per_step_incl_wait_max": max(r["host_cpu_ms_per_step_incl_wait"] for r in per_rank), "ranks": per_rank,
                          "note": "per rank, HIP events on its launch stream inside the timed region: its own K steps (GPU time), then the one all-gather "
                                  "(includes waiting for the slowest rank); host CPU = process time of the rank, enqueue only / up to the closing barrier"},
+            "full": bool(args.full),
             "host_sync": args.host_sync,
             "host_env": {k: os.environ.get(k) for k in ("AMD_DIRECT_DISPATCH", "HSA_ENABLE_IPC_MODE_LEGACY")},
             "ffn2_strip": "256x256 x split-K 4 (uv_gemm_bf16_nt_ws, --splitk-strip)" if args.splitk_strip else "128x128 ring",
             "host_note": "process CPU time (user + system, all threads of this rank) spent issuing one step's launches, and C-ABI entry-point calls per step",
         }
+        if dumped is not None:
+            out["outputs"] = {"dir": args.dump_outputs, **dumped}
         if args.kernel_times:
             out["kernel_times"] = {k: {kk: (round(vv, 4) if isinstance(vv, float) else vv) for kk, vv in v.items()} for k, v in ktimes.items()}
         out["rccl_ranks"] = world if (world > 1 and not share_gpu) else 0
         if share_gpu:
             out["transport"] = "gloo, all ranks on cuda:0 (UV_BENCH_SHARE_GPU=1 test hook: NOT a multi-GPU measurement)"
-        if world == 1 and not args.no_pipeline_path and args.shape == "A":
+        full1 = args.full and world == 1       # the side measurements below: --full runs on one GPU only
+        if full1 and not args.no_pipeline_path and args.shape == "A":
             runner = None
             torch.cuda.empty_cache()
             try:
@@ -950,12 +996,12 @@ def main():
                 out["pipeline_path"]["vs_headline_ms_per_step"] = round(out["pipeline_path"]["ms_per_step"] / out["ms_per_step"], 4)
             except Exception as ex:      # a side measurement: never fails the bench
                 out["pipeline_path"] = {"error": repr(ex)[:300]}
-        if world == 1 and not args.no_default_shape and not args.layers and args.shape == "A":
+        if full1 and not args.no_default_shape and not args.layers and args.shape == "A":
             try:
                 out["default_shape"] = default_shape_probe(model, device, cfg)
             except Exception as ex:      # a side measurement: never fails the bench
                 out["default_shape"] = {"error": repr(ex)[:300]}
-        if world == 1 and not args.no_stress_shape and not args.layers and args.shape == "A":
+        if full1 and not args.no_stress_shape and not args.layers and args.shape == "A":
             runner = None
             torch.cuda.empty_cache()
             try:
@@ -965,12 +1011,12 @@ def main():
                     out["stress_shape"] = stress_shape_probe(device, dict(TI2V_5B_CFG), blocks=cfg["num_layers"], model=model)
             except Exception as ex:      # a side measurement: never fails the bench
                 out["stress_shape"] = {"error": repr(ex)[:300]}
-        if world == 1 and not args.no_ranker and args.shape == "A":
+        if full1 and not args.no_ranker and args.shape == "A":
             try:
                 out["ranker"] = ranker_probe(device)
             except Exception as ex:      # a side measurement: never fails the bench
                 out["ranker"] = {"error": repr(ex)[:300]}
-        if world == 1 and not args.no_vae and not args.layers and args.shape == "A":
+        if full1 and not args.no_vae and not args.layers and args.shape == "A":
             model = None                                         # the 30 GB of DiT weights are not needed any more
             torch.cuda.empty_cache()
             # headline = the VAE's DEFAULT arithmetic since round 4: f16x3 (f32-grade: as close to an fp64 convolution as the exact f32
@@ -985,7 +1031,7 @@ def main():
             x6 = vae_metrics(device, "bf16x6", reps=2)
             out["vae_decode_bf16x6"], out["vae_encode_bf16x6"] = x6["decode"], x6["encode"]
             out["vae_decode_bf16x3"] = vae_metrics(device, "bf16x3", encode=False)["decode"]
-        if world == 1 and not args.no_vae and not args.layers and args.shape == "A":
+        if full1 and not args.no_vae and not args.layers and args.shape == "A":
             try:
                 out["hipblaslt_ref"] = hipblaslt_ref(device)
             except Exception as ex:      # calibration only: never fails the bench
@@ -994,7 +1040,7 @@ def main():
                 out["sdpa_ref"] = sdpa_ref(device)
             except Exception as ex:      # calibration only: never fails the bench
                 out["sdpa_ref"] = {"error": repr(ex)[:200]}
-        if world == 1 and not args.no_cpu_baseline:
+        if full1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(dict(TI2V_5B_CFG))
             if not args.no_vae:
                 out["cpu_baseline"]["vae_decode"] = cpu_baseline_vae()
