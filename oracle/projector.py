@@ -8,8 +8,33 @@ import torch
 import torch.nn.functional as F
 
 
-def forward(sd, tokens, target_len):
-    """sd: bf16 state dict with keys bagel_to_t5_projector.{0,1,4,5}.{weight,bias}; tokens [B, L, D] -> list of [target_len, Dout] bf16."""
+def interpolate_rows(x, target_len, interp="cpu"):
+    """F.interpolate(x^T, size=target_len, mode='linear', align_corners=False)^T on x [B, L, C] bf16, in one of two semantics:
+
+    "cpu"    the op as CPU torch runs it on the bf16 tensor: the CPU kernel keeps the source index and the interpolation WEIGHTS in
+             the tensor's dtype, so the weights themselves are rounded to bf16 before the blend (what the golden fixtures hold: the
+             reference class executed on the CPU).
+    "device" the op as the reference runs it, on the GPU: torch's device kernel keeps index and weights in fp32 (accscalar_t),
+             blends the two bf16 rows in fp32 and rounds once to bf16 - in torch terms F.interpolate(x.float()).to(bf16). This is
+             also what `uv_interp_linear_rows_bf16` computes.
+
+    The two agree only where every weight is exact in bf16, e.g. the golden's 20 / 77 -> 32 rows. At production lengths they do
+    not: against an fp32 emulation of the device formula, CPU bf16 F.interpolate is bit-identical on only 62 % of the elements at
+    77 -> 512, 129 -> 512 and 513 -> 512 (63 % at 300 -> 77; errors ~0.016 on unit-scale values), while the "device" form is
+    100 % (99.995 % at 300 -> 77)."""
+    xt = x.transpose(1, 2)
+    if interp == "cpu":
+        y = F.interpolate(xt, size=target_len, mode="linear", align_corners=False)
+    elif interp == "device":
+        y = F.interpolate(xt.float(), size=target_len, mode="linear", align_corners=False).to(x.dtype)
+    else:
+        raise ValueError(f"interp must be 'cpu' or 'device', got {interp!r}")
+    return y.transpose(1, 2)
+
+
+def forward(sd, tokens, target_len, interp="cpu"):
+    """sd: bf16 state dict with keys bagel_to_t5_projector.{0,1,4,5}.{weight,bias}; tokens [B, L, D] -> list of [target_len, Dout] bf16.
+    interp: semantics of the final resampling (see `interpolate_rows`); "cpu" is the reference class run on the CPU (the golden)."""
     bf = torch.bfloat16
     p = "bagel_to_t5_projector."
     x = tokens.to(bf)
@@ -19,7 +44,7 @@ def forward(sd, tokens, target_len):
     x = F.linear(x, sd[p + "4.weight"], sd[p + "4.bias"])
     x = F.layer_norm(x, (x.shape[-1],), sd[p + "5.weight"], sd[p + "5.bias"], 1e-5)
     if x.shape[1] != target_len:
-        x = F.interpolate(x.transpose(1, 2), size=target_len, mode="linear", align_corners=False).transpose(1, 2)
+        x = interpolate_rows(x, target_len, interp)
     return [x[b] for b in range(x.shape[0])]
 
 

@@ -190,3 +190,36 @@ def test_t5_oracle_matches_reference_golden():
     for n in (48, 33, 5):
         assert torch.equal(t5.encode(sd, t5.TINY_CFG, g[f"ids_{n}"]), g[f"out_{n}"])
     assert torch.equal(t5.relative_position_bucket(g["rel"]), g["buckets"])
+
+
+def test_projector_interpolation_device_semantics():
+    """oracle.projector.interpolate_rows: the "device" form (fp32 index / weights / blend, one bf16 rounding: torch's GPU kernel, the
+    reference's device) against the "cpu" form (CPU torch on bf16 keeps the weights in bf16). At the golden's 20 / 77 -> 32 every
+    weight is exact in bf16 and the two are equal, so tests/golden/context_projector.npz serves both. At 77 -> 512 only the device
+    form stays within 1 bf16 ulp of an fp64 evaluation of the same formula on every element."""
+    from oracle import projector
+    from conftest import bf16_ulp
+    g = load_golden("context_projector")
+    sd = projector.make_state_dict(128, 256, int(g["seed"]))
+    for L in (20, 77):
+        pre = torch.stack(projector.forward(sd, g[f"tokens_{L}"], L))          # the rows before the resampling
+        assert torch.equal(projector.interpolate_rows(pre, 32, "cpu"), projector.interpolate_rows(pre, 32, "device")), L
+        dev = torch.stack(projector.forward(sd, g[f"tokens_{L}"], 32, interp="device"))
+        assert torch.equal(dev, g[f"out_{L}"]), L
+    Lin, Lout = 77, 512
+    x = torch.randn(2, Lin, 512, generator=torch.Generator().manual_seed(3)).to(torch.bfloat16)
+    src = ((torch.arange(Lout, dtype=torch.float64) + 0.5) * Lin / Lout - 0.5).clamp_min(0)
+    i0 = src.floor().long()
+    i1 = torch.clamp(i0 + 1, max=Lin - 1)
+    w1 = (src - i0).view(1, Lout, 1)
+    xd = x.double()
+    truth = (1 - w1) * xd[:, i0] + w1 * xd[:, i1]
+    tol = bf16_ulp(truth)
+    dev = projector.interpolate_rows(x, Lout, "device")
+    cpu = projector.interpolate_rows(x, Lout, "cpu")
+    assert dev.dtype == cpu.dtype == torch.bfloat16 and dev.shape == cpu.shape == (2, Lout, 512)
+    assert ((dev.double() - truth).abs() <= tol).all()
+    over = (cpu.double() - truth).abs() > tol
+    assert over.float().mean() > 0.05, f"CPU bf16 interpolation within 1 ulp on all but {int(over.sum())} elements"
+    with pytest.raises(ValueError):
+        projector.interpolate_rows(x, Lout, "nearest")
