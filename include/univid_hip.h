@@ -70,8 +70,7 @@ int uv_gemm_bf16_nt(const void* A, long lda, const void* W, long ldw, const void
  * from uv_gemm_bf16_nt's by the f32 summation order only (4 partial sums instead of one chain; <= 1 ulp of the epilogue's 16-bit rounding).
  * workspace: device memory, 256-byte aligned, workspace_bytes >= uv_gemm_splitk_ws_bytes(M, N, K); contents need no initialisation and
  * are scratch afterwards; launches that share a workspace must be ordered (same stream). NULL / too small: exactly uv_gemm_bf16_nt.
- * tile_cfg 19 / 20 (tests, tools): the whole problem as split-K 4 / 2 (epilogues 0, 3, 4; workspace 4096 + tiles x split x 256 KiB);
- * 21 = 19 with one K range per XCD instead of one tile per XCD (placement A/B, same results). */
+ * tile_cfg 19 / 20 (tests, tools): the whole problem as split-K 4 / 2 (epilogues 0, 3, 4; workspace 4096 + tiles x split x 256 KiB). */
 int uv_gemm_bf16_nt_ws(const void* A, long lda, const void* W, long ldw, const void* bias_bf16, int M, int N, int K,
                        int epilogue, void* out, long ldo, const float* gate, const int32_t* gate_tid, long gate_stride,
                        int tile_cfg, void* workspace, long workspace_bytes, void* stream);

@@ -572,6 +572,23 @@ def test_ffn0_row_padding_never_adds_a_round_of_tiles():
         assert Lp == L or (Lp % 256 == 0 and 0 < Lp - L < 256 and -(-(Lp // 256 * 56) // 256) == -(-(L // 256 * 56) // 256))
 
 
+def test_splitk_workspace_size_follows_the_gemm_plan():
+    """uv_gemm_splitk_ws_bytes is the GEMM launch plan's one externally visible output: the bytes the split-K strip of a tile_cfg 0
+    call needs (4 096 + strip tiles x 4 slices x 256 KiB), 0 where the plan has no such strip. Without a device the library plans
+    for 256 CUs, which is also what an MI355X reports."""
+    lib = _lib.load()
+    for M, N, K, want in [
+        (22880, 3072, 14336, 62918656),     # 1 080 tiles = 4 rounds + 56 (under 45 % of a round): 21 760 rows persistent, a 1 120-row strip of 5 x 12 tiles
+        (22880, 3072, 3072, 0),             # K < 8 192: the strip stays on the 128x128 ring
+        (1024, 3072, 14336, 0),             # small shape
+        (54560, 3072, 14336, 12587008),     # 32-row strip: 12 tiles
+        (22784, 3072, 14336, 50335744),     # whole row tiles, short round: a 1 024-row strip
+        (22235, 3072, 14336, 25169920),
+        (22880, 3000, 14336, 0),            # N not in whole tiles
+    ]:
+        assert lib.uv_gemm_splitk_ws_bytes(M, N, K) == want, (M, N, K)
+
+
 def test_graph_runner_cache_policy():
     """WanTI2V keeps the `max_graph_runners` most recently used captured graphs (host logic only - stand-ins for the runners; the replay
     itself is tests/test_gpu_parity.py::test_graph_runner_serves_new_prompts_without_recapture_and_never_goes_stale): a hit moves the

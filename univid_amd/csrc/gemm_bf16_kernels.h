@@ -23,9 +23,10 @@
 //                         large projection (tile_cfg 7; what tile_cfg 0 picks for M >= 2048, N % 256 == 0, K % 128 == 0)
 //   gemm_bf16_nt_kernel   generic BM x BN tile, NS LDS stages: 128x128 / 8 waves / 4-stage ring for leftover-row strips
 //                         and small-M projections (tile_cfg 12), 2-stage 4-wave and 16-wave forms for everything else
-//   uv_gemm_bf16_nt       shape-based choice, leftover-row split (launch_m_split)
+//   uv_gemm_bf16_nt       gemm_bf16.hip: plan_gemm (which rows go to which kernel) and the launches of its steps
 #include "common.h"
 #include <stdlib.h>
+#include <type_traits>
 
 const float* uv_zero_page();   // gemm_f32.hip: one 4-KiB page of zeros per device
 
@@ -572,10 +573,6 @@ __device__ __forceinline__ void epi_rmw_rows_lds(const GemmArgs& p, char* smem, 
 // phases pairwise - 32 MFMAs per cluster, half as many barriers and cluster ramps per MFMA: +2-4 % measured.
 // Needs N % 256 == 0 rows of W to exist (clamped like A otherwise) and an even K/64 >= 4.
 #define UV_SB() __builtin_amdgcn_s_barrier()
-#ifndef UV_REBAL
-#define UV_REBAL 1   // VAR 5: W[0] of K tile t+1 is staged in phase A of K tile t (into the other buffer, beside A[1]) instead of as W[0] of t+2 in phase B of t-1:
-                     // 4 + 4 LDS-DMA pieces per phase instead of 2 + 6. Same arithmetic, bit-identical
-#endif
 #define UV_SCHED() __builtin_amdgcn_sched_barrier(0)
 
 // SK > 1 (VAR 5 only): SPLIT-K form for the leftover-row strips of the long-K projections (ffn.2: 1 120 rows x 3 072 columns x K 14 336 =
@@ -609,15 +606,11 @@ __global__ __launch_bounds__(512) void gemm_bf16_8ph_kernel(GemmArgs p) {
         const int q = nblk >> 3, r = nblk & 7, xcd = bid & 7, idx = bid >> 3;
         bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
     } else {
+        // the SK slices of a tile on ONE XCD: per = ceil(nblk * SK / 8) (tile, slice) units per XCD
         const int xcd = bid & 7, idx = bid >> 3, per = gridDim.x >> 3;
-        if (p.gm == 0) {        // the SK slices of a tile on ONE XCD: per = ceil(nblk * SK / 8) (tile, slice) units per XCD
-            const int u = xcd * per + idx;
-            slice = u % SK;
-            bid = u / SK;
-        } else {                // A/B (tile_cfg 21): XCD x takes slice x % SK of the tiles of part x / SK; per = ceil(nblk / (8 / SK)) tiles per XCD
-            slice = xcd % SK;
-            bid = (xcd / SK) * per + idx;
-        }
+        const int u = xcd * per + idx;
+        slice = u % SK;
+        bid = u / SK;
         if (bid >= nblk) return;
     }
     constexpr int GM = 4;
@@ -718,7 +711,8 @@ __global__ __launch_bounds__(512) void gemm_bf16_8ph_kernel(GemmArgs p) {
 // VAR 5: two phases of 32 MFMAs per K tile instead of four of 16 (half as many barriers and cluster ramps per MFMA):
 //     phase A   LDS reads W[0] W[1] A[0] (16)   MFMA (A0,W0) (A0,W1)   DMA W[0] A[1] of K tile t+1 (other buffer)
 //     phase B   LDS reads A[1] (8)              MFMA (A1,W1) (A1,W0)   DMA W[1] A[0] of K tile t+2 (this buffer)
-// (4 + 4 LDS-DMA pieces per wave; UV_REBAL 0 = the schedule of rounds 2-5 with 2 + 6: A[1] of t+1 | W[0] W[1] A[0] of t+2.)
+// W[0] of K tile t+1 is staged in phase A of K tile t, into the other buffer beside A[1], so that each phase issues 4 LDS-DMA
+// pieces per wave (4 + 4) instead of 2 + 6.
 // A half-tile is restaged only after BOTH wave groups have retired their reads of it: the second group runs one barrier behind the
 // first, so a piece staged in front of a phase's first barrier may only overwrite what was last read a whole phase earlier - W[0] of the
 // OTHER buffer (read in phase A of the previous K tile) qualifies in phase A, W[0] of this buffer does not. Each phase waits on a counted
@@ -729,7 +723,7 @@ __global__ __launch_bounds__(512) void gemm_bf16_8ph_kernel(GemmArgs p) {
 #define UV_KTILE5X(K1, K2, B, O, ST1, ST2)                                                        \
     UV_RD_W(B, 0, w0) UV_RD_W(B, 1, w1) UV_RD_A(B, 0)                                             \
     if (ST1) {                                                                                    \
-        if (UV_REBAL) UV_STAGE(w_src[0], K1, (O) * BUF + 2 * HALF)                                \
+        UV_STAGE(w_src[0], K1, (O) * BUF + 2 * HALF)                                              \
         UV_STAGE(a_src[1], K1, (O) * BUF + HALF)                                                  \
         asm volatile("s_waitcnt vmcnt(8)" ::: "memory");                                          \
     } else {                                                                                      \
@@ -741,11 +735,9 @@ __global__ __launch_bounds__(512) void gemm_bf16_8ph_kernel(GemmArgs p) {
     __builtin_amdgcn_s_setprio(0); UV_SCHED(); UV_SB();                                           \
     UV_RD_A(B, 1)                                                                                 \
     if (ST2) {                                                                                    \
-        if (!UV_REBAL) UV_STAGE(w_src[0], K2, (B) * BUF + 2 * HALF)                               \
         UV_STAGE(w_src[1], K2, (B) * BUF + 3 * HALF)                                              \
         UV_STAGE(a_src[0], K2, (B) * BUF)                                                         \
-        if (UV_REBAL) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");                            \
-        else asm volatile("s_waitcnt vmcnt(8)" ::: "memory");                                     \
+        asm volatile("s_waitcnt vmcnt(6)" ::: "memory");                                          \
     } else if (ST1) {                                                                             \
         asm volatile("s_waitcnt vmcnt(2)" ::: "memory");                                          \
     } else {                                                                                      \
@@ -759,12 +751,10 @@ __global__ __launch_bounds__(512) void gemm_bf16_8ph_kernel(GemmArgs p) {
     if constexpr (VAR == 5) { UV_KTILE5(T, B, O, ST1, ST2) } else { UV_KTILE0(T, B, O, ST1, ST2) }
 
     if constexpr (VAR == 5) {
-        // prologue: W0 W1 A0 A1 of K tile 0, W0 W1 A0 of K tile 1; vmcnt(8) = W0 W1 A0 of K tile 0 landed
+        // prologue: W0 W1 A0 A1 of K tile 0, W1 A0 of K tile 1; vmcnt(6) = W0 W1 A0 of K tile 0 landed
         UV_STAGE(w_src[0], 0, 2 * HALF) UV_STAGE(w_src[1], 0, 3 * HALF) UV_STAGE(a_src[0], 0, 0) UV_STAGE(a_src[1], 0, HALF)
-        if (!UV_REBAL) UV_STAGE(w_src[0], 1, BUF + 2 * HALF)
         UV_STAGE(w_src[1], 1, BUF + 3 * HALF) UV_STAGE(a_src[0], 1, BUF)
-        if (UV_REBAL) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+        asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
     } else {
         // prologue: K tile 0 (W0 A0 W1 A1) and W0 A0 W1 of K tile 1; vmcnt(6) = K tile 0 landed
         UV_STAGE(w_src[0], 0, 2 * HALF) UV_STAGE(a_src[0], 0, 0) UV_STAGE(w_src[1], 0, 3 * HALF) UV_STAGE(a_src[1], 0, HALF)
@@ -970,12 +960,10 @@ __global__ __launch_bounds__(512) void gemm_bf16_8ph_persist_kernel(GemmArgs p) 
     bool fresh = true;               // the next K loop needs the prologue (first tile; every tile of the LDS-staged epilogues)
     for (;;) {
         if (fresh) {
-            // prologue: W0 W1 A0 A1 of K tile 0, W0 W1 A0 of K tile 1; vmcnt(8) = W0 W1 A0 of K tile 0 landed
+            // prologue: W0 W1 A0 A1 of K tile 0, W1 A0 of K tile 1; vmcnt(6) = W0 W1 A0 of K tile 0 landed
             UV_STAGE(w_src[0], 0, 2 * HALF) UV_STAGE(w_src[1], 0, 3 * HALF) UV_STAGE(a_src[0], 0, 0) UV_STAGE(a_src[1], 0, HALF)
-            if (!UV_REBAL) UV_STAGE(w_src[0], 1, BUF + 2 * HALF)
             UV_STAGE(w_src[1], 1, BUF + 3 * HALF) UV_STAGE(a_src[0], 1, BUF)
-            if (UV_REBAL) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-            else asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+            asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
             UV_SB();
         }
         fresh = RMW;
@@ -1005,13 +993,12 @@ __global__ __launch_bounds__(512) void gemm_bf16_8ph_persist_kernel(GemmArgs p) 
         }
         if constexpr (!RMW) {
             // K tiles nk-2 and nk-1 of this output tile, ONE code path for every tile (a second copy of the MFMA schedule behind
-            // a branch makes hipcc shuttle all 128 accumulators through copies and spill): staged meanwhile are A[1] of K tile
-            // nk-1 (old pointer) and then K tiles 0 and 1 of the next output tile. The workgroup's last tile "prefetches" its own
+            // a branch makes hipcc shuttle all 128 accumulators through copies and spill): staged meanwhile are W[0] A[1] of K tile
+            // nk-1 (old pointers) and then K tiles 0 and 1 of the next output tile. The workgroup's last tile "prefetches" its own
             // first K tiles again (dA = dW = 0: 128 KiB of harmless loads, drained before the workgroup ends).
-            if (!UV_REBAL) move_ptrs(w_src[0], dW);
             move_ptrs(w_src[1], dW); move_ptrs(a_src[0], dA);
             UV_KTILE5X(nk - 1, 0, 0, 1, true, true)
-            if (UV_REBAL) move_ptrs(w_src[0], dW);      // (W[0] travels with A[1]: phase A's pieces belong to the K tile after this one)
+            move_ptrs(w_src[0], dW);      // (W[0] travels with A[1]: phase A's pieces belong to the K tile after this one)
             move_ptrs(a_src[1], dA);
             UV_KTILE5X(0, 1, 1, 0, true, true)
         } else {
@@ -1065,35 +1052,48 @@ __global__ __launch_bounds__(512) void gemm_bf16_8ph_persist_kernel(GemmArgs p) 
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
+// ---- host side: one launcher, one epilogue dispatch, and the argument checks of each kernel family ----
+
+// Launches KERN: its dynamic-LDS limit is raised once per device; a launch error is reported under the entry point's name `who`.
+template <void (*KERN)(GemmArgs)>
+static int launch_kernel(dim3 grid, dim3 block, size_t lds, hipStream_t stream, const GemmArgs& a, const char* who) {
+    UV_ONCE_PER_DEVICE(hipFuncSetAttribute((const void*)KERN, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(KERN, grid, block, lds, stream, a);
+    UV_CHECK_LAUNCH(who);
+    return 0;
+}
+
+// Turns the run-time epilogue into a compile-time one: calls launch(epi_c<E>()) for E == epi. EPIS is the bit mask of
+// the epilogues the caller's kernel family is built for (no other instance is named, so none is compiled); callers whose family lacks
+// some report that in their own words first.
+constexpr unsigned UV_EPIS_ALL = 0x7f;
+constexpr bool epi_in(unsigned epis, int e) { return e >= 0 && e < 32 && (epis >> e & 1) != 0; }
+template <int E>
+using epi_c = std::integral_constant<int, E>;
+template <unsigned EPIS = UV_EPIS_ALL, class Launch>
+static int launch_epi(int epi, Launch&& launch) {
+    switch (epi) {
+        case UV_EPI_BF16: if constexpr (epi_in(EPIS, UV_EPI_BF16)) return launch(epi_c<UV_EPI_BF16>()); break;
+        case UV_EPI_GELU_BF16: if constexpr (epi_in(EPIS, UV_EPI_GELU_BF16)) return launch(epi_c<UV_EPI_GELU_BF16>()); break;
+        case UV_EPI_F32_FROM_BF16: if constexpr (epi_in(EPIS, UV_EPI_F32_FROM_BF16)) return launch(epi_c<UV_EPI_F32_FROM_BF16>()); break;
+        case UV_EPI_RESID_F32: if constexpr (epi_in(EPIS, UV_EPI_RESID_F32)) return launch(epi_c<UV_EPI_RESID_F32>()); break;
+        case UV_EPI_GATE_RESID_F32: if constexpr (epi_in(EPIS, UV_EPI_GATE_RESID_F32)) return launch(epi_c<UV_EPI_GATE_RESID_F32>()); break;
+        case UV_EPI_BF16_T: if constexpr (epi_in(EPIS, UV_EPI_BF16_T)) return launch(epi_c<UV_EPI_BF16_T>()); break;
+        case UV_EPI_BF16_SSQ: if constexpr (epi_in(EPIS, UV_EPI_BF16_SSQ)) return launch(epi_c<UV_EPI_BF16_SSQ>()); break;
+    }
+    uv_set_error("uv_gemm_bf16_nt: unknown epilogue %d", epi);
+    return -1;
+}
+
 template <int VAR = 0, bool F16 = false>
 static int launch_8ph(const GemmArgs& a0, int epi, hipStream_t stream) {
     GemmArgs a = a0;
     a.tiles_m = (a.M + 255) / 256;
     a.tiles_n = (a.N + 255) / 256;
-    const dim3 grid(a.tiles_m * a.tiles_n), block(512);
-    const size_t lds = 128 * 1024;
-#define UV_LAUNCH8(E)                                                                              \
-    case E: {                                                                                      \
-        auto kern = gemm_bf16_8ph_kernel<E, VAR, F16>;                                               \
-        UV_ONCE_PER_DEVICE(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));  \
-        hipLaunchKernelGGL(kern, grid, block, lds, stream, a);                                     \
-        break;                                                                                     \
-    }
-    switch (epi) {
-        UV_LAUNCH8(UV_EPI_BF16)
-        UV_LAUNCH8(UV_EPI_GELU_BF16)
-        UV_LAUNCH8(UV_EPI_F32_FROM_BF16)
-        UV_LAUNCH8(UV_EPI_RESID_F32)
-        UV_LAUNCH8(UV_EPI_GATE_RESID_F32)
-        UV_LAUNCH8(UV_EPI_BF16_T)
-        UV_LAUNCH8(UV_EPI_BF16_SSQ)
-        default:
-            uv_set_error("uv_gemm_bf16_nt: unknown epilogue %d", epi);
-            return -1;
-    }
-#undef UV_LAUNCH8
-    UV_CHECK_LAUNCH("uv_gemm_bf16_nt");
-    return 0;
+    const dim3 grid(a.tiles_m * a.tiles_n);
+    return launch_epi(epi, [&](auto e) {
+        return launch_kernel<gemm_bf16_8ph_kernel<decltype(e)::value, VAR, F16>>(grid, 512, 128 * 1024, stream, a, "uv_gemm_bf16_nt");
+    });
 }
 
 // Split-K launch of the one-tile-per-workgroup ping-pong kernel (see gemm_bf16_8ph_kernel<.., SK>): workspace = [4 KiB of tile counters]
@@ -1110,33 +1110,19 @@ static int launch_8ph_splitk(const GemmArgs& a0, int epi, hipStream_t stream, vo
     UV_CHECK_ARG(tiles <= 1024, "uv_gemm_bf16_nt_ws: split-K serves leftover strips (at most 1024 tiles; %d here)", tiles);
     UV_CHECK_ARG(ws && ((uintptr_t)ws & 255) == 0 && ws_bytes >= splitk_ws_bytes(a.M, a.N, SK),
                  "uv_gemm_bf16_nt_ws: workspace of %ld bytes (256-byte aligned) needed, %ld given", splitk_ws_bytes(a.M, a.N, SK), ws_bytes);
+    constexpr unsigned EPIS = 1u << UV_EPI_BF16 | 1u << UV_EPI_RESID_F32 | 1u << UV_EPI_GATE_RESID_F32;
+    UV_CHECK_ARG(epi_in(EPIS, epi),
+                 "uv_gemm_bf16_nt_ws: the split-K strip is built for the bf16 and the residual epilogues (0, 3, 4), not %d", epi);
     a.ws_cnt = (int*)ws;
     a.ws_slab = (float*)((char*)ws + 4096);
     if (hipMemsetAsync(a.ws_cnt, 0, (size_t)tiles * sizeof(int), stream) != hipSuccess) {
         uv_set_error("uv_gemm_bf16_nt_ws: hipMemsetAsync of the tile counters failed");
         return -1;
     }
-    const int per = a.gm == 0 ? (tiles * SK + 7) / 8 : (tiles + 8 / SK - 1) / (8 / SK);
-    const dim3 grid(8 * per), block(512);
-    const size_t lds = 128 * 1024;
-#define UV_LAUNCH8S(E)                                                                             \
-    case E: {                                                                                      \
-        auto kern = gemm_bf16_8ph_kernel<E, 5, F16, SK>;                                           \
-        UV_ONCE_PER_DEVICE(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));  \
-        hipLaunchKernelGGL(kern, grid, block, lds, stream, a);                                     \
-        break;                                                                                     \
-    }
-    switch (epi) {
-        UV_LAUNCH8S(UV_EPI_BF16)
-        UV_LAUNCH8S(UV_EPI_RESID_F32)
-        UV_LAUNCH8S(UV_EPI_GATE_RESID_F32)
-        default:
-            uv_set_error("uv_gemm_bf16_nt_ws: the split-K strip is built for the bf16 and the residual epilogues (0, 3, 4), not %d", epi);
-            return -1;
-    }
-#undef UV_LAUNCH8S
-    UV_CHECK_LAUNCH("uv_gemm_bf16_nt_ws");
-    return 0;
+    const dim3 grid(8 * ((tiles * SK + 7) / 8));      // whole groups of 8 workgroups: one per XCD
+    return launch_epi<EPIS>(epi, [&](auto e) {
+        return launch_kernel<gemm_bf16_8ph_kernel<decltype(e)::value, 5, F16, SK>>(grid, 512, 128 * 1024, stream, a, "uv_gemm_bf16_nt_ws");
+    });
 }
 
 template <bool F16 = false>
@@ -1155,30 +1141,10 @@ static int launch_8ph_persist(const GemmArgs& a0, int epi, hipStream_t stream) {
     int wgs = uv_num_cus() & ~7;
     if (wgs > tiles) wgs = tiles & ~7;
     UV_CHECK_ARG(wgs >= 8, "uv_gemm_bf16_nt: too few tiles (%d) for the persistent kernel", tiles);
-    const dim3 grid(wgs), block(512);
-    const size_t lds = 128 * 1024;
-#define UV_LAUNCH8P(E)                                                                             \
-    case E: {                                                                                      \
-        auto kern = gemm_bf16_8ph_persist_kernel<E, F16>;                                          \
-        UV_ONCE_PER_DEVICE(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));  \
-        hipLaunchKernelGGL(kern, grid, block, lds, stream, a);                                     \
-        break;                                                                                     \
-    }
-    switch (epi) {
-        UV_LAUNCH8P(UV_EPI_BF16)
-        UV_LAUNCH8P(UV_EPI_GELU_BF16)
-        UV_LAUNCH8P(UV_EPI_F32_FROM_BF16)
-        UV_LAUNCH8P(UV_EPI_RESID_F32)
-        UV_LAUNCH8P(UV_EPI_GATE_RESID_F32)
-        UV_LAUNCH8P(UV_EPI_BF16_T)
-        UV_LAUNCH8P(UV_EPI_BF16_SSQ)
-        default:
-            uv_set_error("uv_gemm_bf16_nt: unknown epilogue %d", epi);
-            return -1;
-    }
-#undef UV_LAUNCH8P
-    UV_CHECK_LAUNCH("uv_gemm_bf16_nt");
-    return 0;
+    const dim3 grid(wgs);
+    return launch_epi(epi, [&](auto e) {
+        return launch_kernel<gemm_bf16_8ph_persist_kernel<decltype(e)::value, F16>>(grid, 512, 128 * 1024, stream, a, "uv_gemm_bf16_nt");
+    });
 }
 
 template <int BM, int BN, int WM, int WN, int NS = 2, bool F16 = false>
@@ -1186,38 +1152,10 @@ static int launch_cfg(const GemmArgs& a0, int epi, hipStream_t stream) {
     GemmArgs a = a0;
     a.tiles_m = (a.M + BM - 1) / BM;
     a.tiles_n = (a.N + BN - 1) / BN;
-    const dim3 grid(a.tiles_m * a.tiles_n), block(WM * WN * 64);
-    const size_t lds = NS * (BM + BN) * 128;
-#define UV_LAUNCH(E)                                                                               \
-    case E: {                                                                                      \
-        auto kern = gemm_bf16_nt_kernel<BM, BN, WM, WN, E, NS, F16>;                                \
-        UV_ONCE_PER_DEVICE(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));  \
-        hipLaunchKernelGGL(kern, grid, block, lds, stream, a);                                     \
-        break;                                                                                     \
-    }
-    switch (epi) {
-        UV_LAUNCH(UV_EPI_BF16)
-        UV_LAUNCH(UV_EPI_GELU_BF16)
-        UV_LAUNCH(UV_EPI_F32_FROM_BF16)
-        UV_LAUNCH(UV_EPI_RESID_F32)
-        UV_LAUNCH(UV_EPI_GATE_RESID_F32)
-        UV_LAUNCH(UV_EPI_BF16_T)
-        case UV_EPI_BF16_SSQ:
-            if constexpr ((BN / WN) % 32 == 0) {
-                auto kern = gemm_bf16_nt_kernel<BM, BN, WM, WN, UV_EPI_BF16_SSQ, NS, F16>;
-                UV_ONCE_PER_DEVICE(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                hipLaunchKernelGGL(kern, grid, block, lds, stream, a);
-                break;
-            } else {
-                uv_set_error("uv_gemm_bf16_nt_ssq: this tile shape has no whole 32-column groups per wave");
-                return -1;
-            }
-        default:
-            uv_set_error("uv_gemm_bf16_nt: unknown epilogue %d", epi);
-            return -1;
-    }
-#undef UV_LAUNCH
-    UV_CHECK_LAUNCH("uv_gemm_bf16_nt");
-    return 0;
+    constexpr bool SSQ = (BN / WN) % 32 == 0;      // a wave's columns hold whole 32-column groups
+    UV_CHECK_ARG(SSQ || epi != UV_EPI_BF16_SSQ, "uv_gemm_bf16_nt_ssq: this tile shape has no whole 32-column groups per wave");
+    const dim3 grid(a.tiles_m * a.tiles_n);
+    return launch_epi<SSQ ? UV_EPIS_ALL : UV_EPIS_ALL & ~(1u << UV_EPI_BF16_SSQ)>(epi, [&](auto e) {
+        return launch_kernel<gemm_bf16_nt_kernel<BM, BN, WM, WN, decltype(e)::value, NS, F16>>(grid, WM * WN * 64, NS * (BM + BN) * 128, stream, a, "uv_gemm_bf16_nt");
+    });
 }
-
