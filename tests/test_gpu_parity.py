@@ -2436,19 +2436,40 @@ def test_conv3d_kernel_geometries(entry):
     # the same layer as four 2x2 OUTPUT-PHASE launches (up = 2 + 2a + b) with the collapsed taps' weights summed beforehand
     T_, H_, W_ = 5, 6, 7
     x_cl = cl(x)
-    outp = torch.full((T_, 2 * H_, 2 * W_, 64), 7.0, device=DEV)
-    for a in (0, 1):
-        for b_ in (0, 1):
-            wq = _phase_weights(w2, a, b_).permute(0, 2, 3, 4, 1).reshape(64, -1).contiguous().to(DEV)
-            src, extra = x_cl, ()
-            if entry == "uv_conv3d_bf16x6":
-                wq = _split6(wq)
-            elif entry == "uv_conv3d_f16x3":
-                (wq, scale), src = _split_f16_weights(wq), _split_f16_acts(x_cl)
-                extra = (scale, None)
-            _lib.call(entry, _lib.ptr(src), 64, T_, H_, W_, _lib.ptr(wq), _lib.ptr(b2.to(DEV)), _lib.ptr(outp), 64, T_, H_, W_, 64, 64,
-                      1, 2, 2, 1, 1, 1, 0, 1 - a, 1 - b_, 2 + 2 * a + b_, 0, None, 0, *extra, _lib.stream_ptr())
-    assert_f32_close(outp.cpu().permute(3, 0, 1, 2), ref[0], rtol=1e-4, atol=1e-4, name="up as four output phases")
+
+    def phases(embed, reps):
+        """embed: each 2x2 phase kernel inside a 3x3 one, zeros elsewhere (tap i at padding 1 - a = tap i + a at padding 1); reps: the layer's
+        output channels that many times over"""
+        co = 64 * reps
+        outp = torch.full((T_, 2 * H_, 2 * W_, co), 7.0, device=DEV)
+        for a in (0, 1):
+            for b_ in (0, 1):
+                wq = _phase_weights(w2, a, b_)
+                if embed:
+                    w33 = torch.zeros(64, 64, 1, 3, 3)
+                    w33[:, :, :, a:a + 2, b_:b_ + 2] = wq
+                    wq = w33
+                k, pad = (3, (1, 1)) if embed else (2, (1 - a, 1 - b_))
+                wq = wq.repeat(reps, 1, 1, 1, 1).permute(0, 2, 3, 4, 1).reshape(co, -1).contiguous().to(DEV)
+                src, extra = x_cl, ()
+                if entry == "uv_conv3d_bf16x6":
+                    wq = _split6(wq)
+                elif entry == "uv_conv3d_f16x3":
+                    (wq, scale), src = _split_f16_weights(wq), _split_f16_acts(x_cl)
+                    extra = (scale, None)
+                _lib.call(entry, _lib.ptr(src), 64, T_, H_, W_, _lib.ptr(wq), _lib.ptr(b2.repeat(reps).to(DEV)), _lib.ptr(outp), co, T_, H_, W_, 64, co,
+                          1, k, k, 1, 1, 1, 0, pad[0], pad[1], 2 + 2 * a + b_, 0, None, 0, *extra, _lib.stream_ptr())
+        return outp.cpu().permute(3, 0, 1, 2)
+
+    assert_f32_close(phases(False, 1), ref[0], rtol=1e-4, atol=1e-4, name="up as four output phases")
+    # 3x3 taps, padding 1 and Hin == Hout are the LDS-halo kernels' geometry, but those store to plain positions: with the halo kernels forced on
+    # an output-phase launch must still take the gather kernel. 64 output channels as above, and 128 (whole output tiles of the halo kernels).
+    _lib.set_option(_lib.OPT_CONV_HALO, 1)
+    try:
+        for reps in (1, 2):
+            assert_f32_close(phases(True, reps), ref[0].repeat(reps, 1, 1, 1), rtol=1e-4, atol=1e-4, name=f"up as four 3x3 output phases, halo forced, Cout {64 * reps}")
+    finally:
+        _lib.set_option(_lib.OPT_CONV_HALO, -1)
     w3, b3 = torch.randn(128, 64, 3, 1, 1, generator=g) * 0.05, torch.randn(128, generator=g)
     y = F.conv3d(F.pad(x, (0, 0, 0, 0, 2, 0)), w3, b3)                                     # time_conv + interleave
     ref = torch.stack((y[:, :64], y[:, 64:]), 3).reshape(1, 64, 10, 6, 7)

@@ -46,12 +46,15 @@ typedef __attribute__((address_space(3))) void lds_void_c;
 // PREC 3: "bf16x6", f32-GRADE: every f32 operand is three bf16 planes (x = x0 + x1 + x2 exactly) and the product keeps the six
 //         terms with i + j <= 2 (error < 2^-26 |x w|, under f32's own rounding), f32 accumulate. Activations f32 in HBM/LDS, split in
 //         registers; weights pre-split on the host into [Cout][K/32][32 p0 | 32 p1 | 32 p2] bf16 and staged as three plane sub-tiles.
+// LDS bytes of one pipeline stage (the kernel holds two): BM rows of A and BN rows of W, 128 B each per k-tile; PREC 3 stages the weights as
+// three bf16 planes (64-byte rows, one [BN][64 B] sub-tile per plane) instead of f32 rows
+constexpr int conv_stage_bytes(int BM, int BN, int PREC) { return BM * 128 + BN * (PREC == 3 ? 192 : 128); }
+
 template <int BM, int BN, int WM, int WN, int PREC>
 __global__ __launch_bounds__(WM* WN * 64) void conv3d_f32_kernel(ConvArgs p) {
     constexpr int NW = WM * WN;
     constexpr int TM = BM / WM / 16, TN = BN / WN / 16;
-    // PREC 3 stages the weights as three bf16 planes (64-byte rows, one [BN][64 B] sub-tile per plane) instead of f32 rows
-    constexpr int A_BYTES = BM * 128, W_BYTES = PREC == 3 ? BN * 192 : BN * 128, STAGE = A_BYTES + W_BYTES;
+    constexpr int A_BYTES = BM * 128, STAGE = conv_stage_bytes(BM, BN, PREC), W_BYTES = STAGE - A_BYTES;
     constexpr int W_PIECES = PREC == 3 ? 3 * (BN / 16) : BN / 8;             // 1-KiB LDS-DMA pieces per W tile and k-tile
     constexpr int A_INSTR = BM / 8 / NW, W_INSTR = (W_PIECES + NW - 1) / NW;  // a narrow W tile (BN = 16) is staged by the first waves only
     static_assert(BM % (8 * NW) == 0, "A tile rows must divide over the waves");
@@ -359,13 +362,30 @@ __global__ __launch_bounds__(WM* WN * 64) void conv3d_f32_kernel(ConvArgs p) {
 const float* uv_zero_page();
 
 template <int BM, int BN, int WM, int WN, int PREC>
-static void launch_conv(ConvArgs& a, hipStream_t stream) {
-    a.tiles_m = (a.M + BM - 1) / BM;
-    a.tiles_n = (a.Cout + BN - 1) / BN;
-    auto kern = conv3d_f32_kernel<BM, BN, WM, WN, PREC>;
-    const size_t lds = 2 * (BM * 128 + BN * (PREC == 3 ? 192 : 128));
-    UV_ONCE_PER_DEVICE(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kern, dim3(a.tiles_m * a.tiles_n), dim3(WM * WN * 64), lds, stream, a);
+static void launch_conv(const ConvArgs& a, const ConvPlan& plan, hipStream_t stream) {
+    conv_launch<conv3d_f32_kernel<BM, BN, WM, WN, PREC>, WM * WN * 64, 2 * conv_stage_bytes(BM, BN, PREC)>(a, plan, stream);
+}
+
+// the gather kernel's 16 instantiations: plan.kernel = tile + PREC
+static void launch_conv_gather(const ConvArgs& a, const ConvPlan& plan, hipStream_t s) {
+    switch (plan.kernel) {
+        case G256x16 + 0: return launch_conv<256, 16, 4, 1, 0>(a, plan, s);
+        case G256x16 + 3: return launch_conv<256, 16, 4, 1, 3>(a, plan, s);
+        case G256x16 + 4: return launch_conv<256, 16, 4, 1, 4>(a, plan, s);
+        case G160 + 0: return launch_conv<128, 160, 2, 2, 0>(a, plan, s);
+        case G160 + 3: return launch_conv<64, 160, 2, 2, 3>(a, plan, s);
+        case G128x128 + 0: return launch_conv<128, 128, 2, 2, 0>(a, plan, s);
+        case G128x128 + 1: return launch_conv<128, 128, 2, 2, 1>(a, plan, s);
+        case G128x128 + 2: return launch_conv<128, 128, 2, 2, 2>(a, plan, s);
+        case G128x128 + 3: return launch_conv<128, 128, 2, 2, 3>(a, plan, s);
+        case G128x128 + 4: return launch_conv<128, 128, 2, 2, 4>(a, plan, s);
+        case G256x128 + 1: return launch_conv<256, 128, 4, 2, 1>(a, plan, s);
+        case G256x128 + 2: return launch_conv<256, 128, 4, 2, 2>(a, plan, s);
+        case G256x128 + 4: return launch_conv<256, 128, 4, 2, 4>(a, plan, s);
+        case G256x256 + 1: return launch_conv<256, 256, 4, 4, 1>(a, plan, s);
+        case G256x256 + 2: return launch_conv<256, 256, 4, 4, 2>(a, plan, s);
+        case G256x256 + 4: return launch_conv<256, 256, 4, 4, 4>(a, plan, s);
+    }
 }
 
 static int conv_common(const float* in, long ld_in, int Tin, int Hin, int Win, const void* w, const float* bias, float* out,
@@ -392,51 +412,10 @@ static int conv_common(const float* in, long ld_in, int Tin, int Hin, int Win, c
     a.M = Tout * Hout * Wout;
     a.out_scale = out_scale;
     a.act_scale = act_scale;
-    hipStream_t s = (hipStream_t)stream;
-    // the large 3x3(x3) stride-1 convolutions (ResidualBlocks): LDS-halo kernel (conv3d_halo.hip), exact f32 and bf16x6
-    if (uv_conv3d_halo_eligible(a, prec)) {
-        uv_launch_conv3d_halo(a, prec, s);
-        UV_CHECK_LAUNCH("uv_conv3d (halo)");
-        return 0;
-    }
-    if (prec == 4 && uv_conv3d_halo16_eligible(a)) {      // f16x3: its own LDS-halo kernel (pre-split operands, halo filled by LDS-DMA)
-        uv_launch_conv3d_halo16(a, s);
-        UV_CHECK_LAUNCH("uv_conv3d_f16x3 (halo)");
-        return 0;
-    }
-    // tile choice: 256x256 (16 waves, 4 per SIMD) when Cout >= 256 and the grid still fills the chip: halves the A gather
-    // per output; 256x128 (8 waves) next; the 4-wave 128x128 tile for the low-resolution stages
-    const long t256 = (long)((a.M + 255) / 256) * ((Cout + 255) / 256);
-    const long t128 = (long)((a.M + 255) / 256) * ((Cout + 127) / 128);
-    if (prec == 0) {
-        // exact f32: 128-wide column tiles, except where they would mostly compute padding:
-        //   Cout a multiple of 160 but not of 128 (the encoder's 160 / 320 channel stages): 160-wide tiles, no padded columns
-        //     (128-wide ones compute 256 columns for 160: 37.5 % of the MFMA work wasted; 384 for 320: 17 %);
-        //   Cout <= 16 (the decoder's last convolution, 256 -> 12 channels on full-resolution frames): 256 x 16 tiles
-        //     (a 128-wide tile computes 128 columns for 12).
-        if (Cout <= 16) launch_conv<256, 16, 4, 1, 0>(a, s);
-        else if (Cout % 160 == 0 && Cout % 128 != 0) launch_conv<128, 160, 2, 2, 0>(a, s);
-        else launch_conv<128, 128, 2, 2, 0>(a, s);
-    } else if (prec == 3) {
-        if (Cout <= 16) launch_conv<256, 16, 4, 1, 3>(a, s);
-        // 160-wide tiles carry 30 KiB of weight planes per stage: 64 rows keep two workgroups per CU (2 x 76 KiB of LDS)
-        else if (Cout % 160 == 0 && Cout % 128 != 0) launch_conv<64, 160, 2, 2, 3>(a, s);
-        else launch_conv<128, 128, 2, 2, 3>(a, s);
-    } else if (prec == 4) {
-        if (Cout <= 16) launch_conv<256, 16, 4, 1, 4>(a, s);
-        else if (Cout >= 256 && t256 >= 256) launch_conv<256, 256, 4, 4, 4>(a, s);
-        else if (t128 >= 256) launch_conv<256, 128, 4, 2, 4>(a, s);
-        else launch_conv<128, 128, 2, 2, 4>(a, s);
-    } else if (prec == 1) {
-        if (Cout >= 256 && t256 >= 256) launch_conv<256, 256, 4, 4, 1>(a, s);
-        else if (t128 >= 256) launch_conv<256, 128, 4, 2, 1>(a, s);
-        else launch_conv<128, 128, 2, 2, 1>(a, s);
-    } else {
-        if (Cout >= 256 && t256 >= 256) launch_conv<256, 256, 4, 4, 2>(a, s);
-        else if (t128 >= 256) launch_conv<256, 128, 4, 2, 2>(a, s);
-        else launch_conv<128, 128, 2, 2, 2>(a, s);
-    }
-    UV_CHECK_LAUNCH("uv_conv3d");
+    const ConvPlan plan = plan_conv(a, prec, uv_option(UV_OPT_CONV_HALO), uv_num_cus());
+    const bool halo16 = plan.kernel >= HALO_F16_N16, halo = !halo16 && plan.kernel >= HALO_BF16X6;
+    (halo16 ? launch_conv_halo16 : halo ? launch_conv_halo : launch_conv_gather)(a, plan, (hipStream_t)stream);
+    UV_CHECK_LAUNCH(halo16 ? "uv_conv3d_f16x3 (halo)" : halo ? "uv_conv3d (halo)" : "uv_conv3d");
     return 0;
 }
 

@@ -3,8 +3,8 @@
 //
 // Replaces (reference, fp32 nn.Conv3d through cuDNN): CausalConv3d.forward  models/wan/utils/modules/vae2_2.py:17-42 as used by
 // ResidualBlock (vae2_2.py:193-235); same arithmetic contract as conv3d_f32_kernel (conv3d_f32.hip), which keeps every other
-// geometry (1x1x1, strided, time_conv, Cout not a multiple of 16 x 8). Resample's "nearest-exact 2x + Conv2d 3x3" (vae2_2.py:86-96,
-// 153-155) runs here too: the halo image is filled through the upsampling map, the MFMA loop does not know.
+// geometry (1x1x1, strided, time_conv, Cout not a multiple of 16 x 8): plan_conv (conv_args.h) is the rule. Resample's "nearest-exact
+// 2x + Conv2d 3x3" (vae2_2.py:86-96, 153-155) runs here too: the halo image is filled through the upsampling map, the MFMA loop does not know.
 //
 // conv3d_f32_kernel gathers a 128-pixel x 32-channel A tile from L2 for EVERY tap (27 gathers of the same pixels per channel block).
 // Here a workgroup owns an 8 x 32 pixel patch of one frame and stages, once per (input frame dt, 32-channel block), the patch with
@@ -27,18 +27,23 @@ typedef __attribute__((address_space(3))) void lds_void_h;
 // BN = output channels per workgroup: 128, or 160 for the encoder's 160 / 320-channel stages (exact f32 only).
 // WBUF = weight buffers: 2 (next tap's weights land while this tap computes), or 1 - 39 KiB of LDS and <= 168 registers, THREE
 // workgroups per CU that cover each other's weight waits (exact f32, 128-wide tile).
+// LDS layout, shared by the kernel and its launcher: the halo image (8-row patch + one-pixel rim, padded to whole 8-pixel groups; three bf16
+// planes of 64-byte pixels for PREC 3, one of 128-byte f32 pixels for PREC 0), then WBUF weight tiles
+constexpr int halo_pixels(int TW) { return (8 + 2) * (TW + 2); }
+constexpr int halo_bytes(int PREC, int TW) { return (halo_pixels(TW) + 7) / 8 * 8 * (PREC == 3 ? 3 * 64 : 128); }
+constexpr int halo_w_bytes(int PREC, int BN) { return PREC == 3 ? BN * 192 : BN * 128; }
+constexpr int halo_lds_bytes(int PREC, int TW, int BN, int WBUF) { return halo_bytes(PREC, TW) + WBUF * halo_w_bytes(PREC, BN); }
+
 template <int PREC, int TW = 32, int BN = 128, int WBUF = 2>
 __global__ __launch_bounds__(TW * 16) __attribute__((amdgpu_waves_per_eu(WBUF == 1 ? 3 : 2, WBUF == 1 ? 3 : 2))) void conv3d_halo_kernel(ConvArgs p) {
     static_assert(PREC == 0 || PREC == 3, "exact-f32 MFMA or f32-grade bf16x6");
     static_assert(TW == 32 || TW == 16, "patch width");
-    constexpr int TH = 8, HW_ = TW + 2, NHP = (TH + 2) * HW_;                   // 340 / 180 halo pixels
+    constexpr int TH = 8, HW_ = TW + 2, NHP = halo_pixels(TW);                  // 340 / 180 halo pixels
     static_assert(BN == 128 || (BN == 160 && PREC == 0 && TW == 16), "output-channel tile");
     constexpr int NW = TW / 4, NT = NW * 64, TM = 4, TN = BN / 32;
-    constexpr int HALO_ROW = PREC == 3 ? 64 : 128;                              // bytes per halo pixel (per plane for PREC 3)
     constexpr int NHP8 = (NHP + 7) / 8 * 8;                                      // padded to whole 8-pixel groups
-    constexpr int HALO_PLANE = NHP8 * HALO_ROW;
-    constexpr int HALO_BYTES = (PREC == 3 ? 3 : 1) * HALO_PLANE;
-    constexpr int W_BYTES = PREC == 3 ? BN * 192 : BN * 128;
+    constexpr int HALO_BYTES = halo_bytes(PREC, TW), HALO_PLANE = HALO_BYTES / (PREC == 3 ? 3 : 1);
+    constexpr int W_BYTES = halo_w_bytes(PREC, BN);
     constexpr int W_PIECES = W_BYTES / 1024, W_INSTR = W_PIECES / NW;            // 16 / 24 pieces -> 2 / 3 per wave
     constexpr int NLD = (NHP * 8 + NT - 1) / NT;                                // sixteen-byte chunks of the halo per lane (6)
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -47,13 +52,8 @@ __global__ __launch_bounds__(TW * 16) __attribute__((amdgpu_waves_per_eu(WBUF ==
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave >> 1, wn = wave & 1;
-    const int tiles_w = (p.Wout + TW - 1) / TW, tiles_h = (p.Hout + TH - 1) / TH;
-    const int tile_n = blockIdx.x % p.tiles_n;
-    int mt = blockIdx.x / p.tiles_n;
-    const int tx0 = (mt % tiles_w) * TW;
-    mt /= tiles_w;
-    const int ty0 = (mt % tiles_h) * TH;
-    const int tf = mt / tiles_h;                                                 // output frame
+    int tile_n, tx0, ty0, tf;
+    conv_patch<TH, TW>(p, tile_n, tx0, ty0, tf);
     const int n0 = tile_n * BN;
     const int K = p.kt * 9 * p.Cin;
     const long frame = (long)p.Hin * p.Win * p.ld_in;
@@ -268,70 +268,20 @@ __global__ __launch_bounds__(TW * 16) __attribute__((amdgpu_waves_per_eu(WBUF ==
         for (int i = 0; i < TN; ++i) {
             const int n = n0 + wn * (BN / 2) + i * 16 + 4 * fq;
             if (n >= p.Cout) continue;
-            f32x4 v = acc[i][j];
-            if (p.bias) {
-                const f32x4 b = *(const f32x4*)(p.bias + n);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] += b[e];
-            }
-            if (p.resid) {
-                const f32x4 rr = *(const f32x4*)(p.resid + m * p.ldr + n);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] += rr[e];
-            }
-            *(f32x4*)(p.out + m * p.ldo + n) = v;
+            conv_epilogue<false>(p, acc[i][j], m, n, 1.f);
         }
     }
 }
 
-
-// Which convolutions take the halo kernel: 3x3 spatial taps, stride 1, padding 1 (plain or behind the 2x upsampling), no interleave, whole 32-channel input
-// blocks (all callers pad), whole 128-wide output-channel tiles, and enough tiles per frame to fill the chip at four frames per pass.
-// uv_set_option(UV_OPT_CONV_HALO, v) (developer A/B switch and test hook; never the environment): 0 = never, 1 = whenever the geometry
-// fits (also launches too small to fill the chip, which the tests use), -1 = automatic (default; both arithmetics).
-// output-channel tile of the halo kernel for this convolution (0: none fits): whole 128-wide tiles, or - exact f32 - whole 160-wide ones
-static int uv_conv3d_halo_bn(const ConvArgs& a, int prec) {
-    if (a.Cout % 128 == 0) return 128;
-    if (prec == 0 && a.Cout % 160 == 0) return 160;
-    return 0;
+template <int PREC, int TW, int BN, int WBUF>
+static void launch_halo(const ConvArgs& a, const ConvPlan& plan, hipStream_t stream) {
+    conv_launch<conv3d_halo_kernel<PREC, TW, BN, WBUF>, TW * 16, halo_lds_bytes(PREC, TW, BN, WBUF)>(a, plan, stream);
 }
 
-bool uv_conv3d_halo_eligible(const ConvArgs& a, int prec) {
-    const int force = uv_option(UV_OPT_CONV_HALO);
-    if (force == 0) return false;
-    if (!(prec == 0 || prec == 3)) return false;
-    if (a.kh != 3 || a.kw != 3 || (a.kt != 3 && a.kt != 1)) return false;
-    if (a.st != 1 || a.sh != 1 || a.sw != 1 || a.ph != 1 || a.pw != 1 || a.interleave) return false;
-    const int mul = a.up ? 2 : 1;                            // up: the halo image is filled through the 2x nearest-exact map
-    const int bn = uv_conv3d_halo_bn(a, prec);
-    if (a.Hin * mul != a.Hout || a.Win * mul != a.Wout || bn == 0 || a.Cin % 32 != 0) return false;
-    // per-FRAME tile count: the choice must not depend on how many frames a pass carries (the pass length is a memory / speed knob
-    // that leaves results bit-identical, and the two kernels sum their k-tiles in different orders)
-    // (exact f32: 8 x 16 patches on 4-wave workgroups, two per CU - 6.28 s against 6.43 s per 49 x 720 x 1280 decode on the gather kernel,
-    // same process, interleaved; the 8-wave form of round 3's first version lost to it, 6.49 s, with one workgroup per CU)
-    const long tiles = (long)((a.Hout + 7) / 8) * ((a.Wout + (prec == 3 ? 31 : 15)) / (prec == 3 ? 32 : 16)) * (a.Cout / bn);
-    return force == 1 || 4 * tiles >= (prec == 3 ? 1 : 2) * uv_num_cus();
-}
-
-int uv_launch_conv3d_halo(ConvArgs& a, int prec, hipStream_t stream) {
-    const int bn = uv_conv3d_halo_bn(a, prec);
-    a.tiles_n = a.Cout / bn;
-    if (prec == 3) {
-        a.tiles_m = a.Tout * ((a.Hout + 7) / 8) * ((a.Wout + 31) / 32);
-        const size_t lds = 3 * 344 * 64 + 2 * 128 * 192;
-        UV_ONCE_PER_DEVICE(hipFuncSetAttribute((const void*)conv3d_halo_kernel<3, 32>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL((conv3d_halo_kernel<3, 32>), dim3(a.tiles_m * a.tiles_n), dim3(512), lds, stream, a);
-    } else if (bn == 160) {
-        a.tiles_m = a.Tout * ((a.Hout + 7) / 8) * ((a.Wout + 15) / 16);
-        const size_t lds = 184 * 128 + 2 * 160 * 128;          // 63 KiB: two workgroups per CU
-        UV_ONCE_PER_DEVICE(hipFuncSetAttribute((const void*)conv3d_halo_kernel<0, 16, 160>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL((conv3d_halo_kernel<0, 16, 160>), dim3(a.tiles_m * a.tiles_n), dim3(256), lds, stream, a);
-    } else {
-        a.tiles_m = a.Tout * ((a.Hout + 7) / 8) * ((a.Wout + 15) / 16);
-        // single weight buffer: 39 KiB of LDS and 168 registers, three workgroups per CU (6.19-6.21 s against 6.26 s per decode with two
-        // double-buffered workgroups per CU, same process, interleaved, bit-identical: the k order is the same)
-        const size_t lds = 184 * 128 + 128 * 128;
-        hipLaunchKernelGGL((conv3d_halo_kernel<0, 16, 128, 1>), dim3(a.tiles_m * a.tiles_n), dim3(256), lds, stream, a);
+void launch_conv_halo(const ConvArgs& a, const ConvPlan& plan, hipStream_t stream) {
+    switch (plan.kernel) {
+        case HALO_BF16X6: return launch_halo<3, 32, 128, 2>(a, plan, stream);       // 112.5 KiB: one workgroup per CU
+        case HALO_F32_160: return launch_halo<0, 16, 160, 2>(a, plan, stream);      // 63 KiB: two
+        case HALO_F32_128: return launch_halo<0, 16, 128, 1>(a, plan, stream);      // 39 KiB: three
     }
-    return 0;
 }

@@ -6,7 +6,7 @@
 // ResidualBlock (vae2_2.py:193-235); arithmetic contract = conv3d_f32_kernel<.., 4> (x*w ~ xh*wh + xh*wl + xl*wh on
 // v_mfma_f32_16x16x32_f16, f32 accumulate, out = acc * out_scale + bias (+ residual)); only the k ORDER of the sum differs (taps inside a
 // channel block here, channel blocks inside a tap there), so the two agree to f32 summation noise, not bit for bit - the choice between
-// them depends on per-FRAME geometry only, never on the pass length (pass-length independence is bit-exact and tested).
+// them (plan_conv, conv_args.h) depends on per-FRAME geometry only, never on the pass length (pass-length independence is bit-exact and tested).
 //
 // Against conv3d_halo_kernel<3, 32> (bf16x6):
 //   * the activations arrive pre-split ([C/32][32 hi | 32 lo] fp16 per pixel = the 128 bytes of 32 f32 channels, written by
@@ -28,31 +28,32 @@ typedef __attribute__((address_space(3))) void lds_void_g;
 // ONE tap per step (two 20-KiB tiles: 126 KiB of LDS; two-tap steps would need 166 KiB) - the step length was measured not to matter (§9 round 4).
 // TW = patch width: 32 (8 x 32 patches) or 16 (16 x 16: for frames such as 45 x 80 that cut into fewer 16 x 16 than 8 x 32 patches - 15 against
 // 18; a pixel's sum runs over (channel block, tap) in the same order whatever the patch, so the results do not depend on it).
+// LDS layout, shared by the kernels and their launcher: two halo images (256-pixel patch + one-pixel rim in whole one-KiB pieces of 8 pixels x
+// 128 B), then two steps' weights: TAPS tiles of BN rows x 128 B each
+constexpr int halo16_pixels(int TW) { return (256 / TW + 2) * (TW + 2); }
+constexpr int halo16_image_bytes(int TW) { return (halo16_pixels(TW) + 7) / 8 * 1024; }
+constexpr int halo16_lds_bytes(int BN, int TAPS, int TW) { return 2 * halo16_image_bytes(TW) + 2 * TAPS * BN * 128; }
+
 template <int BN = 128, int TAPS = 2, int TW = 32>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void conv3d_halo_f16_kernel(ConvArgs p) {
-    constexpr int TH = 256 / TW, HW_ = TW + 2, NHP = (TH + 2) * HW_;         // 340 / 324 halo pixels
+    constexpr int TH = 256 / TW, HW_ = TW + 2, NHP = halo16_pixels(TW);      // 340 / 324 halo pixels
     constexpr int FPR = TW / 16, RPW = TH / 4;                               // 16-pixel fragments per patch row; patch rows per wave row group
     static_assert(TW == 32 || TW == 16, "patch width");
     constexpr int NW = 8, TM = 4, TN = BN / 32;
-    constexpr int H_PIECES = (NHP + 7) / 8;                                  // 43 one-KiB pieces (8 pixels x 128 B)
-    constexpr int HALO_BYTES = H_PIECES * 1024;                              // 44 032
+    constexpr int HALO_BYTES = halo16_image_bytes(TW), H_PIECES = HALO_BYTES / 1024;   // 43 / 41 one-KiB pieces (8 pixels x 128 B)
     constexpr int H_INSTR = (H_PIECES + NW - 1) / NW;                        // 6 (waves 0..2) / 5
     constexpr int W_BYTES = BN * 128, W_PIECES = W_BYTES / 1024, W_INSTR = (W_PIECES + NW - 1) / NW;   // 16 / 20 KiB: 2 / 2-3 pieces per wave
     static_assert(BN == 128 || BN == 160, "output-channel tile");
     static_assert(H_INSTR <= 6, "one halo piece per tap during taps 1..6");
+    static_assert(2 * HALO_BYTES + 2 * TAPS * W_BYTES == halo16_lds_bytes(BN, TAPS, TW), "LDS layout");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* const wbuf = smem + 2 * HALO_BYTES;         // 2 * TAPS weight tiles: two steps x TAPS taps
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave >> 1, wn = wave & 1;
-    const int tiles_w = (p.Wout + TW - 1) / TW, tiles_h = (p.Hout + TH - 1) / TH;
-    const int tile_n = blockIdx.x % p.tiles_n;
-    int mt = blockIdx.x / p.tiles_n;
-    const int tx0 = (mt % tiles_w) * TW;
-    mt /= tiles_w;
-    const int ty0 = (mt % tiles_h) * TH;
-    const int tf = mt / tiles_h;                                             // output frame
+    int tile_n, tx0, ty0, tf;
+    conv_patch<TH, TW>(p, tile_n, tx0, ty0, tf);
     const int n0 = tile_n * BN;
     const int K = p.kt * 9 * p.Cin;
     const long frame = (long)p.Hin * p.Win * p.ld_in;
@@ -194,20 +195,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         for (int i = 0; i < TN; ++i) {
             const int n = n0 + wn * (BN / 2) + i * 16 + 4 * fq;
             if (n >= p.Cout) continue;
-            f32x4 v = acc[i][j];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] *= out_scale;
-            if (p.bias) {
-                const f32x4 b = *(const f32x4*)(p.bias + n);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] += b[e];
-            }
-            if (p.resid) {
-                const f32x4 rr = *(const f32x4*)(p.resid + m * p.ldr + n);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] += rr[e];
-            }
-            *(f32x4*)(p.out + m * p.ldo + n) = v;
+            conv_epilogue<true>(p, acc[i][j], m, n, out_scale);
         }
     }
 }
@@ -221,10 +209,11 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 // fragment only), ~1 us per workgroup and group, an order of magnitude under the gather form's L2 traffic.
 // ------------------------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(512) void conv3d_halo_f16_n16_kernel(ConvArgs p) {
-    constexpr int TW = 32, TH = 8, HW_ = TW + 2, NHP = (TH + 2) * HW_;
+    constexpr int TW = 32, TH = 8, HW_ = TW + 2, NHP = halo16_pixels(TW);
     constexpr int NW = 8;
-    constexpr int H_PIECES = (NHP + 7) / 8, HALO_BYTES = H_PIECES * 1024, H_INSTR = (H_PIECES + NW - 1) / NW;
+    constexpr int HALO_BYTES = halo16_image_bytes(TW), H_PIECES = HALO_BYTES / 1024, H_INSTR = (H_PIECES + NW - 1) / NW;
     constexpr int W_BYTES = 9 * 16 * 128, W_PIECES = 18, W_INSTR = (W_PIECES + NW - 1) / NW;     // 18 KiB per group, 3 pieces for waves 0..1
+    static_assert(2 * HALO_BYTES + 2 * W_BYTES == halo16_lds_bytes(16, 9, TW), "LDS layout: a group's nine 16-row tiles as one step");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* const wbuf = smem + 2 * HALO_BYTES;
 
@@ -334,59 +323,11 @@ __global__ __launch_bounds__(512) void conv3d_halo_f16_n16_kernel(ConvArgs p) {
     }
 }
 
-// Which f16x3 convolutions take this kernel: the geometry rule of uv_conv3d_halo_eligible (3x3 spatial taps, stride 1, padding 1, plain or
-// behind the 2x upsampling, whole 32-channel input blocks and 128-wide output tiles) and enough tiles PER FRAME to fill the chip at four
-// frames per pass. uv_set_option(UV_OPT_CONV_HALO, 0 | 1) forces never / whenever the geometry fits, as for the other arithmetics.
-// 16 x 16 patches where a frame cuts into FEWER of them than 8 x 32 ones (45 x 80: 3 x 5 = 15 against 6 x 3 = 18; 360 x 640: 920 against 900). A
-// per-frame rule, and the results do not depend on the patch shape anyway (the kernel's note on TW).
-static bool halo16_square_patches(const ConvArgs& a) {
-    return (long)((a.Hout + 15) / 16) * ((a.Wout + 15) / 16) < (long)((a.Hout + 7) / 8) * ((a.Wout + 31) / 32);
-}
-
-bool uv_conv3d_halo16_eligible(const ConvArgs& a) {
-    const int force = uv_option(UV_OPT_CONV_HALO);
-    if (force == 0) return false;
-    if (a.kh != 3 || a.kw != 3 || (a.kt != 3 && a.kt != 1)) return false;
-    if (a.st != 1 || a.sh != 1 || a.sw != 1 || a.ph != 1 || a.pw != 1 || a.interleave) return false;
-    const int mul = a.up ? 2 : 1;
-    if (a.Hin * mul != a.Hout || a.Win * mul != a.Wout || a.Cin % 32 != 0) return false;
-    if (a.Cout <= 16) {      // the narrow-output kernel (the decoder's head): plain geometry only, Cout a multiple of 4
-        const long tiles = (long)((a.Hout + 7) / 8) * ((a.Wout + 31) / 32);
-        return !a.up && a.Cout % 4 == 0 && (force == 1 || 4 * tiles >= uv_num_cus());
+void launch_conv_halo16(const ConvArgs& a, const ConvPlan& plan, hipStream_t stream) {
+    switch (plan.kernel) {      // 122, 126, 146 and 150 KiB of LDS: one workgroup per CU
+        case HALO_F16_N16: return conv_launch<conv3d_halo_f16_n16_kernel, 512, halo16_lds_bytes(16, 9, 32)>(a, plan, stream);
+        case HALO_F16_160: return conv_launch<conv3d_halo_f16_kernel<160, 1, 32>, 512, halo16_lds_bytes(160, 1, 32)>(a, plan, stream);
+        case HALO_F16_SQUARE: return conv_launch<conv3d_halo_f16_kernel<128, 2, 16>, 512, halo16_lds_bytes(128, 2, 16)>(a, plan, stream);
+        case HALO_F16_128: return conv_launch<conv3d_halo_f16_kernel<128, 2, 32>, 512, halo16_lds_bytes(128, 2, 32)>(a, plan, stream);
     }
-    // 128-wide output tiles (two-tap steps pair the channel groups: even counts only), or whole 160-wide ones (the encoder's 160 / 320-channel stages)
-    const int bn = a.Cout % 128 == 0 ? 128 : a.Cout % 160 == 0 ? 160 : 0;
-    if (bn == 0 || (bn == 128 && ((a.kt * (a.Cin >> 5)) & 1))) return false;
-    const long patches = bn == 128 && halo16_square_patches(a) ? (long)((a.Hout + 15) / 16) * ((a.Wout + 15) / 16) : (long)((a.Hout + 7) / 8) * ((a.Wout + 31) / 32);
-    return force == 1 || 4 * patches * (a.Cout / bn) >= uv_num_cus();
-}
-
-int uv_launch_conv3d_halo16(ConvArgs& a, hipStream_t stream) {
-    if (a.Cout <= 16) {
-        a.tiles_n = 1;
-        a.tiles_m = a.Tout * ((a.Hout + 7) / 8) * ((a.Wout + 31) / 32);
-        const size_t lds = 2 * 43 * 1024 + 2 * 9 * 16 * 128;                  // two halo images + two 9-tap weight sets = 122 KiB
-        UV_ONCE_PER_DEVICE(hipFuncSetAttribute((const void*)conv3d_halo_f16_n16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(conv3d_halo_f16_n16_kernel, dim3(a.tiles_m), dim3(512), lds, stream, a);
-        return 0;
-    }
-    a.tiles_m = a.Tout * ((a.Hout + 7) / 8) * ((a.Wout + 31) / 32);
-    if (a.Cout % 128 != 0) {
-        a.tiles_n = a.Cout / 160;
-        const size_t lds160 = 2 * 43 * 1024 + 2 * 160 * 128;                 // two halo images + two 20-KiB weight tiles = 126 KiB
-        UV_ONCE_PER_DEVICE(hipFuncSetAttribute((const void*)conv3d_halo_f16_kernel<160, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds160));
-        hipLaunchKernelGGL((conv3d_halo_f16_kernel<160, 1>), dim3(a.tiles_m * a.tiles_n), dim3(512), lds160, stream, a);
-        return 0;
-    }
-    a.tiles_n = a.Cout / 128;
-    const size_t lds = 2 * 43 * 1024 + 4 * 128 * 128;                        // two halo images + four weight tiles = 150 KiB
-    if (halo16_square_patches(a)) {
-        a.tiles_m = a.Tout * ((a.Hout + 15) / 16) * ((a.Wout + 15) / 16);
-        UV_ONCE_PER_DEVICE(hipFuncSetAttribute((const void*)conv3d_halo_f16_kernel<128, 2, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL((conv3d_halo_f16_kernel<128, 2, 16>), dim3(a.tiles_m * a.tiles_n), dim3(512), lds, stream, a);
-        return 0;
-    }
-    UV_ONCE_PER_DEVICE(hipFuncSetAttribute((const void*)conv3d_halo_f16_kernel<128>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL((conv3d_halo_f16_kernel<128>), dim3(a.tiles_m * a.tiles_n), dim3(512), lds, stream, a);
-    return 0;
 }
