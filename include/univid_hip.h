@@ -124,6 +124,13 @@ int uv_flash_attn_f16(const void* q, long ldq, const void* k, long ldk, const vo
  * (selection depends on Lk, head_dim and the leading dimensions only); for benchmark / profile labels. Host-only. */
 int uv_flash_attn_kernel_name(int Lk, int head_dim, long ldk, long ldvt, int f16, char* buf, int len);
 
+/* The whole launch plan of uv_flash_attn_bf16 (f16 = 0) / uv_flash_attn_f16 (f16 = 1) for a problem, on the current device (256 compute
+ * units without one) and under the current UV_OPT_ATTN_CUT: the kernel's name as above, *q_blocks query blocks per (sample, head), of
+ * which the first *n12 own 12 units of 32 queries and the others 8 (flash_attn_fwd12_kernel; 0 for the other kernels, whose blocks own
+ * 128 queries), and *grid = q_blocks * H * batch workgroups. Host-only; for tests and tuning tools. */
+int uv_flash_attn_plan(int batch, int Lq, int Lk, int H, int head_dim, long ldk, long ldvt, int f16, char* kernel, int len,
+                       int* q_blocks, int* n12, int* grid);
+
 /* Operator-seam helpers: what flash_attention(q, k, v, ...) (attention.py:24-130) does around the core when it is handed
  * [B, L, N, C] tensors of any float dtype: `half(x)` casts (:59-83), and `.type(out_dtype)` of the result (:130); the
  * transpose produces the V^T operand of uv_flash_attn_* from token-major V rows.

@@ -489,6 +489,67 @@ def test_flash_attention_long_key_kernel(Lk):
     assert (out[:Lq].float() - 1).abs().max() <= 2 ** -7
 
 
+@pytest.mark.parametrize("H", [4, 2])
+def test_flash_attention_result_does_not_depend_on_the_block_cut(H):
+    """flash_attn_fwd12_kernel under every kind of query-block cut (OPT_ATTN_CUT; plan_attn, csrc/attn_args.h) at 16 units per head: the
+    automatic cut; 1 = two 12-unit blocks, the second with 4 units and 8 loader-only waves; 2 = one 12-unit block followed by one 8-unit
+    block; 3 = two 8-unit blocks. H = 4 (8 heads in total): both block totals divide by 8 and the kernel takes its XCD-aware order; H = 2:
+    the mixed cut's totals (4 + 4) do not, plain id order. All outputs bit-identical, one checked against the fp64 softmax, nothing
+    written past Lq."""
+    Lq, Lk, D, B = 500, 2104, 128, 2
+    C = H * D
+    g = torch.Generator(device=DEV).manual_seed(77 + H)
+    q = torch.randn(B * Lq, C, generator=g, device=DEV).to(BF16)
+    k = torch.randn(B * Lk, C, generator=g, device=DEV).to(BF16)
+    v = torch.randn(B * Lk, C, generator=g, device=DEV).to(BF16)
+    vt = torch.zeros(C, (B - 1) * Lk + (Lk + 63) // 64 * 64, dtype=BF16, device=DEV)
+    vt[:, :B * Lk] = v.t()
+    outs = {}
+    try:
+        for cut, blocks in ((0, None), (1, (2, 0)), (2, (1, 1)), (3, (0, 2))):
+            L().set_option(L().OPT_ATTN_CUT, cut)
+            plan = L().attn_plan(Lq, Lk, D, B, H)
+            assert plan["kernel"] == "flash_attn_fwd12_kernel" and plan["grid"] == plan["q_blocks"] * H * B
+            if blocks is not None:
+                assert (plan["n12"], plan["q_blocks"] - plan["n12"]) == blocks
+            out = torch.full((B * Lq + 8, C), 7.0, dtype=BF16, device=DEV)
+            L().flash_attn(q, k, vt, out, Lq, Lk, H, D, D ** -0.5, batch=B)
+            assert (out[B * Lq:] == 7.0).all(), f"cut {cut} wrote past Lq"
+            outs[cut] = out[:B * Lq]
+    finally:
+        L().reset_options()
+    for cut in (1, 2, 3):
+        assert torch.equal(outs[0].view(torch.int16), outs[cut].view(torch.int16)), f"cut {cut} changed the result"
+    for b in range(B):
+        qs, ks, vs = (t[b * n:(b + 1) * n].double().view(n, H, D).transpose(0, 1) for t, n in ((q, Lq), (k, Lk), (v, Lk)))
+        truth = (torch.softmax(qs @ ks.transpose(1, 2) / math.sqrt(D), -1) @ vs).transpose(0, 1).reshape(Lq, C)
+        err = (outs[1][b * Lq:(b + 1) * Lq].double() - truth).abs()
+        assert (err <= 3 * bf16_ulp(truth.float()) + 2e-3 * float(truth.abs().max())).all(), f"sample {b}: max err {float(err.max()):.3e}"
+
+
+@pytest.mark.parametrize("Lk,D", [(200, 128), (2104, 128), (200, 64)])
+def test_flash_attention_direct_store_epilogue(Lk, D):
+    """An output whose row stride is no multiple of 8 elements (ldo = C + 4: a view into a wider buffer, still 16-byte aligned) takes the
+    kernels' direct O-row store instead of the transpose through LDS - flash_attn_fwd3_kernel (Lk 200), flash_attn_fwd12_kernel (Lk 2104)
+    and flash_attn_fwd_kernel<64>, which has no other: bit-identical to the dense output, and neither the four columns between the rows
+    nor the rows past Lq (ragged last wave and workgroup at Lq = 150) are touched."""
+    Lq, H = 150, 2
+    C = H * D
+    g = torch.Generator(device=DEV).manual_seed(Lk + D)
+    q, k = (torch.randn(n, C, generator=g, device=DEV).to(BF16) for n in (Lq, Lk))
+    vt = torch.zeros(C, (Lk + 63) // 64 * 64, dtype=BF16, device=DEV)
+    vt[:, :Lk] = torch.randn(C, Lk, generator=g, device=DEV).to(BF16)
+    dense = torch.full((Lq + 8, C), 7.0, dtype=BF16, device=DEV)
+    L().flash_attn(q, k, vt, dense, Lq, Lk, H, D, D ** -0.5)
+    wide = torch.full((Lq + 8, C + 4), 7.0, dtype=BF16, device=DEV)
+    out = wide[:, :C]
+    assert out.stride(0) % 8 == 4 and out.data_ptr() % 16 == 0
+    L().flash_attn(q, k, vt, out, Lq, Lk, H, D, D ** -0.5)
+    assert torch.isfinite(dense[:Lq].float()).all() and (dense[Lq:] == 7.0).all()
+    assert torch.equal(out[:Lq].view(torch.int16), dense[:Lq].view(torch.int16))
+    assert (wide[:, C:] == 7.0).all() and (wide[Lq:] == 7.0).all()
+
+
 @pytest.mark.parametrize("Lq,Lk,B,scale,spike", [(2048, 2048, 1, 1.0, False), (2100, 2100, 1, 1.0, False), (700, 4000, 2, 1.0, False),
                                                  (3000, 2992, 2, 2.0, True), (11440, 11440, 2, 1.0, False)])
 def test_flash_attention_pw4_kernel_is_bit_identical_to_fwd12(Lq, Lk, B, scale, spike):

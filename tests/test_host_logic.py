@@ -589,6 +589,51 @@ def test_splitk_workspace_size_follows_the_gemm_plan():
         assert lib.uv_gemm_splitk_ws_bytes(M, N, K) == want, (M, N, K)
 
 
+def test_attention_launch_plan_is_pinned():
+    """uv_flash_attn_plan is plan_attn's (csrc/attn_args.h) externally visible output: the kernel, the query blocks per (sample, head), how
+    many of them own 12 units and the grid of an attention launch. Without a device the library plans for 256 CUs, which is also what an
+    MI355X reports. The numeric cuts are what the list-scheduling model gave before it moved into plan_attn."""
+    lib = _lib.load()
+    _lib.reset_options()
+
+    def plan(B, H, Lq, Lk, D=128, f16=False, ldk=None):
+        buf, qb, n12, grid = ctypes.create_string_buffer(96), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+        ldvt = (B - 1) * Lk + (Lk + 63) // 64 * 64
+        rc = lib.uv_flash_attn_plan(B, Lq, Lk, H, D, H * D if ldk is None else ldk, ldvt, int(f16), buf, 96, ctypes.byref(qb), ctypes.byref(n12),
+                                    ctypes.byref(grid))
+        assert rc == 0, lib.uv_last_error()
+        return buf.value.decode(), n12.value, qb.value - n12.value, grid.value        # kernel, n12, n8 (fwd12) / blocks of 128 queries, grid
+
+    F12, F3 = "flash_attn_fwd12_kernel", "flash_attn_fwd3_kernel"
+    assert plan(2, 24, 11440, 11440) == (F12, 26, 6, 1536)        # the bench shape
+    assert plan(1, 24, 11440, 11440) == (F12, 30, 0, 720)
+    assert plan(2, 24, 27280, 27280) == (F12, 69, 4, 3504)        # UniVid's default workload
+    assert plan(1, 24, 27280, 27280) == (F12, 72, 0, 1728)
+    assert plan(2, 2, 500, 2104) == (F12, 0, 2, 8)
+    assert plan(1, 24, 11440, 2047) == (F3, 0, 90, 90 * 24)       # one Lk below the threshold: 4-wave workgroups, ceil(Lq / 128) blocks
+    assert plan(1, 3, 129, 2047) == (F3, 0, 2, 6)
+    assert plan(1, 24, 11440, 2048)[0] == F12
+    assert plan(2, 4, 260, 2104, D=64) == ("flash_attn_fwd_kernel<64>", 0, 3, 24)
+    assert plan(2, 4, 260, 2104, f16=True) == ("flash_attn_fwd_kernel<128>", 0, 3, 24)
+    assert plan(1, 4, 260, 2104, ldk=1 << 24) == ("flash_attn_fwd_kernel<128>", 0, 3, 12)      # 64 * ldk >= 2^30: past the 32-bit lane offsets
+    assert plan(1, 4, 260, 2104, ldk=(1 << 24) - 8)[0] == F12
+    assert _lib.attn_plan(11440, 11440, 128, batch=2, H=24) == dict(kernel=F12, q_blocks=32, n12=26, grid=1536)
+    assert _lib.attn_kernel_name(11440, 512, 128, 2, H=24) == F3
+    try:
+        for Lq, H, B in ((11440, 24, 2), (500, 4, 2), (500, 2, 2), (33, 1, 1)):
+            nwu = -(-Lq // 32)
+            for v in (1, 2, 3, 4, 7, 45, 46, 60):
+                _lib.set_option(_lib.OPT_ATTN_CUT, v)
+                n8 = v - 1
+                n12 = max(0, -(-(nwu - 8 * n8) // 12))
+                assert plan(B, H, Lq, 2104) == (F12, n12, n8, (n12 + n8) * H * B), (Lq, v)
+                assert plan(B, H, Lq, 512)[1:] == (0, -(-Lq // 128), -(-Lq // 128) * H * B), "the option only concerns the 12-wave kernel"
+    finally:
+        _lib.reset_options()
+    assert plan(2, 24, 11440, 11440) == (F12, 26, 6, 1536)
+    assert lib.uv_flash_attn_plan(1, 0, 64, 1, 128, 128, 64, 0, ctypes.create_string_buffer(8), 8, None, None, None) != 0
+
+
 def test_graph_runner_cache_policy():
     """WanTI2V keeps the `max_graph_runners` most recently used captured graphs (host logic only - stand-ins for the runners; the replay
     itself is tests/test_gpu_parity.py::test_graph_runner_serves_new_prompts_without_recapture_and_never_goes_stale): a hit moves the

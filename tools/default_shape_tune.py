@@ -35,12 +35,14 @@ def timed(fn, n):
 
 cuts = [0] + [n8 + 1 for n8 in range(0, min(nwu // 8, 40) + 1)]
 res = {c: [] for c in cuts}
+plans = {}
 ref = None
 for r in range(rounds):
     for c in cuts:
         _lib.set_option(_lib.OPT_ATTN_CUT, c)
         res[c].append(timed(lambda: _lib.flash_attn(q, k, vt, out, L, L, H, D, 1 / math.sqrt(D), batch=B), 3))
         if r == 0:
+            plans[c] = _lib.attn_plan(L, L, D, B, H)      # what the library launches under this option value
             h = out.view(torch.int16).sum(dtype=torch.int64).item()
             ref = h if ref is None else ref
             assert h == ref, "the cut changed the result"
@@ -49,10 +51,9 @@ fl = B * 4.0 * L * L * C
 print(f"self-attention L={L} B={B}: nwu={nwu} units per head")
 for c in cuts:
     m = statistics.median(res[c])
-    n8 = c - 1
-    n12 = 0 if c == 0 else max(0, -(-(nwu - 8 * n8) // 12))
-    tag = "model's choice" if c == 0 else f"{n12} x 12 + {n8} x 8"
-    print(f"  cut {tag:>18}: {m:8.3f} ms  {fl / m / 1e9:7.1f} TF/s", flush=True)
+    n12, n8 = plans[c]["n12"], plans[c]["q_blocks"] - plans[c]["n12"]
+    tag = f"{n12} x 12 + {n8} x 8" + (" (model's choice)" if c == 0 else "")
+    print(f"  cut {tag:>34}: {m:8.3f} ms  {fl / m / 1e9:7.1f} TF/s", flush=True)
 
 M = B * L
 for name, N, K, epi in (("q", 3072, 3072, EPI_BF16), ("ffn.0", 14336, 3072, EPI_GELU_BF16), ("ffn.2-shape", 3072, 14336, EPI_BF16)):

@@ -15,7 +15,7 @@
 #include <vector>
 
 void uv_set_error(const char* fmt, ...) { printf("uv_set_error: %s\n", fmt); }
-int uv_launch_attn_pw4(const AttnArgs&, hipStream_t) { return -1; }
+int uv_option(int) { return 0; }      // the library's developer options (capi.hip): defaults
 
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("HIP error %s at %s:%d\n", hipGetErrorString(e_), __FILE__, __LINE__); exit(1); } } while (0)
 

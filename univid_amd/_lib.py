@@ -37,6 +37,7 @@ SIGNATURES = {
     "uv_flash_attn_bf16": [_P, _L, _P, _L, _P, _L, _P, _L, _I, _I, _I, _I, _I, _F, _P],
     "uv_flash_attn_f16": [_P, _L, _P, _L, _P, _L, _P, _L, _I, _I, _I, _I, _I, _F, _P],
     "uv_flash_attn_kernel_name": [_I, _I, _L, _L, _I, _c.c_char_p, _I],
+    "uv_flash_attn_plan": [_I, _I, _I, _I, _I, _L, _L, _I, _c.c_char_p, _I, _c.POINTER(_I), _c.POINTER(_I), _c.POINTER(_I)],
     "uv_transpose_16": [_P, _L, _P, _L, _I, _I, _I, _P],
     "uv_cast_f32_to16": [_P, _P, _L, _I, _P],
     "uv_cast_16_to_f32": [_P, _P, _L, _I, _P],
@@ -343,6 +344,18 @@ def attn_kernel_name(Lq, Lk, D, batch=1, H=None, f16=False):
     if rc != 0:
         raise UnividHipError(load().uv_last_error().decode())
     return buf.value.decode()
+
+
+def attn_plan(Lq, Lk, D, batch=1, H=1, f16=False):
+    """Launch plan of `flash_attn` for this geometry (dense [tokens, H*D] rows) on the current device - 256 CUs without one - under the
+    current OPT_ATTN_CUT: dict(kernel=name, q_blocks=blocks per (sample, head), n12=how many of them own 12 units, grid=workgroups)."""
+    buf = ctypes.create_string_buffer(96)
+    qb, n12, grid = _I(0), _I(0), _I(0)
+    ldvt = (batch - 1) * Lk + (Lk + 63) // 64 * 64
+    lib = load()
+    if lib.uv_flash_attn_plan(batch, Lq, Lk, H, D, H * D, ldvt, int(f16), buf, 96, ctypes.byref(qb), ctypes.byref(n12), ctypes.byref(grid)) != 0:
+        raise UnividHipError(lib.uv_last_error().decode())
+    return dict(kernel=buf.value.decode(), q_blocks=qb.value, n12=n12.value, grid=grid.value)
 
 
 def layernorm_mod(x, out, L, C, eps, mode=0, tab=None, shift_off=0, scale_off=0, tid=None, w=None, b=None,

@@ -10,7 +10,8 @@
 //   flash_attn_fwd12_kernel  head_dim 128, bf16, Lk >= 2048 (self-attention): one 12-wave workgroup per CU, up to 384 queries per K/V^T stream
 //   flash_attn_fwd3_kernel   head_dim 128, bf16, shorter Lk (cross-attention): three 4-wave workgroups per CU (48 KiB LDS, <= 168 registers)
 //   flash_attn_fwd_kernel    head_dim 64 / fp16 operands / very large leading dimensions: two 4-wave workgroups per CU (the first design)
-// attn_select() is the ONE place that decides which of them serves a call (uv_flash_attn_kernel_name reports it).
+// plan_attn() (attn_args.h) is the ONE place that decides which of them serves a call, on what query-block cut and on what grid
+// (uv_flash_attn_plan / uv_flash_attn_kernel_name report it); launch_attn() below is the one launch site.
 // Common structure (one wave = 32 queries of one head; staged KV tile = 64 keys):
 //   * swapped product S^T = K.Q^T with v_mfma_f32_32x32x16_bf16: the query sits on the lane, its
 //     32 keys of a tile sit in the 16 accumulator registers of both half-waves, so the softmax row
@@ -27,11 +28,9 @@
 //     is computed; one vmcnt(0) + one barrier per tile.
 //   * the softmax reference maximum moves only when a row maximum outgrows it by more than 2^UV_ATT_DEFER.
 //   * independent samples are one launch: q/k/out rows and V^T COLUMNS stacked per sample.
-// Template parameters of flash_attn_fwd_kernel: D head_dim (128 / 64), SGB fragment reads scheduled 6 ahead of their MFMA, F16 IEEE fp16 operands.
+// Template parameters: D head_dim (128 / 64; at 128 flash_attn_fwd_kernel schedules its fragment reads 6 ahead of their MFMA), F16 IEEE fp16
+// operands, QN 1 = WanRMSNorm of the raw q projection in the Q prologue.
 #include "attn_args.h"
-#ifndef UV_ATTN_PROBE
-#define UV_ATTN_PROBE 0      // 1 / 2: timing-only LDS-read probes of flash_attn_fwd12_kernel, built only by tools/diag/build_attn_probe.py
-#endif
 #include <stdio.h>
 #include <stdlib.h>
 #include <type_traits>
@@ -54,7 +53,7 @@ typedef __attribute__((address_space(3))) void lds_void_a;
 // 4 waves x 32 queries per workgroup, 2 workgroups per CU: the two waves that share a SIMD then belong to DIFFERENT workgroups, are
 // not re-aligned by a common barrier every tile, and drift into complementary phases - one in its MFMA cluster while the other
 // does softmax VALU work.
-template <int D, bool SGB = false, bool F16 = false, int QN = 0>
+template <int D, bool F16 = false, int QN = 0>
 __global__ __launch_bounds__(256, 2) void flash_attn_fwd_kernel(AttnArgs p) {
     static_assert(!F16 || QN == 0, "the fused q-norm prologue is built for bf16 only");
     constexpr int NW = 4;
@@ -77,14 +76,7 @@ __global__ __launch_bounds__(256, 2) void flash_attn_fwd_kernel(AttnArgs p) {
     const int bh = blockIdx.x / p.q_blocks;
     const int qb = blockIdx.x - bh * p.q_blocks;
     const int head = bh % p.H;
-    {   // independent samples are stacked along the token axis: rows of q/k/out, COLUMNS of V^T
-        const long b = bh / p.H;
-        p.q += b * p.Lq * p.ldq;
-        if (QN) p.q_rs += b * p.Lq;
-        p.k += b * p.Lk * p.ldk;
-        p.vt += (long)b * p.Lk;
-        p.out += b * p.Lq * p.ldo;
-    }
+    attn_sample_offset<QN>(p, bh / p.H);
     const int q0w = qb * (NW * UV_ATT_QW) + wave * UV_ATT_QW;
     const long hcol = (long)head * D;
 
@@ -221,7 +213,7 @@ __global__ __launch_bounds__(256, 2) void flash_attn_fwd_kernel(AttnArgs p) {
             }
         }
 
-        if constexpr (SGB && D == 128) {   // fragment reads 6 ahead of the MFMA that consumes them
+        if constexpr (D == 128) {   // fragment reads 6 ahead of the MFMA that consumes them
             __builtin_amdgcn_sched_group_barrier(0x100, 6, 0);
 #pragma unroll
             for (int i_ = 0; i_ < 10; ++i_) {
@@ -291,7 +283,7 @@ __global__ __launch_bounds__(256, 2) void flash_attn_fwd_kernel(AttnArgs p) {
             l_run += psum;
 
             // ---- O^T += V^T . P^T
-            if constexpr (SGB && D == 128) __builtin_amdgcn_sched_barrier(0);
+            if constexpr (D == 128) __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int d = 0; d < ND; ++d)
 #pragma unroll
@@ -304,7 +296,7 @@ __global__ __launch_bounds__(256, 2) void flash_attn_fwd_kernel(AttnArgs p) {
                     }
         }
 
-        if constexpr (SGB && D == 128) {
+        if constexpr (D == 128) {
             __builtin_amdgcn_sched_group_barrier(0x100, 6, 1);
 #pragma unroll
             for (int i_ = 0; i_ < 10; ++i_) {
@@ -328,17 +320,7 @@ __global__ __launch_bounds__(256, 2) void flash_attn_fwd_kernel(AttnArgs p) {
         const float l_tot = l_half + __shfl_xor(l_half, 32, 64);
         const float inv = 1.0f / l_tot;
         const int q = q0w + r;
-        if (q < p.Lq) {
-            bf16_t* op = p.out + (long)q * p.ldo + hcol + 4 * h;
-#pragma unroll
-            for (int d = 0; d < ND; ++d)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    u32x2 o = {pack16_2<F16>(oacc[d][4 * g + 0] * inv, oacc[d][4 * g + 1] * inv),
-                               pack16_2<F16>(oacc[d][4 * g + 2] * inv, oacc[d][4 * g + 3] * inv)};
-                    *(u32x2*)(op + 32 * d + 8 * g) = o;
-                }
-        }
+        if (q < p.Lq) attn_store_direct<F16, ND>(p.out + (long)q * p.ldo + hcol + 4 * h, oacc, inv);
     }
 }
 
@@ -367,8 +349,9 @@ __device__ __forceinline__ void glds16_sbase(const char* sbase, unsigned voff, u
                  : "memory");
 }
 
-// AHEAD = fragment reads in flight ahead of their MFMA (2 .. 5 measured: all within 0.5 %); XCD = XCD-aware block order (A/B knob).
-template <int AHEAD = 3, bool XCD = true, int QN = 0>
+constexpr int UV_ATT_AHEAD = 3;      // fwd3 / fwd12: fragment reads in flight ahead of their MFMA (2 .. 5 measured: all within 0.5 %)
+
+template <int QN = 0>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void flash_attn_fwd3_kernel(AttnArgs p) {
     constexpr int D = 128, NW = 4, KROW = 256, NKK = 8, ND = 4;
     constexpr int K_BYTES = UV_ATT_KV * KROW, V_BYTES = D * 128;
@@ -385,7 +368,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
     // each head's K / V^T is pulled into all 8 L2s. Remapped, XCD x works through the contiguous range [x NB/8, (x+1) NB/8) of
     // (sample, head, q-block) ids: one or two heads at a time per L2, each head in one L2 only.
     int vb = blockIdx.x;
-    if constexpr (XCD) {
+    {
         const int nb = gridDim.x, per = nb >> 3, rem = nb & 7;
         const int x = vb & 7, j = vb >> 3;
         // XCD x owns per + (x < rem) ids; its range starts after the ranges of XCDs 0 .. x-1
@@ -394,14 +377,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
     const int bh = vb / p.q_blocks;
     const int qb = vb - bh * p.q_blocks;
     const int head = bh % p.H;
-    {
-        const long b = bh / p.H;
-        p.q += b * p.Lq * p.ldq;
-        if (QN) p.q_rs += b * p.Lq;
-        p.k += b * p.Lk * p.ldk;
-        p.vt += (long)b * p.Lk;
-        p.out += b * p.Lq * p.ldo;
-    }
+    attn_sample_offset<QN>(p, bh / p.H);
     const int q0w = qb * (NW * UV_ATT_QW) + wave_u * UV_ATT_QW;
     const long hcol = (long)head * D;
     UV_TL(vb, 0);
@@ -454,15 +430,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
     const unsigned smem_a = (unsigned)(uintptr_t)(lds_void_a*)smem;
     unsigned kaddr[NKK];
     unsigned vaddr[2][2];
-    {
-        const int k_key = r & 15, v_key = (r >> 1) & 7;
-#pragma unroll
-        for (int kk = 0; kk < NKK; ++kk) kaddr[kk] = smem_a + r * KROW + (((2 * kk + h) ^ k_key) << 4);
-#pragma unroll
-        for (int T = 0; T < 2; ++T)
-#pragma unroll
-            for (int s2 = 0; s2 < 2; ++s2) vaddr[T][s2] = smem_a + V_OFF + r * 128 + (((4 * T + 2 * s2 + h) ^ v_key) << 4);
-    }
+    attn_frag_addrs(smem_a, V_OFF, r, h, kaddr, vaddr);
 
     f32x16 oacc[ND];
 #pragma unroll
@@ -516,13 +484,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
                 const bf16x8 kf = *(lds_frag_p)(kaddr[kk] + PAR * K_BYTES + T * 32 * KROW);
                 sacc = mfma_32x32x16<false>(kf, qf[kk], sacc);
             }
-            __builtin_amdgcn_sched_group_barrier(0x100, AHEAD, 0);      // fragment reads AHEAD ahead of their MFMAs
+            __builtin_amdgcn_sched_group_barrier(0x100, UV_ATT_AHEAD, 0);      // fragment reads UV_ATT_AHEAD ahead of their MFMAs
 #pragma unroll
-            for (int i_ = 0; i_ < 8 - AHEAD; ++i_) {
+            for (int i_ = 0; i_ < 8 - UV_ATT_AHEAD; ++i_) {
                 __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
                 __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
             }
-            __builtin_amdgcn_sched_group_barrier(0x008, AHEAD, 0);
+            __builtin_amdgcn_sched_group_barrier(0x008, UV_ATT_AHEAD, 0);
             __builtin_amdgcn_sched_barrier(0);
             if (T == 0) {
                 // K(t+1) into the other K buffer (every wave left tile t-1, its last reader, before the barrier that opened tile t)
@@ -586,13 +554,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
                     const bf16x8 vf = *(lds_frag_p)(vaddr[T][s2] + d * 32 * 128);
                     oacc[d] = mfma_32x32x16<false>(vf, pf[s2], oacc[d]);
                 }
-            __builtin_amdgcn_sched_group_barrier(0x100, AHEAD, 1);
+            __builtin_amdgcn_sched_group_barrier(0x100, UV_ATT_AHEAD, 1);
 #pragma unroll
-            for (int i_ = 0; i_ < 8 - AHEAD; ++i_) {
+            for (int i_ = 0; i_ < 8 - UV_ATT_AHEAD; ++i_) {
                 __builtin_amdgcn_sched_group_barrier(0x008, 1, 1);
                 __builtin_amdgcn_sched_group_barrier(0x100, 1, 1);
             }
-            __builtin_amdgcn_sched_group_barrier(0x008, AHEAD, 1);
+            __builtin_amdgcn_sched_group_barrier(0x008, UV_ATT_AHEAD, 1);
             __builtin_amdgcn_sched_barrier(0);
         }
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");          // this wave's share of K(t+1); own LDS reads retired
@@ -640,15 +608,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
             if (q0w + row < p.Lq) *(u32x4*)(p.out + (long)(q0w + row) * p.ldo + hcol + chunk * 8) = v;
         }
     } else if (q < p.Lq) {
-        bf16_t* op = p.out + (long)q * p.ldo + hcol + 4 * h;
-#pragma unroll
-        for (int d = 0; d < ND; ++d)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                u32x2 o = {pack16_2<false>(oacc[d][4 * g + 0] * inv, oacc[d][4 * g + 1] * inv),
-                           pack16_2<false>(oacc[d][4 * g + 2] * inv, oacc[d][4 * g + 3] * inv)};
-                *(u32x2*)(op + 32 * d + 8 * g) = o;
-            }
+        attn_store_direct<false, ND>(p.out + (long)q * p.ldo + hcol + 4 * h, oacc, inv);
     }
     UV_TL(vb, 3);
 #ifdef UV_ATTN_TIMELINE_DRAIN
@@ -667,12 +627,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
 // waves only gives, at the DiT's shape (2 x 24 heads x 358 units), 1 440 workgroups = 5.6 rounds of 256 CUs: the sixth round
 // runs on 62 % of the chip for the time of a full one. A workgroup's time is set by its busiest SIMD (three waves each at 12
 // units), so what shortens the tail is workgroups with TWO waves on every SIMD: the host cuts each head into n12 blocks of 12
-// units and n8 blocks of 8 units (attn12_cut: 26 + 6 there) and orders all 12-unit blocks before all 8-unit blocks, so every CU
+// units and n8 blocks of 8 units (plan_attn: 26 + 6 there) and orders all 12-unit blocks before all 8-unit blocks, so every CU
 // ends with short workgroups instead of some CUs ending with a long one. All 12 waves of a workgroup stage K / V^T tiles and
 // take every barrier; the waves beyond the block's unit count are LOADER-ONLY (no QK / softmax / PV). Per-query arithmetic does
 // not depend on the cut: results are bit-identical for any cut.
 // ------------------------------------------------------------------------------------------------------------------------
-template <int AHEAD = 3, bool XCD = true, int QN = 0>
+template <int QN = 0>
 __global__ __launch_bounds__(768) __attribute__((amdgpu_waves_per_eu(3, 3))) void flash_attn_fwd12_kernel(AttnArgs p) {
     constexpr int D = 128, NW = 12, KROW = 256, NKK = 8, ND = 4;
     constexpr int K_BYTES = UV_ATT_KV * KROW, V_BYTES = D * 128;
@@ -691,7 +651,7 @@ __global__ __launch_bounds__(768) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
     const int nbh = p.H * p.batch, n8 = p.q_blocks - p.n12;
     const int tot12 = p.n12 * nbh, tot8 = n8 * nbh;
     int id = blockIdx.x;                 // < tot12: a 12-unit block, else 8-unit block number id - tot12
-    if (XCD && (tot12 & 7) == 0 && (tot8 & 7) == 0) {
+    if ((tot12 & 7) == 0 && (tot8 & 7) == 0) {
         const int x = blockIdx.x & 7, j = blockIdx.x >> 3, c12 = tot12 >> 3, c8 = tot8 >> 3;
         id = j < c12 ? x * c12 + j : tot12 + x * c8 + (j - c12);
     }
@@ -707,14 +667,7 @@ __global__ __launch_bounds__(768) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
         units = 8;
     }
     const int head = bh % p.H;
-    {
-        const long b = bh / p.H;
-        p.q += b * p.Lq * p.ldq;
-        if (QN) p.q_rs += b * p.Lq;
-        p.k += b * p.Lk * p.ldk;
-        p.vt += (long)b * p.Lk;
-        p.out += b * p.Lq * p.ldo;
-    }
+    attn_sample_offset<QN>(p, bh / p.H);
     const int nwu = (p.Lq + UV_ATT_QW - 1) / UV_ATT_QW;
     const bool compute_wave = wave_u < min(units, nwu - u0);      // the head's last block may be ragged
     const int q0w = (u0 + wave_u) * UV_ATT_QW;
@@ -771,15 +724,7 @@ __global__ __launch_bounds__(768) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
     typedef const __attribute__((address_space(3))) bf16x8* lds_frag_p;
     unsigned kaddr[NKK];
     unsigned vaddr[2][2];
-    {
-        const int k_key = r & 15, v_key = (r >> 1) & 7;
-#pragma unroll
-        for (int kk = 0; kk < NKK; ++kk) kaddr[kk] = smem_a + r * KROW + (((2 * kk + h) ^ k_key) << 4);
-#pragma unroll
-        for (int T = 0; T < 2; ++T)
-#pragma unroll
-            for (int s2 = 0; s2 < 2; ++s2) vaddr[T][s2] = smem_a + V_OFF + r * 128 + (((4 * T + 2 * s2 + h) ^ v_key) << 4);
-    }
+    attn_frag_addrs(smem_a, V_OFF, r, h, kaddr, vaddr);
 
     f32x16 oacc[ND];
 #pragma unroll
@@ -787,9 +732,6 @@ __global__ __launch_bounds__(768) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
 #pragma unroll
         for (int e = 0; e < 16; ++e) oacc[d][e] = 0.f;
     float m_run = -INFINITY, l_run = 0.f;
-#if UV_ATTN_PROBE
-    bf16x8 kf_keep = qf[0], vf_keep = qf[1];      // timing-only probes (see the tile body): never in the product build
-#endif
 
     const int nt = (p.Lk + UV_ATT_KV - 1) / UV_ATT_KV;
     const int nt_full = p.Lk / UV_ATT_KV;
@@ -845,26 +787,16 @@ __global__ __launch_bounds__(768) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
             for (int e = 0; e < 16; ++e) sacc[e] = 0.f;
 #pragma unroll
             for (int kk = 0; kk < NKK; ++kk) {
-#if UV_ATTN_PROBE == 1      // timing-only probe (tools/diag/build_attn_probe.py; WRONG results): half of the fragment reads skipped, the skipped fragment = a copy of the previous one
-                bf16x8 kf;
-                if (kk & 1) kf = kf_keep; else kf = *(lds_frag_p)(kaddr[kk] + PAR * K_BYTES + T * 32 * KROW);
-                kf_keep = kf;
-#elif UV_ATTN_PROBE == 2    // timing-only probe: every read still issued and waited for, the odd fragments then REPLACED by a copy of the previous one (same operand data as probe 1)
-                bf16x8 kf = *(lds_frag_p)(kaddr[kk] + PAR * K_BYTES + T * 32 * KROW);
-                if (kk & 1) { asm volatile("" :: "v"(kf)); kf = kf_keep; }
-                kf_keep = kf;
-#else
                 const bf16x8 kf = *(lds_frag_p)(kaddr[kk] + PAR * K_BYTES + T * 32 * KROW);
-#endif
                 sacc = mfma_32x32x16<false>(kf, qf[kk], sacc);
             }
-            __builtin_amdgcn_sched_group_barrier(0x100, AHEAD, 0);
+            __builtin_amdgcn_sched_group_barrier(0x100, UV_ATT_AHEAD, 0);
 #pragma unroll
-            for (int i_ = 0; i_ < 8 - AHEAD; ++i_) {
+            for (int i_ = 0; i_ < 8 - UV_ATT_AHEAD; ++i_) {
                 __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
                 __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
             }
-            __builtin_amdgcn_sched_group_barrier(0x008, AHEAD, 0);
+            __builtin_amdgcn_sched_group_barrier(0x008, UV_ATT_AHEAD, 0);
             __builtin_amdgcn_sched_barrier(0);
             if (MASKED) {
 #pragma unroll
@@ -909,26 +841,16 @@ __global__ __launch_bounds__(768) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
             for (int d = 0; d < ND; ++d)
 #pragma unroll
                 for (int s2 = 0; s2 < 2; ++s2) {
-#if UV_ATTN_PROBE == 1
-                    bf16x8 vf;
-                    if (s2 & 1) vf = vf_keep; else vf = *(lds_frag_p)(vaddr[T][s2] + PAR * V_BYTES + d * 32 * 128);
-                    vf_keep = vf;
-#elif UV_ATTN_PROBE == 2
-                    bf16x8 vf = *(lds_frag_p)(vaddr[T][s2] + PAR * V_BYTES + d * 32 * 128);
-                    if (s2 & 1) { asm volatile("" :: "v"(vf)); vf = vf_keep; }
-                    vf_keep = vf;
-#else
                     const bf16x8 vf = *(lds_frag_p)(vaddr[T][s2] + PAR * V_BYTES + d * 32 * 128);
-#endif
                     oacc[d] = mfma_32x32x16<false>(vf, pf[s2], oacc[d]);
                 }
-            __builtin_amdgcn_sched_group_barrier(0x100, AHEAD, 1);
+            __builtin_amdgcn_sched_group_barrier(0x100, UV_ATT_AHEAD, 1);
 #pragma unroll
-            for (int i_ = 0; i_ < 8 - AHEAD; ++i_) {
+            for (int i_ = 0; i_ < 8 - UV_ATT_AHEAD; ++i_) {
                 __builtin_amdgcn_sched_group_barrier(0x008, 1, 1);
                 __builtin_amdgcn_sched_group_barrier(0x100, 1, 1);
             }
-            __builtin_amdgcn_sched_group_barrier(0x008, AHEAD, 1);
+            __builtin_amdgcn_sched_group_barrier(0x008, UV_ATT_AHEAD, 1);
             __builtin_amdgcn_sched_barrier(0);
         }
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
@@ -982,15 +904,7 @@ __global__ __launch_bounds__(768) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
             }
         }
     } else if (q < p.Lq) {
-        bf16_t* op = p.out + (long)q * p.ldo + hcol + 4 * h;
-#pragma unroll
-        for (int d = 0; d < ND; ++d)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                u32x2 o = {pack16_2<false>(oacc[d][4 * g + 0] * inv, oacc[d][4 * g + 1] * inv),
-                           pack16_2<false>(oacc[d][4 * g + 2] * inv, oacc[d][4 * g + 3] * inv)};
-                *(u32x2*)(op + 32 * d + 8 * g) = o;
-            }
+        attn_store_direct<false, ND>(p.out + (long)q * p.ldo + hcol + 4 * h, oacc, inv);
     }
     UV_TL(blockIdx.x, 3);
 #ifdef UV_ATTN_TIMELINE_DRAIN
@@ -999,71 +913,44 @@ __global__ __launch_bounds__(768) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
 #endif
 }
 
-// ---- kernel selection: the ONE place that decides which kernel serves a call ------------------------------------------------
-enum AttnKernel { ATT_FWD12 = 0, ATT_FWD3 = 1, ATT_FWD_D128 = 2, ATT_FWD_D64 = 3 };
-static const char* const kAttnKernelName[] = {"flash_attn_fwd12_kernel", "flash_attn_fwd3_kernel", "flash_attn_fwd_kernel<128>",
-                                              "flash_attn_fwd_kernel<64>"};
-
-static AttnKernel attn_select(int Lk, int head_dim, long ldk, long ldvt, bool f16) {
-    if (head_dim != 128) return ATT_FWD_D64;
-    // fwd12 / fwd3 address their LDS-DMA pieces with 32-bit lane offsets from a uniform base
-    if (f16 || 128 * ldvt >= (1L << 30) || 64 * ldk >= (1L << 30)) return ATT_FWD_D128;
-    // long key sequences: one 12-wave workgroup per CU shares each K / V^T tile among up to 384 queries (a third of the L2 -> LDS
-    // traffic; -2.8 % on the self-attention launches); short ones (cross-attention, Lk = 512: prologue and last round weigh
-    // more) keep the 4-wave workgroups (the 12-wave form is 24 % slower there)
-    if (Lk < 2048) return ATT_FWD3;
-    return ATT_FWD12;
+// ---- host side: validate, fill AttnArgs, plan (plan_attn, attn_args.h), launch -----------------------------------------------------------
+// The one launch site: every kernel instance is named here once, on the plan's grid and block.
+static void launch_attn(AttnArgs a, const AttnPlan& plan, bool qn, bool f16, hipStream_t st) {
+    a.q_blocks = plan.q_blocks;
+    a.n12 = plan.n12;
+    void (*kern)(AttnArgs) = nullptr;
+    switch (plan.kernel) {      // fwd12 / fwd3 are bf16 only (plan_attn), the q-norm prologue too (attn_entry)
+        case ATT_FWD12: kern = qn ? flash_attn_fwd12_kernel<1> : flash_attn_fwd12_kernel<0>; break;
+        case ATT_FWD3: kern = qn ? flash_attn_fwd3_kernel<1> : flash_attn_fwd3_kernel<0>; break;
+        case ATT_FWD_D128:
+            kern = f16 ? flash_attn_fwd_kernel<128, true, 0> : qn ? flash_attn_fwd_kernel<128, false, 1> : flash_attn_fwd_kernel<128, false, 0>;
+            break;
+        case ATT_FWD_D64:
+            kern = f16 ? flash_attn_fwd_kernel<64, true, 0> : qn ? flash_attn_fwd_kernel<64, false, 1> : flash_attn_fwd_kernel<64, false, 0>;
+            break;
+    }
+    hipLaunchKernelGGL(kern, dim3(plan.grid), dim3(plan.block), 0, st, a);
 }
 
-// Cut of a (sample, head)'s NWU = ceil(Lq / 32) query units into n12 blocks of 12 units followed by n8 blocks of 8 units for
-// flash_attn_fwd12_kernel. Model: a 12-unit workgroup takes time 1, an 8-unit one T8 = 0.76 (measured), every XCD's CUs pick
-// their workgroups up in id order (12-unit blocks first = longest-first list scheduling); the cut with the smallest simulated
-// makespan wins, ties go to fewer workgroups. Measured at the DiT shape (batch 2): 26 + 6 blocks 2.86 ms against 2.90 ms for
-// 30 + 0; mixes with more 8-unit blocks lose (24 + 9: 3.03 ms). At batch 1 the model picks 30 + 0 (768 workgroups = 3 rounds).
-static void attn12_cut(int Lq, int heads_total, int* n12_out, int* n8_out) {
-    const int nwu = (Lq + UV_ATT_QW - 1) / UV_ATT_QW, ncu = uv_num_cus();
-    // small per-thread memo (ctypes releases the GIL: two host threads, one per GPU, may be in here with different shapes at once;
-    // alternating shapes must not re-run the list-scheduling scan, ~ blocks x CUs x cuts host operations, on every call)
-    struct Memo { int nwu, key, n12, n8; };
-    static thread_local Memo memo[8];
-    static thread_local int memo_next = 0;
-    const int mkey = heads_total * 1024 + ncu;
-    for (const Memo& e : memo)
-        if (e.nwu == nwu && e.key == mkey) { *n12_out = e.n12; *n8_out = e.n8; return; }
-    const double T8 = 0.76;   // measured: all-8-unit cut 0.365 ms per round of workgroups, all-12-unit cut 0.48 ms (batch 2, L = 11 440)
-    int best12 = (nwu + 11) / 12, best8 = 0;
-    double best = 1e30;
-    for (int n8 = 0; n8 * 8 < nwu + 8; ++n8) {
-        const int rest = nwu - 8 * n8;
-        const int n12 = rest > 0 ? (rest + 11) / 12 : 0;
-        if (n12 == 0 && n8 * 8 - nwu >= 8) break;
-        // list scheduling on ncu identical machines: loads kept in a small array (ncu <= 1024)
-        double load[1024];
-        const int m = ncu < 1024 ? ncu : 1024;
-        for (int i = 0; i < m; ++i) load[i] = 0.0;
-        auto place = [&](long count, double t) {
-            for (long j = 0; j < count; ++j) {
-                int arg = 0;
-                for (int i = 1; i < m; ++i) if (load[i] < load[arg]) arg = i;
-                load[arg] += t;
-            }
-        };
-        place((long)n12 * heads_total, 1.0);
-        place((long)n8 * heads_total, T8);
-        double mk = 0.0;
-        for (int i = 0; i < m; ++i) mk = load[i] > mk ? load[i] : mk;
-        if (mk < best - 1e-9) { best = mk; best12 = n12; best8 = n8; }
-    }
-    memo[memo_next] = Memo{nwu, mkey, best12, best8};
-    memo_next = (memo_next + 1) & 7;
-    *n12_out = best12; *n8_out = best8;
+// The plan uv_flash_attn_bf16 / _f16 launch for this problem on the current device (256 CUs without one) under the current UV_OPT_ATTN_CUT:
+// kernel name, query blocks per (sample, head), how many of them own 12 units (flash_attn_fwd12_kernel; the others own 8), workgroups.
+extern "C" int uv_flash_attn_plan(int batch, int Lq, int Lk, int H, int head_dim, long ldk, long ldvt, int f16, char* kernel, int len,
+                                  int* q_blocks, int* n12, int* grid) {
+    UV_CHECK_ARG(kernel && len > 0 && q_blocks && n12 && grid, "uv_flash_attn_plan: null pointer");
+    UV_CHECK_ARG(head_dim == 128 || head_dim == 64, "uv_flash_attn_plan: head_dim %d unsupported (64 or 128)", head_dim);
+    UV_CHECK_ARG(Lq > 0 && Lk > 0 && H > 0 && batch > 0, "uv_flash_attn_plan: bad shape B=%d Lq=%d Lk=%d H=%d", batch, Lq, Lk, H);
+    const AttnPlan plan = plan_attn(batch, Lq, Lk, H, head_dim, ldk, ldvt, f16 != 0, uv_num_cus(), uv_option(UV_OPT_ATTN_CUT));
+    snprintf(kernel, len, "%s", kAttnKernelName[plan.kernel]);
+    *q_blocks = plan.q_blocks; *n12 = plan.n12; *grid = plan.grid;
+    return 0;
 }
 
 // Name of the kernel uv_flash_attn_bf16 / _f16 dispatches for this problem (bench.py labels its roofline line with it).
 extern "C" int uv_flash_attn_kernel_name(int Lk, int head_dim, long ldk, long ldvt, int f16, char* buf, int len) {
     UV_CHECK_ARG(buf && len > 0, "uv_flash_attn_kernel_name: bad buffer");
     UV_CHECK_ARG(head_dim == 128 || head_dim == 64, "uv_flash_attn_kernel_name: head_dim %d unsupported (64 or 128)", head_dim);
-    snprintf(buf, len, "%s", kAttnKernelName[attn_select(Lk, head_dim, ldk, ldvt, f16 != 0)]);
+    // the kernel does not depend on batch, Lq, H, the CU count or the cut (a forced cut: no list-scheduling scan for a name)
+    snprintf(buf, len, "%s", kAttnKernelName[plan_attn(1, 1, Lk, 1, head_dim, ldk, ldvt, f16 != 0, 1, 1).kernel]);
     return 0;
 }
 
@@ -1082,48 +969,12 @@ static int attn_entry(const char* name, const void* q, long ldq, const void* k, 
     AttnArgs a;
     a.q = (const bf16_t*)q; a.k = (const bf16_t*)k; a.vt = (const bf16_t*)vt; a.out = (bf16_t*)out;
     a.ldq = ldq; a.ldk = ldk; a.ldvt = ldvt; a.ldo = ldo;
-    a.Lq = Lq; a.Lk = Lk; a.H = H; a.batch = batch; a.n12 = 0;
+    a.Lq = Lq; a.Lk = Lk; a.H = H; a.batch = batch;
     a.scale_log2 = softmax_scale * 1.4426950408889634f;
     a.q_rs = q_rs; a.q_w = q_w;
     const bool qn = q_rs != nullptr;
     UV_CHECK_ARG(!qn || (q_w && !F16 && (((uintptr_t)q_w | (uintptr_t)q_rs) & 15) == 0), "%s: q_rs needs q_weight (f32, 16-byte aligned), bf16 only", name);
-    hipStream_t st = (hipStream_t)stream;
-    switch (attn_select(Lk, head_dim, ldk, ldvt, F16)) {
-        case ATT_FWD12:
-            {
-                int n12 = 0, n8 = 0;
-                attn12_cut(Lq, H * batch, &n12, &n8);
-                if (const int force = uv_option(UV_OPT_ATTN_CUT); force > 0) {       // A/B tools: n8 = force - 1 eight-unit blocks per head
-                    const int nwu = (Lq + UV_ATT_QW - 1) / UV_ATT_QW, rest = nwu - 8 * (force - 1);
-                    n8 = force - 1;
-                    n12 = rest > 0 ? (rest + 11) / 12 : 0;
-                }
-                a.n12 = n12;
-                a.q_blocks = n12 + n8;
-            }
-            if (qn) hipLaunchKernelGGL((flash_attn_fwd12_kernel<3, true, 1>), dim3(a.q_blocks * H * batch), dim3(768), 0, st, a);
-            else hipLaunchKernelGGL((flash_attn_fwd12_kernel<3, true>), dim3(a.q_blocks * H * batch), dim3(768), 0, st, a);
-            break;
-        case ATT_FWD3:
-            a.q_blocks = (Lq + 127) / 128;
-            if (qn) hipLaunchKernelGGL((flash_attn_fwd3_kernel<3, true, 1>), dim3(a.q_blocks * H * batch), dim3(256), 0, st, a);
-            else hipLaunchKernelGGL((flash_attn_fwd3_kernel<3, true>), dim3(a.q_blocks * H * batch), dim3(256), 0, st, a);
-            break;
-        case ATT_FWD_D128:
-            a.q_blocks = (Lq + 127) / 128;
-            if constexpr (!F16) {
-                if (qn) { hipLaunchKernelGGL((flash_attn_fwd_kernel<128, true, false, 1>), dim3(a.q_blocks * H * batch), dim3(256), 0, st, a); break; }
-            }
-            hipLaunchKernelGGL((flash_attn_fwd_kernel<128, true, F16>), dim3(a.q_blocks * H * batch), dim3(256), 0, st, a);
-            break;
-        case ATT_FWD_D64:
-            a.q_blocks = (Lq + 127) / 128;
-            if constexpr (!F16) {
-                if (qn) { hipLaunchKernelGGL((flash_attn_fwd_kernel<64, false, false, 1>), dim3(a.q_blocks * H * batch), dim3(256), 0, st, a); break; }
-            }
-            hipLaunchKernelGGL((flash_attn_fwd_kernel<64, false, F16>), dim3(a.q_blocks * H * batch), dim3(256), 0, st, a);
-            break;
-    }
+    launch_attn(a, plan_attn(batch, Lq, Lk, H, head_dim, ldk, ldvt, F16, uv_num_cus(), uv_option(UV_OPT_ATTN_CUT)), qn, F16, (hipStream_t)stream);
     UV_CHECK_LAUNCH(name);
     return 0;
 }

@@ -1,4 +1,6 @@
-// Argument block and shared constants of the flash-attention kernels (attention.hip; tools/diag/attn_pw4.hip).
+// The flash-attention kernels' shared host and device pieces (attention.hip; tools/diag/attn_pw4.hip): the argument block and constants,
+// plan_attn - the ONE place that decides which kernel serves a call, on what query-block cut and on what grid -, and the device code the
+// kernels have in common.
 #pragma once
 #include "common.h"
 
@@ -20,6 +22,102 @@ struct AttnArgs {
     const float* q_rs;
     const float* q_w;
 };
+
+enum AttnKernel { ATT_FWD12 = 0, ATT_FWD3 = 1, ATT_FWD_D128 = 2, ATT_FWD_D64 = 3 };
+static const char* const kAttnKernelName[] = {"flash_attn_fwd12_kernel", "flash_attn_fwd3_kernel", "flash_attn_fwd_kernel<128>",
+                                              "flash_attn_fwd_kernel<64>"};
+struct AttnPlan {
+    int kernel;            // AttnKernel
+    int q_blocks, n12;     // query blocks per (sample, head); of them the 12-unit ones (flash_attn_fwd12_kernel only, else 0)
+    int grid, block;       // workgroups = q_blocks * H * batch; threads per workgroup
+};
+
+// Which kernel serves this attention call, how each (sample, head) is cut into query blocks, and on what grid. ncus = the device's CU
+// count, force_cut = UV_OPT_ATTN_CUT (A/B tools and tests; 0 = automatic): the callers read both and pass them in. Pure: the same answer
+// for the same arguments, whatever ran before (the memo below only saves the scan).
+static inline AttnPlan plan_attn(int batch, int Lq, int Lk, int H, int head_dim, long ldk, long ldvt, bool f16, int ncus, int force_cut) {
+    const int nbh = H * batch;
+    auto blocks128 = [&](int kernel) {       // the 4-wave kernels: 128 queries per workgroup
+        const int qb = (Lq + 4 * UV_ATT_QW - 1) / (4 * UV_ATT_QW);
+        return AttnPlan{kernel, qb, 0, qb * nbh, 256};
+    };
+    if (head_dim != 128) return blocks128(ATT_FWD_D64);
+    // fwd12 / fwd3 address their LDS-DMA pieces with 32-bit lane offsets from a uniform base
+    if (f16 || 128 * ldvt >= (1L << 30) || 64 * ldk >= (1L << 30)) return blocks128(ATT_FWD_D128);
+    // long key sequences: one 12-wave workgroup per CU shares each K / V^T tile among up to 384 queries (a third of the L2 -> LDS
+    // traffic; -2.8 % on the self-attention launches); short ones (cross-attention, Lk = 512: prologue and last round weigh
+    // more) keep the 4-wave workgroups (the 12-wave form is 24 % slower there)
+    if (Lk < 2048) return blocks128(ATT_FWD3);
+
+    // flash_attn_fwd12_kernel: the cut of a (sample, head)'s NWU = ceil(Lq / 32) query units into n12 blocks of 12 units followed by n8
+    // blocks of 8 units. Model: a 12-unit workgroup takes time 1, an 8-unit one T8 = 0.76 (measured), every XCD's CUs pick their
+    // workgroups up in id order (12-unit blocks first = longest-first list scheduling); the cut with the smallest simulated makespan
+    // wins, ties go to fewer workgroups. Measured at the DiT shape (batch 2, 48 heads x 358 units): 26 + 6 blocks 2.86 ms against
+    // 2.90 ms for 30 + 0; mixes with more 8-unit blocks lose (24 + 9: 3.03 ms). At batch 1 the model picks 30 + 0 (720 workgroups on
+    // 256 CUs: three rounds, the last one 81 % full).
+    const int nwu = (Lq + UV_ATT_QW - 1) / UV_ATT_QW;
+    auto cut = [&](int n12, int n8) { return AttnPlan{ATT_FWD12, n12 + n8, n12, (n12 + n8) * nbh, 768}; };
+    auto n12_beside = [&](int n8) { return nwu > 8 * n8 ? (nwu - 8 * n8 + 11) / 12 : 0; };
+    if (force_cut > 0) return cut(n12_beside(force_cut - 1), force_cut - 1);      // n8 = force_cut - 1 eight-unit blocks per head
+    // small per-thread memo (ctypes releases the GIL: two host threads, one per GPU, may be in here with different shapes at once;
+    // alternating shapes must not re-run the list-scheduling scan, ~ blocks x CUs x cuts host operations, on every call)
+    struct Memo { int nwu, nbh, ncus, n12, n8; };
+    static thread_local Memo memo[8];
+    static thread_local int memo_next = 0;
+    for (const Memo& e : memo)
+        if (e.nwu == nwu && e.nbh == nbh && e.ncus == ncus) return cut(e.n12, e.n8);
+    const double T8 = 0.76;   // measured: all-8-unit cut 0.365 ms per round of workgroups, all-12-unit cut 0.48 ms (batch 2, L = 11 440)
+    int best12 = (nwu + 11) / 12, best8 = 0;
+    double best = 1e30;
+    for (int n8 = 0; n8 * 8 < nwu + 8; ++n8) {
+        const int n12 = n12_beside(n8);
+        if (n12 == 0 && n8 * 8 - nwu >= 8) break;
+        // list scheduling on ncus identical machines: loads kept in a small array (ncus <= 1024)
+        double load[1024];
+        const int m = ncus < 1024 ? ncus : 1024;
+        for (int i = 0; i < m; ++i) load[i] = 0.0;
+        auto place = [&](long count, double t) {
+            for (long j = 0; j < count; ++j) {
+                int arg = 0;
+                for (int i = 1; i < m; ++i) if (load[i] < load[arg]) arg = i;
+                load[arg] += t;
+            }
+        };
+        place((long)n12 * nbh, 1.0);
+        place((long)n8 * nbh, T8);
+        double mk = 0.0;
+        for (int i = 0; i < m; ++i) mk = load[i] > mk ? load[i] : mk;
+        if (mk < best - 1e-9) { best = mk; best12 = n12; best8 = n8; }
+    }
+    memo[memo_next] = Memo{nwu, nbh, ncus, best12, best8};
+    memo_next = (memo_next + 1) & 7;
+    return cut(best12, best8);
+}
+
+// ---- device code the kernels share
+// Independent samples are stacked along the token axis: rows of q / k / out, COLUMNS of V^T. Moves the argument block to sample b.
+template <int QN>
+__device__ __forceinline__ void attn_sample_offset(AttnArgs& p, long b) {
+    p.q += b * p.Lq * p.ldq;
+    if (QN) p.q_rs += b * p.Lq;
+    p.k += b * p.Lk * p.ldk;
+    p.vt += (long)b * p.Lk;
+    p.out += b * p.Lq * p.ldo;
+}
+
+// O row of one query straight from the MFMA layout: op = the row's first element of this lane (column hcol + 4 h), 4 ND pieces of 8 bytes.
+// Any ldo % 4 == 0.
+template <bool F16, int ND>
+__device__ __forceinline__ void attn_store_direct(bf16_t* op, const f32x16 (&oacc)[ND], float inv) {
+#pragma unroll
+    for (int d = 0; d < ND; ++d)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            u32x2 o = {pack16_2<F16>(oacc[d][4 * g + 0] * inv, oacc[d][4 * g + 1] * inv),
+                       pack16_2<F16>(oacc[d][4 * g + 2] * inv, oacc[d][4 * g + 3] * inv)};
+            *(u32x2*)(op + 32 * d + 8 * g) = o;
+        }
+}
 
 // Q fragments of one wave: lane (r, h) holds Q[qrow][hcol + 16 kk + 8 h .. + 7], kk = 0 .. NKK-1. QN = 1: q is the RAW projection and the row's
 // RMSNorm is applied by attn_apply_qnorm with the rounding points of rmsnorm_rope_kernel (dit_glue.hip): bf16( bf16(q * rs) * w ), products in
@@ -69,4 +167,17 @@ __device__ __forceinline__ void attn_apply_qnorm(bf16x8 (&qf)[NKK], const AttnQN
 
 __device__ __forceinline__ int perm23(int i) {  // swap bits 2 and 3
     return (i & ~12) | ((i & 4) << 1) | ((i & 8) >> 1);
+}
+
+// Fragment read addresses of flash_attn_fwd3_kernel / flash_attn_fwd12_kernel (LDS byte addresses; buffer, key-half and d-tile offsets are
+// instruction immediates). K: row r of 256 bytes, logical chunk 2 kk + h, physical chunk ^= r & 15. V^T (at v_off): row r of 128 bytes, logical
+// chunk 4 T + 2 s + h, physical chunk ^= (r >> 1) & 7.
+__device__ __forceinline__ void attn_frag_addrs(unsigned smem_a, unsigned v_off, int r, int h, unsigned (&kaddr)[8], unsigned (&vaddr)[2][2]) {
+    const int k_key = r & 15, v_key = (r >> 1) & 7;
+#pragma unroll
+    for (int kk = 0; kk < 8; ++kk) kaddr[kk] = smem_a + r * 256 + (((2 * kk + h) ^ k_key) << 4);
+#pragma unroll
+    for (int T = 0; T < 2; ++T)
+#pragma unroll
+        for (int s2 = 0; s2 < 2; ++s2) vaddr[T][s2] = smem_a + v_off + r * 128 + (((4 * T + 2 * s2 + h) ^ v_key) << 4);
 }
