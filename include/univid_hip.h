@@ -93,6 +93,19 @@ int uv_gemm_bf16_nt_ssq(const void* A, long lda, const void* W, long ldw, const 
  * WanRMSNorm's x.pow(2).mean(-1) + eps, rsqrt (model.py:85). */
 int uv_rms_scale_from_ssq(const float* ssq, long ld_ssq, int M, int groups, int C, float eps, float* rs, void* stream);
 
+/* Down-projection of an UN-MERGED LoRA adapter (peft==0.17.1 peft/tuners/lora/layer.py `Linear.forward`:
+ * `result = result + lora_B(lora_A(dropout(x))) * scaling`, as the reference runs it after LoRAManager.load_lora_weights ->
+ * PeftModel.from_pretrained, models/model_pipeline.py:724-750): out[m][j] = bf16(scale[j] * sum_k x[m][k] A[j][k]) for j < R and
+ * exactly 0 for R <= j < Rpad. x bf16 [M, ldx], A bf16 [R, lda] (the lora_A weights of every adapter / projection reading x, stacked
+ * row-wise), scale f32 [R] (lora_alpha / r, rslora, per-module patterns, run-time strength: applied before the ONE rounding to bf16,
+ * which is lora_A(x)'s), fp32 accumulate. K % 64 == 0, 1 <= R <= Rpad, Rpad % 128 == 0, leading dimensions multiples of 8, pointers
+ * 16-byte aligned. out may be x + K (same rows, disjoint columns): the projection then runs as uv_gemm_bf16_nt over
+ * [x | out] . [W | B | 0]^T with K + Rpad columns, so the adapter lands in the fp32 accumulator in front of the fused epilogue.
+ * Nothing outside [0, M) x [0, Rpad) of out is written, nothing beyond column K or row M of x is read. Every output element is one
+ * fixed-order chain over k (no split-K, no atomics): a row's bits do not depend on the other rows of the launch. */
+int uv_lora_down_bf16(const void* x, long ldx, const void* A, long lda, const float* scale, int M, int K, int R, void* out, long ldo,
+                      int Rpad, void* stream);
+
 /* C[M,N] = A[M,K] . W[N,K]^T + bias (+ resid), all fp32, exact-f32 MFMA (16x16x4).
  * Replaces Head.head (fp32 island, model.py:286-290) and the VAE's 1x1 convolutions (vae2_2.py:211,249-250,766-767).
  * K % 4 == 0, N % 4 == 0. */
@@ -183,6 +196,8 @@ int uv_linear_rows_f32(const float* x, long ldx, const float* W, const float* b,
 /* out[r][i] = mod[i] + e0[r][i]  (modulation + e, model.py:239, 287) */
 int uv_add_rows_f32(const float* mod, const float* e0, float* out, int R, long n, void* stream);
 int uv_cast_f32_bf16(const float* in, void* out, long n, void* stream);
+/* the same for [R, C] rows with leading dimensions (an output buffer that carries a LoRA slot behind its C columns); C % 4 == 0 */
+int uv_cast_f32_bf16_rows(const float* in, long ldi, void* out, long ldo, int R, int C, void* stream);
 /* x_f32 += float(y_bf16): un-fused residual used when WanCrossAttention.forward has been re-assigned (UniVid's hook). */
 int uv_add_bf16_resid(float* x, long ldx, const void* y, long ldy, int L, int C, void* stream);
 /* UniVid's dynamic text weight on the embedded context of ONE sample (Wan22ContextWrapper's per-layer hook,

@@ -33,6 +33,8 @@ SIGNATURES = {
     "uv_gemm_f32_nt": [_P, _L, _P, _L, _P, _I, _I, _I, _P, _L, _P, _L, _P],
     "uv_gemm_bf16_nt_ssq": [_P, _L, _P, _L, _P, _I, _I, _I, _P, _L, _P, _L, _I, _P],
     "uv_rms_scale_from_ssq": [_P, _L, _I, _I, _I, _F, _P, _P],
+    "uv_lora_down_bf16": [_P, _L, _P, _L, _P, _I, _I, _I, _P, _L, _I, _P],
+    "uv_cast_f32_bf16_rows": [_P, _L, _P, _L, _I, _I, _P],
     "uv_flash_attn_bf16_qnorm": [_P, _L, _P, _L, _P, _L, _P, _L, _I, _I, _I, _I, _I, _F, _P, _P, _P],
     "uv_flash_attn_bf16": [_P, _L, _P, _L, _P, _L, _P, _L, _I, _I, _I, _I, _I, _F, _P],
     "uv_flash_attn_f16": [_P, _L, _P, _L, _P, _L, _P, _L, _I, _I, _I, _I, _I, _F, _P],
@@ -306,6 +308,36 @@ def rms_scale_from_ssq(ssq, rs, M, C, eps):
     _chk(rs, torch.float32, "rms_scale_from_ssq.rs")
     call("uv_rms_scale_from_ssq", ptr(ssq), ssq.stride(0), M, ssq.shape[1], C, float(eps), ptr(rs), stream_ptr())
     return rs
+
+
+def lora_down(buf, K, A, scale, M=None, Rpad=None):
+    """The un-merged LoRA slot of an activation buffer, in place: buf bf16 [rows, >= K + Rpad] holds x in its first K columns;
+    columns [K, K + Rpad) of its first M rows become bf16(scale * (x A^T)), zero beyond A's R rows (include/univid_hip.h).
+    A bf16 [R, K] (stacked lora_A weights), scale f32 [R]. Rpad defaults to R rounded up to whole 128-column groups."""
+    _chk(buf, torch.bfloat16, "lora_down.buf")
+    _chk(A, torch.bfloat16, "lora_down.A")
+    _chk(scale, torch.float32, "lora_down.scale")
+    R = A.shape[0]
+    M = buf.shape[0] if M is None else M
+    Rpad = (R + 127) // 128 * 128 if Rpad is None else Rpad
+    if buf.dim() != 2 or A.dim() != 2 or A.shape[1] != K or scale.numel() != R or buf.shape[1] < K + Rpad or M > buf.shape[0]:
+        raise UnividHipError(f"lora_down: buffer {tuple(buf.shape)} / A {tuple(A.shape)} / scale {tuple(scale.shape)} do not fit K = {K}, "
+                             f"slot = {Rpad}, M = {M}")
+    out = buf[:, K:]
+    call("uv_lora_down_bf16", ptr(buf), buf.stride(0), ptr(A), A.stride(0), ptr(scale), M, K, R, ptr(out), buf.stride(0), Rpad, stream_ptr(),
+         flops=2 * M * R * K)
+    return buf
+
+
+def cast_f32_bf16(x, out, R, C):
+    """out[:R, :C] = bf16(x[:R, :C]); the contiguous entry point when neither side has a wider leading dimension."""
+    _chk(x, torch.float32, "cast_f32_bf16.x")
+    _chk(out, torch.bfloat16, "cast_f32_bf16.out")
+    if x.stride(0) == C and out.stride(0) == C:
+        call("uv_cast_f32_bf16", ptr(x), ptr(out), R * C, stream_ptr())
+    else:
+        call("uv_cast_f32_bf16_rows", ptr(x), x.stride(0), ptr(out), out.stride(0), R, C, stream_ptr())
+    return out
 
 
 def gemm_f32(a, w, bias, out, resid=None, M=None):

@@ -9,7 +9,8 @@ Mirrors the parts of /root/reference/models/model_pipeline.py that sit directly 
 so that inference.py can drive this package unchanged. Everything off the hot path is pluggable instead of
 re-built (SURVEY.md section 2 marks it out of scope): the BAGEL-7B semantic extractor, the ContextProjector adapter,
 the umT5 text encoder, training and video file I/O are callables/objects the caller supplies. LoRA adapters are loaded
-for inference by `univid_amd.lora.LoRAManager` (merged into the dense weights).
+for inference by `univid_amd.lora.LoRAManager` (merged into the dense weights by default; `config.lora_merge = False` /
+`load_lora_weights(..., merge=False)` keeps them un-merged and swappable per request, as the reference runs them).
 
 Behaviour kept on purpose: the text-encoder override of the reference is dead code (Python resolves
 `obj(...)` through the type), so the DiT receives the text encoder's embeddings; the per-layer forward hook IS live
@@ -51,6 +52,7 @@ class CrossAttentionConfig:
     lora_alpha: int = 16
     lora_dropout: float = 0.1
     lora_target_strategy: str = "your_method_here"
+    lora_merge: bool = True       # CrossAttentionFusionPipeline.load_lora: fold the adapter into the dense weights (False: attach it un-merged)
     guidance_strength: float = 1.0
     bagel_cross_attn_layers: List[int] = None
     freeze_bagel: bool = True
@@ -379,6 +381,14 @@ class CrossAttentionFusionPipeline:
         # native_text_weight=False: the reference's closures on the model's generic path (kept as the comparison the tests and bench use)
         self.wan_wrapper = Wan22ContextWrapper(wan_pipeline, self.context_projector, self.logger, config, native=native_text_weight)
         self.save_fn = save_fn
+
+    def load_lora(self, load_path, name="default", weight=1.0, merge=None):
+        """inference.py:218-224 as one call: `lora_manager.load_lora_weights(load_path, dit_model)` with the config's `lora_merge`
+        (merge=None) - merged into the dense weights, or attached un-merged under `name` at strength `weight`."""
+        if self.lora_manager is None:
+            raise RuntimeError("config.use_lora is off: this pipeline has no lora_manager")
+        merge = bool(getattr(self.config, "lora_merge", True)) if merge is None else bool(merge)
+        return self.lora_manager.load_lora_weights(load_path, self.dit_model, merge=merge, name=name, weight=weight)
 
     def _check_gpu(self, field_name):
         idx, n = getattr(self.config, field_name), torch.cuda.device_count()

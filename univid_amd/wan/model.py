@@ -58,12 +58,86 @@ class _Prepared:
                 "a LoRA-wrapped nn.Linear (PEFT lora.Linear) was found in the DiT: the HIP path reads dense weights and would "
                 "ignore the adapter. Load the adapter directory with `univid_amd.lora.LoRAManager().load_lora_weights(dir, model)` "
                 "(folds it into the dense weights), or fold it in with `peft_model.merge_and_unload()` and call "
-                "`WanModel.invalidate()` before the next forward.")
+                "`WanModel.invalidate()` before the next forward - or, to keep the adapter un-merged and swappable, attach the adapter "
+                "directory to the un-wrapped model with `LoRAManager().load_lora_weights(dir, model, merge=False)`.")
         w = lin.weight.detach()
         if pad_k and w.shape[1] % pad_k:
             w = torch.nn.functional.pad(w, (0, pad_k - w.shape[1] % pad_k))
         self.w = w.to(BF16).contiguous()
         self.b = None if lin.bias is None else lin.bias.detach().to(BF16).contiguous()
+
+
+# ---- un-merged LoRA (univid_amd/lora.py attaches; peft lora/layer.py Linear.forward) ---------------------------------------------
+# An attached adapter lives on its nn.Linear as `lin._uv_lora = {adapter name: {"A": [r, in], "B": [out, r], "scaling": s, "weight": w}}`
+# and never touches the fp32 master weight. The projections that read ONE activation share one slot of whole 128-column groups behind
+# that activation's K columns: uv_lora_down_bf16 writes T = bf16(scale o (x A^T)) there (every adapter's lora_A stacked row-wise), and
+# each adapted projection's bf16 operand becomes [W | B | 0] with its lora_B in its own column range of the slot, so the tuned GEMM
+# kernels run unchanged with K + S columns and the adapter's contribution lands in the fp32 accumulator in front of the fused epilogue.
+LORA_MAX_SLOT = 512     # columns of one activation's slot = the stacked rank of all adapters on all projections reading it, rounded up to 128
+
+
+class _LoraSlot:
+    """Stacked lora_A [R, K] bf16, the per-row scale f32 [R] (scaling x run-time weight) and the slot width S of one activation."""
+    __slots__ = ("A", "scale", "S", "rows")
+
+    def __init__(self, entries, dev):
+        self.rows = [(ad, ad["A"].shape[0]) for ad in entries]
+        R = sum(r for _, r in self.rows)
+        self.S = _round_up(R, 128)
+        if self.S > LORA_MAX_SLOT:
+            raise ValueError(f"the adapters on the projections of one input stack to rank {R}: more than the {LORA_MAX_SLOT} slot columns "
+                             f"(LORA_MAX_SLOT) an activation buffer carries")
+        self.A = torch.cat([ad["A"].to(device=dev, dtype=BF16) for ad in entries]).contiguous()
+        self.scale = torch.empty(R, dtype=torch.float32, device=dev)
+        self.refresh_scale()
+
+    def refresh_scale(self):
+        """Re-reads scaling x weight of every adapter into the device vector, in place (graph-captured launches read the same memory)."""
+        host = torch.cat([torch.full((r,), float(ad["scaling"]) * float(ad["weight"]), dtype=torch.float32) for ad, r in self.rows])
+        self.scale.copy_(host)
+
+
+def _prepare_group(lins):
+    """({name: _Prepared}, _LoraSlot | None) of the nn.Linears that read the same activation. Without attached adapters: exactly the
+    dense operands. With: the adapted projections get [W | B | 0] (the others keep W and ignore the slot)."""
+    preps = {n: _Prepared(l) for n, l in lins.items()}
+    entries = [(n, ad) for n, l in lins.items() for ad in getattr(l, "_uv_lora", {}).values()]
+    if not entries:
+        return preps, None
+    first = next(iter(preps.values())).w
+    K, dev = first.shape[1], first.device
+    slot = _LoraSlot([ad for _, ad in entries], dev)
+    col = K
+    for n, ad in entries:
+        p, r = preps[n], ad["A"].shape[0]
+        if p.w.shape[1] == K:
+            w = torch.zeros(p.w.shape[0], K + slot.S, dtype=BF16, device=dev)
+            w[:, :K] = p.w
+            p.w = w
+        p.w[:, col:col + r] = ad["B"].to(device=dev, dtype=BF16)
+        col += r
+    return preps, slot
+
+
+def _act_buf(rows, K, slots, dev):
+    """bf16 activation [rows, K + S]: S = the widest slot of the projections that will read it (0 without adapters: the plain buffer)."""
+    S = max((s.S for s in slots if s is not None), default=0)
+    return torch.empty(rows, K + S, dtype=BF16, device=dev)
+
+
+def _slotted(t, K, slot, M=None):
+    """The activation `t` (x in its first K columns) as the [W | B] GEMMs of `slot` read it: the slot's down-projection of the first M
+    rows written behind the K columns, in place when `t` was allocated with room for it (_act_buf), into a widened copy otherwise."""
+    if slot is None:
+        return t
+    M = t.shape[0] if M is None else M
+    if t.shape[1] < K + slot.S:
+        e = torch.empty(t.shape[0], K + slot.S, dtype=BF16, device=t.device)
+        e[:M, :K].copy_(t[:M, :K])
+        t = e
+    if M:
+        _lib.lora_down(t, K, slot.A, slot.scale, M=M, Rpad=slot.S)
+    return t
 
 
 class WanRMSNorm(nn.Module):
@@ -93,10 +167,16 @@ class WanSelfAttention(nn.Module):
         self.norm_q = WanRMSNorm(dim, eps=eps)
         self.norm_k = WanRMSNorm(dim, eps=eps)
         self._prep = None
+        self._slots = {}
         self._kv_cache = {}
 
+    _groups = {"qkv": ("q", "k", "v"), "o": ("o",)}      # projections by the activation they read (one LoRA slot each)
+
     def prepare(self):
-        self._prep = {n: _Prepared(getattr(self, n)) for n in ("q", "k", "v", "o")}
+        self._prep, self._slots = {}, {}
+        for g, names in self._groups.items():
+            preps, self._slots[g] = _prepare_group({n: getattr(self, n) for n in names})
+            self._prep.update(preps)
         self._kv_cache = {}
 
     def _self_attn(self, h, L, grid, freqs, x_resid, gate, gate_tid, batch=1, sp=None):
@@ -108,6 +188,7 @@ class WanSelfAttention(nn.Module):
         p = self._prep
         dev = h.device
         M = batch * L
+        h = _slotted(h, C, self._slots["qkv"], M)
         ql = torch.empty(M, C, dtype=BF16, device=dev)
         kl = torch.empty(M, C, dtype=BF16, device=dev)
         vt = _vt_scratch("vt", C, batch, L, dev)
@@ -116,8 +197,9 @@ class WanSelfAttention(nn.Module):
         _lib.gemm_bf16(h, p["v"].w, p["v"].b, vt, EPI_BF16_T, M=M)   # V^T [C, tokens]: sample b = columns b*L..
         # q and k of every stacked sample in one launch (RoPE positions restart with every sample)
         _lib.rmsnorm_rope_qk(ql, kl, self.norm_q.weight, self.norm_k.weight, M, L, C, D, self.eps, freqs, grid)
-        att = torch.empty(M, C, dtype=BF16, device=dev)
+        att = _act_buf(M, C, (self._slots["o"],), dev)
         _lib.flash_attn(ql, kl, vt, att, L, L, H, D, 1.0 / math.sqrt(D), batch=batch)
+        att = _slotted(att, C, self._slots["o"], M)
         _lib.gemm_bf16(att, p["o"].w, p["o"].b, x_resid, EPI_GATE_RESID_F32, M=M, gate=gate, gate_tid=gate_tid)
 
     def _self_attn_sp(self, h, n, grid, freqs, x_resid, gate, gate_tid, batch, sp):
@@ -140,6 +222,7 @@ class WanSelfAttention(nn.Module):
         kf = torch.empty(batch * Lt, Cp, dtype=BF16, device=dev)
         vtf = _vt_scratch("vt_sp", Cp, batch, Lt, dev)
         if M:
+            h = _slotted(h, C, self._slots["qkv"], M)
             _lib.gemm_bf16(h, p["q"].w, p["q"].b, ql, EPI_BF16, M=M)
             _lib.gemm_bf16(h, p["k"].w, p["k"].b, kl, EPI_BF16, M=M)
             _lib.gemm_bf16(h, p["v"].w, p["v"].b, vt, EPI_BF16_T, M=M)
@@ -157,6 +240,7 @@ class WanSelfAttention(nn.Module):
         for b in range(batch):
             par.tokens_to_heads(attf[b * Lt:(b + 1) * Lt], Lt, att[b * n:(b + 1) * n])
         if M:
+            att = _slotted(att, C, self._slots["o"], M)
             _lib.gemm_bf16(att, p["o"].w, p["o"].b, x_resid, EPI_GATE_RESID_F32, M=M, gate=gate, gate_tid=gate_tid)
 
     def forward(self, x, seq_lens, grid_sizes, freqs):
@@ -168,9 +252,9 @@ class WanSelfAttention(nn.Module):
         for b in range(x.size(0)):
             L = x.size(1)
             Lk = int(seq_lens[b])
-            h = x[b].to(BF16).contiguous()
             C, H, D = self.dim, self.num_heads, self.head_dim
             p = self._prep
+            h = _slotted(x[b].to(BF16).contiguous(), C, self._slots["qkv"])
             ql = torch.empty(L, C, dtype=BF16, device=x.device)
             kl = torch.empty(L, C, dtype=BF16, device=x.device)
             vt = torch.zeros(C, _round_up(L, 64), dtype=BF16, device=x.device)
@@ -180,8 +264,9 @@ class WanSelfAttention(nn.Module):
             grid = tuple(int(v) for v in grid_sizes[b])
             _lib.rmsnorm_rope(ql, ql, self.norm_q.weight, L, C, D, self.eps, fr, grid)
             _lib.rmsnorm_rope(kl, kl, self.norm_k.weight, L, C, D, self.eps, fr, grid)
-            att = torch.empty(L, C, dtype=BF16, device=x.device)
+            att = _act_buf(L, C, (self._slots["o"],), x.device)
             _lib.flash_attn(ql, kl, vt, att, L, Lk, H, D, 1.0 / math.sqrt(D))
+            att = _slotted(att, C, self._slots["o"])
             y = torch.empty(L, C, dtype=BF16, device=x.device)
             _lib.gemm_bf16(att, p["o"].w, p["o"].b, y, EPI_BF16)
             outs.append(y)
@@ -192,6 +277,7 @@ class WanCrossAttention(WanSelfAttention):
     """Text cross-attention (model.py:158-180). The class name and the (x, context, context_lens) signature are
     part of UniVid's contract: Wan22ContextWrapper finds modules by `__class__.__name__ == 'WanCrossAttention'`
     and replaces `module.forward` with a closure that rescales `context` (model_pipeline.py:1745-1807)."""
+    _groups = {"q": ("q",), "kv": ("k", "v"), "o": ("o",)}
     fuse_q_norm = True      # norm_q inside the attention kernel's Q prologue instead of a pass over q (A/B switch; same arithmetic but for
                             # the summation order of the row's mean square)
 
@@ -207,6 +293,7 @@ class WanCrossAttention(WanSelfAttention):
         C, D = self.dim, self.head_dim
         p = self._prep
         dev = ctx.device
+        ctx = _slotted(ctx, C, self._slots["kv"], batch * Lc)
         if out is not None:
             kl, vt = out
             _lib.gemm_bf16(ctx, p["k"].w, p["k"].b, kl, EPI_BF16, M=batch * Lc)
@@ -235,9 +322,10 @@ class WanCrossAttention(WanSelfAttention):
         p = self._prep
         dev = hq.device
         M = batch * L
+        hq = _slotted(hq, C, self._slots["q"], M)
         ql = torch.empty(M, C, dtype=BF16, device=dev)
         kl, vt = self._context_kv(ctx, Lc, batch, kv_key)
-        att = torch.empty(M, C, dtype=BF16, device=dev)
+        att = _act_buf(M, C, (self._slots["o"],), dev)
         if self.fuse_q_norm and C % 32 == 0:
             # norm_q without a pass of its own over q (round 5): the q GEMM's epilogue leaves each output row's sums of squares per 32-column
             # group, a tiny kernel turns them into the row scale 1 / sqrt(mean + eps), and the attention kernel's Q prologue applies scale and
@@ -254,7 +342,7 @@ class WanCrossAttention(WanSelfAttention):
         return att
 
     def _cross_fused(self, hq, ctx, L, Lc, x_resid, batch=1, kv_key=None):
-        att = self._attend(hq, ctx, L, Lc, batch, kv_key)
+        att = _slotted(self._attend(hq, ctx, L, Lc, batch, kv_key), self.dim, self._slots["o"], batch * L)
         p = self._prep["o"]
         _lib.gemm_bf16(att, p.w, p.b, x_resid, EPI_RESID_F32, M=batch * L)
 
@@ -266,7 +354,7 @@ class WanCrossAttention(WanSelfAttention):
         outs = []
         for b in range(x.size(0)):
             L, Lc = x.size(1), context.size(1)
-            att = self._attend(x[b].to(BF16).contiguous(), context[b].to(BF16).contiguous(), L, Lc)
+            att = _slotted(self._attend(x[b].to(BF16).contiguous(), context[b].to(BF16).contiguous(), L, Lc), self.dim, self._slots["o"])
             y = torch.empty(L, self.dim, dtype=BF16, device=x.device)
             p = self._prep["o"]
             _lib.gemm_bf16(att, p.w, p.b, y, EPI_BF16)
@@ -287,11 +375,17 @@ class WanAttentionBlock(nn.Module):
         self.ffn = nn.Sequential(nn.Linear(dim, ffn_dim), nn.GELU(approximate="tanh"), nn.Linear(ffn_dim, dim))
         self.modulation = nn.Parameter(torch.randn(1, 6, dim) / dim ** 0.5)
         self._prep = None
+        self._slots = {}
 
     def prepare(self):
         self.self_attn.prepare()
         self.cross_attn.prepare()
-        self._prep = {"ffn0": _Prepared(self.ffn[0]), "ffn2": _Prepared(self.ffn[2])}
+        self._prepare_ffn()
+
+    def _prepare_ffn(self):
+        p0, s0 = _prepare_group({"ffn0": self.ffn[0]})
+        p2, s2 = _prepare_group({"ffn2": self.ffn[2]})
+        self._prep, self._slots = {**p0, **p2}, {"ffn0": s0, "ffn2": s2}
 
     def _run(self, x, L, e0_rows, tid, grid, freqs, ctx, first_block, batch=1, sp=None, kv_key=None, twin_rows=False):
         """x: fp32 [batch*L, C] residual stream (independent samples stacked along the token axis), updated IN PLACE.
@@ -301,6 +395,11 @@ class WanAttentionBlock(nn.Module):
         first cross-attention): the self-attention half runs on sample 0 only and its result is copied to the others."""
         C = self.dim
         dev = x.device
+        # (an adapter attached or detached since the last forward left exactly its own module un-prepared: univid_amd/lora.py)
+        _ensure_prepared(self.self_attn)
+        _ensure_prepared(self.cross_attn)
+        if self._prep is None:
+            self._prepare_ffn()
         n_t = e0_rows.shape[0]
         Ls, L = L, batch * L          # Ls = tokens per sample; L = rows of every row-wise kernel below
         tab = torch.empty(n_t, 6 * C, dtype=torch.float32, device=dev)
@@ -309,7 +408,7 @@ class WanAttentionBlock(nn.Module):
         # (rows of the block's bf16 activations: L, or L rounded up to whole 256-row tiles for ffn.0 - see below; the pad rows are never
         # written and their products never read, so they need no zeroing and no scratch that outlives the forward)
         Lf = _ffn0_rows(L, self.ffn_dim, dev)
-        h_full = torch.empty(Lf, C, dtype=BF16, device=dev)
+        h_full = _act_buf(Lf, C, (self.self_attn._slots["qkv"], self.cross_attn._slots["q"], self._slots["ffn0"]), dev)
         h = h_full[:L]
         # NOTE for consumers of `mid` (ffn.0's output, below): its rows >= L are the GELU of whatever the allocator left in h_full[L:]
         # - UNDEFINED, possibly NaN / Inf. Rows are independent in every kernel of the block and ffn.2 reads L rows only.
@@ -328,11 +427,11 @@ class WanAttentionBlock(nn.Module):
         if self.cross_attn_norm:
             _lib.layernorm_mod(x, h, L, C, self.eps, mode=2, w=self.norm3.weight, b=self.norm3.bias)
         else:
-            _lib.call("uv_cast_f32_bf16", _lib.ptr(x), _lib.ptr(h), L * C, _lib.stream_ptr())
+            _lib.cast_f32_bf16(x, h, L, C)
         Lc = ctx.shape[0] // batch
         if "forward" in self.cross_attn.__dict__:
             # forward was re-assigned on the instance (UniVid hook): honour it, then add the residual un-fused
-            y = self.cross_attn.forward(h.view(batch, Ls, C), ctx.view(batch, Lc, C), None)
+            y = self.cross_attn.forward(h[:, :C].view(batch, Ls, C), ctx.view(batch, Lc, C), None)
             y = y.reshape(L, C).contiguous()
             _lib.call("uv_add_bf16_resid", _lib.ptr(x), x.stride(0), _lib.ptr(y), y.stride(0), L, C, _lib.stream_ptr())
         else:
@@ -343,11 +442,13 @@ class WanAttentionBlock(nn.Module):
         # input hold whatever the buffer held (rows are independent: nothing of them reaches a row that is read), their outputs are never
         # read (ffn.2 runs on L rows); results unchanged (a row's arithmetic is the same in both kernels)
         _lib.layernorm_mod(x, h, L, C, self.eps, mode=1, tab=tab, shift_off=3 * C, scale_off=4 * C, tid=tid)
-        mid = torch.empty(Lf, self.ffn_dim, dtype=BF16, device=dev)
+        h_full = _slotted(h_full, C, self._slots["ffn0"], L)
+        mid = _act_buf(Lf, self.ffn_dim, (self._slots["ffn2"],), dev)
         _lib.gemm_bf16(h_full, self._prep["ffn0"].w, self._prep["ffn0"].b, mid, EPI_GELU_BF16, M=Lf)
         # ffn.2's leftover rows (1 120 of 22 880) as one round of 256 x 256 tiles x split-K 4 where the library has that strip for the
         # shape (K >= 8192): it needs scratch for the partial tiles (63 MB at this shape; the allocator hands every block the same one)
-        nws = _splitk_ws_bytes(L, C, self.ffn_dim, dev)
+        mid = _slotted(mid, self.ffn_dim, self._slots["ffn2"], L)
+        nws = _splitk_ws_bytes(L, C, self._prep["ffn2"].w.shape[1], dev)
         ws = torch.empty(nws, dtype=torch.uint8, device=dev) if nws else None
         _lib.gemm_bf16(mid, self._prep["ffn2"].w, self._prep["ffn2"].b, x, EPI_GATE_RESID_F32, M=L,
                        gate=tab[:, 5 * C:], gate_tid=tid, ws=ws)
