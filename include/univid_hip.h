@@ -106,6 +106,35 @@ int uv_rms_scale_from_ssq(const float* ssq, long ld_ssq, int M, int groups, int 
 int uv_lora_down_bf16(const void* x, long ldx, const void* A, long lda, const float* scale, int M, int K, int R, void* out, long ldo,
                       int Rpad, void* stream);
 
+/* ---- DiT: MXFP8 GEMMs (opt-in fast mode of ffn.0 / ffn.2; WanModel.set_ffn_precision("mxfp8")) ---------------------------------
+ * Format (OCP Microscaling, MXFP8): elements are e4m3fn (the OCP encoding: bias 7, largest finite 448, no infinity, NaN = 0x7F / 0xFF;
+ * not the fnuz encoding), in blocks of 32 CONSECUTIVE K ELEMENTS OF ONE ROW, with one e8m0 scale byte (2^(e - 127)) per block:
+ *   amax    = largest magnitude of the block
+ *   e       = clamp(biased_fp32_exponent(amax) - 8, 0, 254), i.e. the scale 2^(floor(log2 amax) - 8); an all-zero block: e = 0, codes 0
+ *   element = round-to-nearest-even of x / 2^(e - 127) to e4m3 AFTER clamping to +-448 (the scaled amax lies in [256, 512), above
+ *             e4m3's 448: the clamp is explicit, the conversion's own overflow behaviour is never relied on; no code is ever a NaN)
+ * Layouts: codes uint8 [rows, ld] (ld in bytes, ld % 16 == 0); scales uint8 [rows, ld_s] row-major, ld_s >= K / 32, ld_s % 4 == 0;
+ * K % 128 == 0 (one 16x16x128 instruction step). Code pointers 16-byte, scale pointers 4-byte aligned. */
+
+/* bf16 x [M, ldx] -> codes [M, ldc] + scales [M, ld_s] as above, one pass (16-byte loads and stores). Quantises the activations in front
+ * of uv_gemm_mxfp8_nt and, once at prepare time, the weights (from the bf16 operand copy uv_gemm_bf16_nt would read: the two modes differ
+ * by the quantisation only). Replaces nothing in the reference (models/wan/utils/modules/model.py:212-214 run in bf16 there): it is
+ * what the fast mode adds. With finite inputs the bytes of a row are a pure function of that row - not of M, the row offset or the
+ * other rows; non-finite inputs are outside the contract and stay confined to their own row. Columns >= K of codes and >= K / 32 of
+ * scales are not written. */
+int uv_mx_quant_bf16(const void* x, long ldx, void* codes, long ldc, void* scales, long ld_s, int M, int K, void* stream);
+
+/* C[M,N] = deq(A)[M,K] . deq(W)[N,K]^T + bias on v_mfma_scale_f32_16x16x128_f8f6f4, fp32 accumulate: uv_gemm_bf16_nt for MXFP8 operands
+ * (replaces the same lines for ffn.0 / ffn.2, model.py:212-214, 252-255, in the fast mode). A codes [M, lda] with A_scale [M, ld_as],
+ * W codes [N, ldw] with W_scale [N, ld_ws]; bias bf16 [N] (8-byte aligned) or NULL. Epilogues UV_EPI_BF16, UV_EPI_GELU_BF16,
+ * UV_EPI_F32_FROM_BF16, UV_EPI_RESID_F32, UV_EPI_GATE_RESID_F32 with exactly the semantics of uv_gemm_bf16_nt (same device code);
+ * out / ldo / gate / gate_tid / gate_stride as there. M arbitrary, N % 256 == 0, K % 128 == 0; anything else is rejected and nothing is
+ * written. Every output element is ONE fixed-order chain over K (one instruction per 128-element K step, K steps in order; no split-K,
+ * no atomics): a row's bits do not depend on M, on the row offset, or on which tile shape of the launch plan computed it. */
+int uv_gemm_mxfp8_nt(const void* A, long lda, const void* A_scale, long ld_as, const void* W, long ldw, const void* W_scale, long ld_ws,
+                     const void* bias_bf16, int M, int N, int K, int epilogue, void* out, long ldo, const float* gate,
+                     const int32_t* gate_tid, long gate_stride, void* stream);
+
 /* C[M,N] = A[M,K] . W[N,K]^T + bias (+ resid), all fp32, exact-f32 MFMA (16x16x4).
  * Replaces Head.head (fp32 island, model.py:286-290) and the VAE's 1x1 convolutions (vae2_2.py:211,249-250,766-767).
  * K % 4 == 0, N % 4 == 0. */

@@ -1,7 +1,8 @@
 """End-to-end generation time (developer tool): WanTI2V.t2v / i2v with the production model sizes (30-block TI2V-5B DiT, full-width VAE,
 random-init weights, synthetic prompt embeddings): 50 UniPC steps with CFG + VAE decode, per stage, for the exact-f32 VAE and the
 f32-grade bf16x6 / f16x3 modes - at the bench size (49 frames of 704 x 1280) and at UniVid's own default workload (121 frames of
-704 x 1280, inference.py:48-50).   env: STEPS (50), FRAMES ("49,121"), PRECS ("fp32,bf16x6,f16x3")"""
+704 x 1280, inference.py:48-50).   env: STEPS (50), FRAMES ("49,121"), PRECS ("fp32,bf16x6,f16x3")
+    --ffn-precision bf16|mxfp8   the DiT's FFN projections in the opt-in MXFP8 mode (WanModel.set_ffn_precision)"""
 import os, sys, time, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from univid_amd import _lib
@@ -15,6 +16,9 @@ with torch.device(dev):
     m = WanModel.from_config(TI2VConfig.dit)
 m = m.eval().requires_grad_(False)
 m.init_weights(0)
+ffn_precision = sys.argv[sys.argv.index("--ffn-precision") + 1] if "--ffn-precision" in sys.argv else "bf16"
+m.set_ffn_precision(ffn_precision)
+print(f"ffn_precision {ffn_precision}", flush=True)
 m.prepare()
 g = torch.Generator(device=dev).manual_seed(1)
 pe = [torch.randn(40, 4096, device=dev, generator=g) * 0.1]
@@ -31,7 +35,7 @@ precs = os.environ.get("PRECS", "fp32,bf16x6,f16x3").split(",")
 for F in frames:
     for prec in precs:
         vae = Wan2_2_VAE(device=dev, seed=0, precision=prec)
-        pipe = WanTI2V(model=m, vae=vae, device=dev)
+        pipe = WanTI2V(model=m, vae=vae, device=dev, ffn_precision=ffn_precision)
         with torch.no_grad():
             # warm-up of both loops (2 steps each): one-time costs - the VAE's weight preparation, the HIP-graph captures of the t2v and i2v
             # forward pairs (one per latent shape and mode; a NEW PROMPT does not recapture) - stay out of the timed generations

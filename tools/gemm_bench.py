@@ -1,6 +1,7 @@
 """GEMM micro-benchmark on the DiT's shapes: every tile config, interleaved rounds in ONE process, random operands.
 
     python tools/gemm_bench.py [--cfgs 0,5,6,7] [--rounds 5] [--check]
+    python tools/gemm_bench.py --mx          the two FFN shapes, bf16 (tile_cfg 0) against MXFP8 (uv_gemm_mxfp8_nt), quantise passes included
 
 Prints median/min TFLOP/s per (shape, config). `--check` compares each config with an fp64 reference on a row sample.
 """
@@ -43,6 +44,58 @@ SHAPES = [
 ]
 
 
+def _median_us(fn, rounds, iters):
+    ts = []
+    for r in range(rounds + 1):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(iters):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        if r:
+            ts.append(e0.elapsed_time(e1) / iters * 1e3)
+    return statistics.median(ts)
+
+
+def bench_mx(rounds, iters):
+    """ffn.0 (GELU) and ffn.2 (gated residual) at the CFG pair's 22 880 rows: the bf16 path (tile_cfg 0) against the MXFP8 path, whose
+    activation-quantise passes (uv_mx_quant_bf16 of ffn.0's input and of `mid`) are timed separately and counted into the pair time.
+    Random operands; one process, the variants interleaved per round by _median_us's caller order."""
+    dev = "cuda"
+    g = torch.Generator(device=dev).manual_seed(1)
+    M, C, F = L2, 3072, 14336
+    u8 = torch.uint8
+    h = (torch.rand(M, C, device=dev, generator=g) * 2 - 1).to(torch.bfloat16)
+    w0 = ((torch.rand(F, C, device=dev, generator=g) * 2 - 1) * 0.05).to(torch.bfloat16)
+    w2 = ((torch.rand(C, F, device=dev, generator=g) * 2 - 1) * 0.02).to(torch.bfloat16)
+    b0 = (torch.rand(F, device=dev, generator=g) - 0.5).to(torch.bfloat16)
+    b2 = (torch.rand(C, device=dev, generator=g) - 0.5).to(torch.bfloat16)
+    x = torch.rand(M, C, device=dev, generator=g)
+    gate = torch.rand(2, C, device=dev, generator=g)
+    tid = (torch.arange(M, device=dev) * 2 // M).to(torch.int32)
+    mid = torch.zeros(M, F, device=dev, dtype=torch.bfloat16)
+    q = {n: (torch.empty(t.shape, dtype=u8, device=dev), torch.empty(t.shape[0], t.shape[1] // 32, dtype=u8, device=dev))
+         for n, t in (("h", h), ("mid", mid), ("w0", w0), ("w2", w2))}
+    _lib.mx_quant(w0, *q["w0"])
+    _lib.mx_quant(w2, *q["w2"])
+    steps = {
+        "bf16 ffn.0 (gelu)": (lambda: _lib.gemm_bf16(h, w0, b0, mid, EPI_GELU_BF16), 2.0 * M * F * C),
+        "bf16 ffn.2 (gate+resid)": (lambda: _lib.gemm_bf16(mid, w2, b2, x, EPI_GATE_RESID_F32, gate=gate, gate_tid=tid), 2.0 * M * F * C),
+        "mx quant h [22880 x 3072]": (lambda: _lib.mx_quant(h, *q["h"]), 0),
+        "mxfp8 ffn.0 (gelu)": (lambda: _lib.gemm_mxfp8(*q["h"], *q["w0"], b0, mid, EPI_GELU_BF16), 2.0 * M * F * C),
+        "mx quant mid [22880 x 14336]": (lambda: _lib.mx_quant(mid, *q["mid"]), 0),
+        "mxfp8 ffn.2 (gate+resid)": (lambda: _lib.gemm_mxfp8(*q["mid"], *q["w2"], b2, x, EPI_GATE_RESID_F32, gate=gate, gate_tid=tid), 2.0 * M * F * C),
+    }
+    us = {}
+    for name, (fn, fl) in steps.items():
+        us[name] = _median_us(fn, rounds, iters)
+        print(f"{name:30s} {us[name]:8.1f} us" + (f"  {fl / us[name] / 1e6:7.1f} TF/s" if fl else ""), flush=True)
+    bf = us["bf16 ffn.0 (gelu)"] + us["bf16 ffn.2 (gate+resid)"]
+    mx = sum(v for k, v in us.items() if k.startswith("mx"))
+    print(f"pair: bf16 {bf:.1f} us, mxfp8 incl. both quantise passes {mx:.1f} us, ratio bf16 / mxfp8 = {bf / mx:.3f}", flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cfgs", default="0,1,2,5,6")
@@ -51,7 +104,11 @@ def main():
     ap.add_argument("--check", action="store_true")
     ap.add_argument("--shapes", default="")
     ap.add_argument("--ws", action="store_true", help="pass a split-K workspace (tile_cfg 19 / 20; tile_cfg 0's ffn.2 strip)")
+    ap.add_argument("--mx", action="store_true", help="ffn.0 + ffn.2: bf16 against MXFP8 (quantise passes timed separately, included in the pair)")
     a = ap.parse_args()
+    if a.mx:
+        _lib.init()
+        return bench_mx(a.rounds, a.iters)
     cfgs = [int(c) for c in a.cfgs.split(",")]
     _lib.init()
     dev = "cuda"

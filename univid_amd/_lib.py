@@ -30,6 +30,8 @@ SIGNATURES = {
     "uv_gemm_bf16_nt_ws": [_P, _L, _P, _L, _P, _I, _I, _I, _I, _P, _L, _P, _P, _L, _I, _P, _L, _P],
     "uv_gemm_splitk_ws_bytes": [_I, _I, _I],
     "uv_gemm_f16_nt": [_P, _L, _P, _L, _P, _I, _I, _I, _I, _P, _L, _P, _P, _L, _I, _P],
+    "uv_mx_quant_bf16": [_P, _L, _P, _L, _P, _L, _I, _I, _P],
+    "uv_gemm_mxfp8_nt": [_P, _L, _P, _L, _P, _L, _P, _L, _P, _I, _I, _I, _I, _P, _L, _P, _P, _L, _P],
     "uv_gemm_f32_nt": [_P, _L, _P, _L, _P, _I, _I, _I, _P, _L, _P, _L, _P],
     "uv_gemm_bf16_nt_ssq": [_P, _L, _P, _L, _P, _I, _I, _I, _P, _L, _P, _L, _I, _P],
     "uv_rms_scale_from_ssq": [_P, _L, _I, _I, _I, _F, _P, _P],
@@ -287,6 +289,39 @@ def gemm_bf16(a, w, bias, out, epi, M=None, gate=None, gate_tid=None, tile_cfg=0
         return out
     call("uv_gemm_f16_nt" if f16 else "uv_gemm_bf16_nt", ptr(a), a.stride(0), ptr(w), w.stride(0), ptr(bias), M, N, K, epi, ptr(out), out.stride(0),
          ptr(gate), ptr(gate_tid), 0 if gate is None else gate.stride(0), tile_cfg, stream_ptr(), flops=2 * M * N * K)
+    return out
+
+
+def mx_quant(x, codes, scales, M=None, K=None):
+    """x bf16 [rows, >= K] -> OCP MXFP8: codes uint8 [rows, >= K] (e4m3fn) and scales uint8 [rows, >= K / 32] (one e8m0 byte per 32
+    consecutive K elements of a row; include/univid_hip.h states the rule). Quantises the first M rows / K columns (defaults: all of x)."""
+    _chk(x, torch.bfloat16, "mx_quant.x")
+    _chk(codes, torch.uint8, "mx_quant.codes")
+    _chk(scales, torch.uint8, "mx_quant.scales")
+    M = x.shape[0] if M is None else M
+    K = x.shape[1] if K is None else K
+    if x.dim() != 2 or codes.dim() != 2 or scales.dim() != 2 or M > min(x.shape[0], codes.shape[0], scales.shape[0]) or \
+            K > min(x.shape[1], codes.shape[1]) or K > 32 * scales.shape[1]:
+        raise UnividHipError(f"mx_quant: x {tuple(x.shape)} / codes {tuple(codes.shape)} / scales {tuple(scales.shape)} do not fit M = {M}, K = {K}")
+    call("uv_mx_quant_bf16", ptr(x), x.stride(0), ptr(codes), codes.stride(0), ptr(scales), scales.stride(0), M, K, stream_ptr())
+    return codes, scales
+
+
+def gemm_mxfp8(a, a_scale, w, w_scale, bias, out, epi, M=None, gate=None, gate_tid=None):
+    """gemm_bf16 for MXFP8 operands: a [M,K] / w [N,K] uint8 e4m3fn codes with their e8m0 scales [rows, >= K / 32] uint8 (mx_quant);
+    bias bf16 [N] | None; out per epilogue, EPI_BF16 ... EPI_GATE_RESID_F32 (see include/univid_hip.h)."""
+    for t, n in ((a, "a"), (a_scale, "a_scale"), (w, "w"), (w_scale, "w_scale")):
+        _chk(t, torch.uint8, "gemm_mxfp8." + n)
+    if bias is not None:
+        _chk(bias, torch.bfloat16, "gemm_mxfp8.bias")
+    M = a.shape[0] if M is None else M
+    N, K = w.shape
+    if a.shape[1] < K or M > min(a.shape[0], a_scale.shape[0]) or a_scale.shape[1] * 32 < K or w_scale.shape[1] * 32 < K or w_scale.shape[0] < N:
+        raise UnividHipError(f"gemm_mxfp8: a {tuple(a.shape)} / a_scale {tuple(a_scale.shape)} / w {tuple(w.shape)} / w_scale "
+                             f"{tuple(w_scale.shape)} do not fit M = {M}")
+    call("uv_gemm_mxfp8_nt", ptr(a), a.stride(0), ptr(a_scale), a_scale.stride(0), ptr(w), w.stride(0), ptr(w_scale), w_scale.stride(0),
+         ptr(bias), M, N, K, epi, ptr(out), out.stride(0), ptr(gate), ptr(gate_tid), 0 if gate is None else gate.stride(0), stream_ptr(),
+         flops=2 * M * N * K)
     return out
 
 

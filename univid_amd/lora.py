@@ -192,6 +192,12 @@ def attach_adapter_(model: nn.Module, name: str, factors, cfg: dict, weight: flo
                                       f"only those run un-merged")
         if name in getattr(lin, "_uv_lora", {}):
             raise RuntimeError(f"an adapter named {name!r} is already attached to {path!r}")
+        own = _owner(model, path)
+        if getattr(own, "ffn_precision", "bf16") == "mxfp8" and hasattr(own, "ffn") and any(lin is own.ffn[i] for i in (0, 2)):
+            raise NotImplementedError(
+                f"{path!r}: an un-merged adapter (merge=False) on ffn.0 / ffn.2 cannot be combined with ffn_precision 'mxfp8' (the MXFP8 GEMM "
+                f"has no adapter slot). Merge the adapter (merge=True: the merged weights are re-quantised) or call "
+                f"set_ffn_precision('bf16') first. Un-merged adapters on the attention projections work in both modes.")
         todo.append((path, lin, a, b, module_scaling(cfg, path, a.shape[0])))
     for path, lin, a, b, s in todo:
         dev = lin.weight.device

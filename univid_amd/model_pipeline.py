@@ -53,6 +53,7 @@ class CrossAttentionConfig:
     lora_dropout: float = 0.1
     lora_target_strategy: str = "your_method_here"
     lora_merge: bool = True       # CrossAttentionFusionPipeline.load_lora: fold the adapter into the dense weights (False: attach it un-merged)
+    ffn_precision: str = "bf16"   # "mxfp8": the DiT's ffn.0 / ffn.2 on MXFP8 operands (WanModel.set_ffn_precision), an opt-in fast mode
     guidance_strength: float = 1.0
     bagel_cross_attn_layers: List[int] = None
     freeze_bagel: bool = True
@@ -376,6 +377,11 @@ class CrossAttentionFusionPipeline:
             wan_pipeline = self._initialize_wan22(wan_config)
         self.wan_pipeline = wan_pipeline
         self.dit_model = wan_pipeline.model
+        # a pipeline built here got the config's mode in its constructor; an INJECTED one keeps the mode it came with unless the config asks
+        # for another than the default
+        ffn_precision = getattr(config, "ffn_precision", "bf16")
+        if ffn_precision != "bf16" and hasattr(self.dit_model, "set_ffn_precision") and ffn_precision != self.dit_model.ffn_precision:
+            self.dit_model.set_ffn_precision(ffn_precision)
         self.vae_model = wan_pipeline.vae
         self.text_encoder = wan_pipeline.text_encoder
         # native_text_weight=False: the reference's closures on the model's generic path (kept as the comparison the tests and bench use)
@@ -403,7 +409,7 @@ class CrossAttentionFusionPipeline:
         self._check_gpu("wan_gpu")
         try:
             return WanTI2V(config=wan_config, checkpoint_dir=path, device_id=self.config.wan_gpu, rank=0, t5_fsdp=False, dit_fsdp=False,
-                           use_sp=False)
+                           use_sp=False, ffn_precision=getattr(self.config, "ffn_precision", "bf16"))
         except Exception as e:
             raise RuntimeError(f"Wan2.2 initialization failed: {e}") from e
 

@@ -67,6 +67,38 @@ class _Prepared:
         self.b = None if lin.bias is None else lin.bias.detach().to(BF16).contiguous()
 
 
+FFN_PRECISIONS = ("bf16", "mxfp8")
+
+
+class _PreparedMx:
+    """OCP MXFP8 operand of one nn.Linear for uv_gemm_mxfp8_nt: e4m3fn codes [N, K] and e8m0 scales [N, K / 32] (uint8 both), quantised
+    by uv_mx_quant_bf16 from the bf16 copy the bf16 path reads - which is not kept - and the bf16 bias."""
+    __slots__ = ("w", "s", "b")
+
+    def __init__(self, lin: nn.Linear):
+        p = _Prepared(lin)
+        N, K = p.w.shape
+        self.w = torch.empty(N, K, dtype=torch.uint8, device=p.w.device)
+        self.s = torch.empty(N, K // 32, dtype=torch.uint8, device=p.w.device)
+        _lib.mx_quant(p.w, self.w, self.s)
+        self.b = p.b
+
+
+def _check_ffn_precision(mode, dim, ffn_dim, ffn):
+    """Everything that can refuse a mode, before any state changes."""
+    if mode not in FFN_PRECISIONS:
+        raise ValueError(f"ffn_precision {mode!r}: one of {FFN_PRECISIONS}")
+    if mode == "mxfp8":
+        if dim % 256 or ffn_dim % 256:
+            raise ValueError(f"ffn_precision 'mxfp8' needs dim and ffn_dim to be multiples of 256 (dim {dim}, ffn_dim {ffn_dim}): "
+                             "uv_gemm_mxfp8_nt takes N % 256 == 0 and K % 128 == 0")
+        if any(getattr(ffn[i], "_uv_lora", None) for i in (0, 2)):
+            raise NotImplementedError(
+                "ffn_precision 'mxfp8' and an un-merged LoRA adapter (merge=False) on ffn.0 / ffn.2 cannot be combined: the MXFP8 GEMM has no "
+                "adapter slot. Detach the adapter or merge it (merge=True: the merged weights are re-quantised), or keep ffn_precision 'bf16'. "
+                "Un-merged adapters on the attention projections work in both modes.")
+
+
 # ---- un-merged LoRA (univid_amd/lora.py attaches; peft lora/layer.py Linear.forward) ---------------------------------------------
 # An attached adapter lives on its nn.Linear as `lin._uv_lora = {adapter name: {"A": [r, in], "B": [out, r], "scaling": s, "weight": w}}`
 # and never touches the fp32 master weight. The projections that read ONE activation share one slot of whole 128-column groups behind
@@ -376,13 +408,25 @@ class WanAttentionBlock(nn.Module):
         self.modulation = nn.Parameter(torch.randn(1, 6, dim) / dim ** 0.5)
         self._prep = None
         self._slots = {}
+        self.ffn_precision = "bf16"      # set_ffn_precision: instance state, never a module global
 
     def prepare(self):
         self.self_attn.prepare()
         self.cross_attn.prepare()
         self._prepare_ffn()
 
+    def set_ffn_precision(self, mode):
+        """"bf16" (default: the reference's arithmetic) or "mxfp8": ffn.0 / ffn.2 on the block-scaled matrix instructions with OCP MXFP8
+        operands (uv_gemm_mxfp8_nt) - a labelled fast mode, narrower than the reference. The FFN operands are re-prepared on the next forward."""
+        _check_ffn_precision(mode, self.dim, self.ffn_dim, self.ffn)
+        self.ffn_precision = mode
+        self._prep = None
+
     def _prepare_ffn(self):
+        if self.ffn_precision == "mxfp8":
+            _check_ffn_precision("mxfp8", self.dim, self.ffn_dim, self.ffn)
+            self._prep, self._slots = {"ffn0": _PreparedMx(self.ffn[0]), "ffn2": _PreparedMx(self.ffn[2])}, {"ffn0": None, "ffn2": None}
+            return
         p0, s0 = _prepare_group({"ffn0": self.ffn[0]})
         p2, s2 = _prepare_group({"ffn2": self.ffn[2]})
         self._prep, self._slots = {**p0, **p2}, {"ffn0": s0, "ffn2": s2}
@@ -442,6 +486,17 @@ class WanAttentionBlock(nn.Module):
         # input hold whatever the buffer held (rows are independent: nothing of them reaches a row that is read), their outputs are never
         # read (ffn.2 runs on L rows); results unchanged (a row's arithmetic is the same in both kernels)
         _lib.layernorm_mod(x, h, L, C, self.eps, mode=1, tab=tab, shift_off=3 * C, scale_off=4 * C, tid=tid)
+        if self.ffn_precision == "mxfp8":
+            # the opt-in fast mode: both projections' operands as OCP MXFP8 (quantised per row: no pad rows, no slot), same fused epilogues
+            p0, p2, F, u8 = self._prep["ffn0"], self._prep["ffn2"], self.ffn_dim, torch.uint8
+            hq, hs = torch.empty(L, C, dtype=u8, device=dev), torch.empty(L, C // 32, dtype=u8, device=dev)
+            _lib.mx_quant(h, hq, hs, M=L, K=C)
+            mid = torch.empty(L, F, dtype=BF16, device=dev)
+            _lib.gemm_mxfp8(hq, hs, p0.w, p0.s, p0.b, mid, EPI_GELU_BF16, M=L)
+            mq, ms = torch.empty(L, F, dtype=u8, device=dev), torch.empty(L, F // 32, dtype=u8, device=dev)
+            _lib.mx_quant(mid, mq, ms)
+            _lib.gemm_mxfp8(mq, ms, p2.w, p2.s, p2.b, x, EPI_GATE_RESID_F32, M=L, gate=tab[:, 5 * C:], gate_tid=tid)
+            return
         h_full = _slotted(h_full, C, self._slots["ffn0"], L)
         mid = _act_buf(Lf, self.ffn_dim, (self._slots["ffn2"],), dev)
         _lib.gemm_bf16(h_full, self._prep["ffn0"].w, self._prep["ffn0"].b, mid, EPI_GELU_BF16, M=Lf)
@@ -653,6 +708,7 @@ class WanModel(nn.Module):
         self.cache_context = False
         self.sp = None   # SeqParallel when Ulysses sequence parallelism is enabled (enable_sequence_parallel)
         self._text_weight = None  # (per-sample weights, rows, layers | None): set_text_weight
+        self.ffn_precision = "bf16"  # set_ffn_precision
         self.dedup_twins = True   # block 0's self-attention half once for samples that enter with identical rows (the CFG pair); A/B switch
         self.register_load_state_dict_post_hook(lambda m, _k: m.invalidate())
 
@@ -667,6 +723,23 @@ class WanModel(nn.Module):
             b.self_attn._prep = None
             b.cross_attn._prep = None
             b.cross_attn._kv_cache = {}
+
+    def set_ffn_precision(self, mode):
+        """Arithmetic of every block's ffn.0 / ffn.2: "bf16" (default; like for like with the reference) or "mxfp8" - OCP MXFP8 operands
+        (e4m3 elements, one power-of-two scale per 32 K elements, activations and weights alike) on the block-scaled matrix instructions,
+        fp32 accumulate, same fused epilogues: a labelled FAST mode, narrower than the reference's arithmetic (README). In "mxfp8" the
+        blocks hold codes + scales instead of the bf16 weight copies of the two projections. Everything else in the block stays bf16.
+        Merged LoRA works (weights are re-quantised after invalidate()); an un-merged adapter on ffn.0 / ffn.2 raises NotImplementedError
+        here - and attaching one while the mode is "mxfp8" raises in LoRAManager - before any state changes. Calls invalidate(): the
+        prepared-weights generation moves on, so captured HIP graphs (WanTI2V) re-capture."""
+        for b in self.blocks:
+            _check_ffn_precision(mode, b.dim, b.ffn_dim, b.ffn)
+        if not len(self.blocks):
+            _check_ffn_precision(mode, 256, 256, {0: None, 2: None})
+        self.ffn_precision = mode
+        for b in self.blocks:
+            b.ffn_precision = mode
+        self.invalidate()
 
     def prepare(self):
         """Materialise the bf16 operand copies autocast would create on every call of the reference."""

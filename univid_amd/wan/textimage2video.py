@@ -238,7 +238,7 @@ class _GraphedPair:
 class WanTI2V:
     def __init__(self, config=TI2VConfig, checkpoint_dir=None, device_id=0, rank=0, t5_fsdp=False, dit_fsdp=False,
                  use_sp=False, t5_cpu=False, init_on_cpu=True, convert_model_dtype=False, *, model: WanModel = None,
-                 vae=None, text_encoder: Optional[Callable] = None, device=None):
+                 vae=None, text_encoder: Optional[Callable] = None, device=None, ffn_precision=None):
         if t5_fsdp or dit_fsdp:
             raise NotImplementedError("FSDP is not part of this build (UniVid passes False, models/model_pipeline.py:2205-2207; "
                                       "the fp32 masters + bf16 operands of the 5B DiT are 30 GB of a 288 GB GPU)")
@@ -272,6 +272,11 @@ class WanTI2V:
             from .checkpoint import load_wan_model
             model = load_wan_model(checkpoint_dir)
         self.model = model.eval().requires_grad_(False).to(self.device)
+        if ffn_precision is not None and ffn_precision != self.model.ffn_precision:
+            # "bf16" | "mxfp8" (WanModel.set_ffn_precision): the opt-in MXFP8 mode of the FFN projections; None keeps the mode the model
+            # came with ("bf16" unless it was switched). The runners' key carries the model's prepared-weights generation, so a later
+            # switch on self.model re-captures
+            self.model.set_ffn_precision(ffn_precision)
         if checkpoint_dir is not None:
             # textimage2video.py:88-103: the VAE and the text encoder come from the same directory. Each is loaded when its
             # file is there and no instance was injected; a missing file leaves the stage to be injected (vae= / text_encoder=)
