@@ -294,7 +294,8 @@ __global__ void video_out_kernel(const float* y, long ld, float* vid, int F, int
         const int c = (int)(r / T);
         const int ch = c * 4 + (w & 1) * 2 + (h & 1);
         const float v = y[(((long)t * Hp + (h >> 1)) * Wp + (w >> 1)) * ld + ch];
-        vid[(((long)c * F + f0 + t) * H + h) * W + w] = fminf(fmaxf(v, -1.0f), 1.0f);
+        // torch.clamp semantics: a NaN stays NaN (fminf / fmaxf return the other operand: a decode that went NaN came out as -1, a valid dark video)
+        vid[(((long)c * F + f0 + t) * H + h) * W + w] = v < -1.0f ? -1.0f : (v > 1.0f ? 1.0f : v);
     }
 }
 
