@@ -282,6 +282,12 @@ int uv_dpmpp_update(const float* x, const float* m0, const float* m1, float* out
 int uv_conv3d_f32(const float* in, long ld_in, int Tin, int Hin, int Win, const float* w, const float* bias, float* out,
                   long ldo, int Tout, int Hout, int Wout, int Cin, int Cout, int kt, int kh, int kw, int st, int sh, int sw,
                   int t_off, int ph, int pw, int up, int interleave, const float* resid, long ldr, void* stream);
+/* The launch plan of a uv_conv3d_* call of this geometry on the current device (256 CUs without one) under the current UV_OPT_CONV_HALO:
+ * the kernel's name (one of 23: 16 gather-kernel instantiations "G<rows>x<columns>+<prec>" / "G160+<prec>", 7 LDS-halo kernels "HALO_*"),
+ * and its grid, tiles_m row tiles (halo kernels: pixel patches) x tiles_n output-channel tiles. prec: 0 uv_conv3d_f32, 1 / 2 uv_conv3d_bf16x3
+ * without / with in_split, 3 uv_conv3d_bf16x6, 4 uv_conv3d_f16x3. Runs the geometry checks of the call itself. Host only. */
+int uv_conv3d_plan(int prec, int Tout, int Hout, int Wout, int Hin, int Win, int Cin, int Cout, int kt, int kh, int kw, int st, int sh,
+                   int sw, int ph, int pw, int up, int interleave, char* kernel, int len, int* tiles_m, int* tiles_n);
 /* uv_conv3d_f32 with the products computed on the bf16 matrix pipe by exact three-way splitting of both f32 operands (x = x0 + x1 + x2,
  * round-to-nearest bf16 planes; the six terms with i + j <= 2; f32 accumulate): per-product error below 2^-26 (under f32 rounding).
  * Activations / bias / residual / output as in uv_conv3d_f32 (split in registers); w_split6 = uv_split_weights_bf16x6 of the f32

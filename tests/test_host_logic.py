@@ -634,6 +634,115 @@ def test_attention_launch_plan_is_pinned():
     assert lib.uv_flash_attn_plan(1, 0, 64, 1, 128, 128, 64, 0, ctypes.create_string_buffer(8), 8, None, None, None) != 0
 
 
+def test_conv_launch_plan_is_pinned():
+    """uv_conv3d_plan is plan_conv's (csrc/conv_args.h) externally visible output: which of the 23 convolution kernels a uv_conv3d_* call
+    launches, on how many row tiles (halo kernels: pixel patches) x output-channel tiles. Without a device the library plans for 256 CUs,
+    which is also what an MI355X reports; the big-tile thresholds are literal numbers either way. tests/test_conv_kernels.py asserts the
+    plan of every case it launches; here the thresholds themselves are pinned from both sides."""
+    lib = _lib.load()
+    _lib.reset_options()
+
+    def plan(prec, Tout, Hout, Wout, Hin, Win, Cin, Cout, kt, kh, kw, **kw_):
+        p = _lib.conv_plan(prec, Tout, Hout, Wout, Hin, Win, Cin, Cout, kt, kh, kw, **kw_)
+        return p["kernel"], p["tiles_m"], p["tiles_n"]
+
+    # the name table next to enum ConvKernel: 23 distinct names
+    src = open(os.path.join(os.path.dirname(_lib.LIB_PATH), "csrc", "conv_args.h")).read()
+    names = re.findall(r'"([^"]+)"', re.search(r"kConvKernelName\[[^\]]*\]\s*=\s*\{(.*?)\};", src, flags=re.S).group(1))
+    assert len(names) == 23 and len(set(names)) == 23
+
+    down = dict(sh=2, sw=2)        # Resample's stride-2 1x3x3 behind ZeroPad2d(0, 1, 0, 1)
+    for prec in (1, 2, 4):
+        # case A: 32 600 pixels = 128 tiles of 256 rows; x 2 column tiles = 256 workgroups, the threshold itself
+        assert plan(prec, 1, 163, 200, 326, 400, 32, 160, 1, 3, 3, **down) == (f"G256x128+{prec}", 128, 2)
+        assert plan(prec, 1, 163, 200, 326, 400, 32, 320, 1, 3, 3, **down) == (f"G256x256+{prec}", 128, 2)
+        # case B: 32 437 pixels = 127 tiles of 256 rows: 254 workgroups, one row tile below the threshold
+        assert plan(prec, 1, 163, 199, 326, 398, 32, 160, 1, 3, 3, **down) == (f"G128x128+{prec}", 254, 2)
+        # case C: 127 row tiles x 2 tiles of 256 columns = 254 misses by two; x 3 tiles of 128 columns does not
+        assert plan(prec, 1, 127, 256, 254, 512, 32, 320, 1, 3, 3, **down) == (f"G256x128+{prec}", 127, 3)
+        assert plan(prec, 1, 127, 256, 254, 512, 32, 128, 1, 3, 3, **down) == (f"G128x128+{prec}", 254, 1)
+        # Cout < 256 never takes the 256-wide tile, however many rows
+        assert plan(prec, 2, 163, 200, 326, 400, 32, 252, 1, 3, 3, **down) == (f"G256x128+{prec}", 255, 2)
+        # the other launch forms plan alike: time_conv with interleave, an output-phase launch, 1x1x1
+        assert plan(prec, 1, 163, 200, 163, 200, 32, 512, 3, 1, 1, interleave=1) == (f"G256x256+{prec}", 128, 2)
+        assert plan(prec, 1, 163, 200, 163, 200, 32, 320, 1, 2, 2, ph=1, pw=0, up=3) == (f"G256x256+{prec}", 128, 2)
+        assert plan(prec, 1, 110, 200, 110, 200, 32, 640, 1, 1, 1) == (f"G256x256+{prec}", 86, 3)
+        assert plan(prec, 1, 108, 200, 108, 200, 32, 640, 1, 1, 1) == (f"G256x128+{prec}", 85, 5)      # 85 x 3 = 255
+    # narrow and 160-wide outputs, 3 x 19 x 23 = 1 311 pixels
+    small = (3, 19, 23, 19, 23, 64)
+    for prec in (0, 3, 4):
+        assert plan(prec, *small, 12, 3, 3, 3, ph=1, pw=1) == (f"G256x16+{prec}", 6, 1)
+        assert plan(prec, *small, 16, 3, 3, 3, ph=1, pw=1) == (f"G256x16+{prec}", 6, 1)
+        assert plan(prec, *small, 20, 3, 3, 3, ph=1, pw=1) == (f"G128x128+{prec}", 11, 1)
+    for prec in (1, 2):
+        assert plan(prec, *small, 12, 3, 3, 3, ph=1, pw=1) == (f"G128x128+{prec}", 11, 1)
+    assert plan(0, *small, 160, 3, 3, 3, ph=1, pw=1) == ("G160+0", 11, 1)            # 128 rows per tile
+    assert plan(0, *small, 320, 3, 3, 3, ph=1, pw=1) == ("G160+0", 11, 2)
+    assert plan(3, *small, 160, 3, 3, 3, ph=1, pw=1) == ("G160+3", 21, 1)            # 64 rows per tile
+    assert plan(3, *small, 320, 3, 3, 3, ph=1, pw=1) == ("G160+3", 21, 2)
+    assert plan(0, *small, 640, 3, 3, 3, ph=1, pw=1) == ("G128x128+0", 11, 5)        # a multiple of 128 as well: 128-wide tiles
+    for prec in (1, 2, 4):
+        assert plan(prec, *small, 160, 3, 3, 3, ph=1, pw=1) == (f"G128x128+{prec}", 11, 2)
+    # automatic: a halo kernel where four frames of patches fill 256 CUs (exact f32: twice that)
+    assert plan(4, 1, 45, 80, 45, 80, 64, 128, 3, 3, 3, ph=1, pw=1) == ("G128x128+4", 29, 1)        # 4 x 15 patches
+    assert plan(4, 1, 360, 640, 360, 640, 64, 128, 3, 3, 3, ph=1, pw=1) == ("HALO_F16_128", 900, 1)     # 920 square patches against 900
+    assert plan(0, 1, 64, 128, 64, 128, 64, 128, 3, 3, 3, ph=1, pw=1) == ("G128x128+0", 64, 1)          # 4 x 64 patches of 8 x 16 < 512
+    assert plan(0, 1, 64, 256, 64, 256, 64, 128, 3, 3, 3, ph=1, pw=1) == ("HALO_F32_128", 128, 1)       # 4 x 128 = 512
+    try:
+        _lib.set_option(_lib.OPT_CONV_HALO, 1)
+        halo = lambda prec, T, H, W, ci, co, kt, up=0: plan(prec, T, H * (2 if up == 1 else 1), W * (2 if up == 1 else 1), H, W, ci, co, kt, 3, 3, ph=1, pw=1, up=up)
+        assert halo(4, 2, 8, 32, 64, 128, 3) == ("HALO_F16_128", 2, 1)               # kt * Cin / 32 = 6
+        assert halo(4, 2, 8, 32, 64, 256, 1) == ("HALO_F16_128", 2, 2)               # 2
+        assert halo(4, 2, 8, 32, 32, 128, 3) == ("G128x128+4", 4, 1)                 # 3: odd, the gather kernel
+        assert halo(4, 2, 8, 32, 96, 128, 1) == ("G128x128+4", 4, 1)                 # 3
+        assert halo(4, 2, 8, 32, 96, 128, 3) == ("G128x128+4", 4, 1)                 # 9
+        assert halo(4, 2, 16, 16, 64, 128, 3) == ("HALO_F16_SQUARE", 2, 1)           # one 16 x 16 patch against two 8 x 32
+        assert halo(4, 2, 45, 80, 64, 128, 3) == ("HALO_F16_SQUARE", 30, 1)          # 15 against 18
+        assert halo(4, 1, 13, 48, 64, 256, 1) == ("HALO_F16_SQUARE", 3, 2)           # 3 against 4
+        assert halo(4, 2, 19, 23, 64, 128, 3) == ("HALO_F16_128", 6, 1)              # 4 against 3
+        assert halo(4, 2, 19, 23, 64, 160, 3) == ("HALO_F16_160", 6, 1)
+        assert halo(4, 2, 19, 23, 32, 320, 3) == ("HALO_F16_160", 6, 2)              # no parity rule on the 160-wide kernel
+        assert halo(4, 3, 19, 40, 64, 12, 3) == ("HALO_F16_N16", 18, 1)
+        assert halo(4, 3, 19, 40, 64, 16, 1) == ("HALO_F16_N16", 18, 1)
+        assert halo(4, 3, 19, 40, 64, 12, 1, up=1) == ("G256x16+4", 36, 1)           # the narrow halo kernel: plain geometry only
+        assert halo(4, 3, 19, 40, 64, 96, 3) == ("G128x128+4", 18, 1)                # neither 128- nor 160-wide tiles
+        assert halo(4, 2, 9, 13, 64, 128, 1, up=1) == ("HALO_F16_128", 6, 1)         # 18 x 26 upsampled: 3 patches a frame
+        assert halo(0, 2, 19, 23, 64, 160, 3) == ("HALO_F32_160", 12, 1)             # exact f32: 8 x 16 patches
+        assert halo(0, 2, 19, 23, 64, 320, 3) == ("HALO_F32_160", 12, 2)
+        assert halo(0, 2, 19, 23, 32, 128, 3) == ("HALO_F32_128", 12, 1)
+        assert halo(0, 2, 19, 23, 32, 384, 1) == ("HALO_F32_128", 12, 3)
+        assert halo(0, 2, 19, 23, 32, 12, 3) == ("G256x16+0", 4, 1)
+        assert halo(3, 2, 19, 23, 64, 128, 3) == ("HALO_BF16X6", 6, 1)
+        assert halo(3, 2, 19, 23, 64, 256, 1) == ("HALO_BF16X6", 6, 2)
+        assert halo(3, 2, 19, 23, 64, 160, 3) == ("G160+3", 14, 1)                   # bf16x6: whole 128-wide tiles only
+        assert halo(3, 2, 19, 23, 64, 12, 3) == ("G256x16+3", 4, 1)
+        for prec in (1, 2):
+            assert halo(prec, 2, 19, 23, 64, 128, 3) == (f"G128x128+{prec}", 7, 1)   # bf16x3 has no halo kernel
+        for prec in (0, 3, 4):
+            # the halo geometry, but an output-phase launch (halo kernels store to plain positions) or interleave, a stride, another padding
+            for up in (2, 3, 4, 5):
+                assert plan(prec, 2, 19, 23, 19, 23, 64, 128, 1, 3, 3, ph=1, pw=1, up=up) == (f"G128x128+{prec}", 7, 1), (prec, up)
+            assert plan(prec, 2, 19, 23, 19, 23, 64, 128, 3, 3, 3, ph=1, pw=1, interleave=1) == (f"G128x128+{prec}", 7, 1)
+            assert plan(prec, 2, 19, 23, 19, 23, 64, 128, 3, 3, 3, ph=1, pw=1, st=2)[0] == f"G128x128+{prec}"
+            assert plan(prec, 2, 19, 23, 19, 23, 64, 128, 3, 3, 3, ph=0, pw=1)[0] == f"G128x128+{prec}"
+            assert plan(prec, 2, 10, 12, 19, 23, 64, 128, 1, 3, 3, ph=1, pw=1, sh=2, sw=2)[0] == f"G128x128+{prec}"
+        _lib.set_option(_lib.OPT_CONV_HALO, 0)
+        for prec in (0, 3, 4):
+            assert halo(prec, 2, 19, 23, 64, 128, 3) == (f"G128x128+{prec}", 7, 1)
+            assert halo(prec, 1, 360, 640, 64, 128, 3) == (("G256x128+4", 900, 1) if prec == 4 else (f"G128x128+{prec}", 1800, 1))
+        assert halo(4, 3, 19, 40, 64, 12, 3) == ("G256x16+4", 9, 1)
+        assert halo(0, 2, 19, 23, 64, 160, 3) == ("G160+0", 7, 1)
+    finally:
+        _lib.reset_options()
+    # what conv_common refuses, the query refuses
+    for bad in (dict(Cin=48), dict(Cout=10), dict(Tout=0), dict(up=6), dict(up=2, sh=2), dict(interleave=1, Cout=12), dict(prec=5)):
+        a = dict(prec=0, Tout=2, Hout=19, Wout=23, Hin=19, Win=23, Cin=64, Cout=128, kt=1, kh=3, kw=3)
+        a.update(bad)
+        with pytest.raises(_lib.UnividHipError):
+            _lib.conv_plan(**a)
+    assert lib.uv_conv3d_plan(0, 2, 19, 23, 19, 23, 64, 128, 1, 3, 3, 1, 1, 1, 1, 1, 0, 0, None, 0, None, None) != 0
+
+
 def test_graph_runner_cache_policy():
     """WanTI2V keeps the `max_graph_runners` most recently used captured graphs (host logic only - stand-ins for the runners; the replay
     itself is tests/test_gpu_parity.py::test_graph_runner_serves_new_prompts_without_recapture_and_never_goes_stale): a hit moves the

@@ -74,6 +74,7 @@ SIGNATURES = {
                          _P, _L, _I, _P],
     "uv_conv3d_f16x3": [_P, _L, _I, _I, _I, _P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I,
                         _P, _L, _F, _P, _P],
+    "uv_conv3d_plan": [_I] * 18 + [_c.c_char_p, _I, _c.POINTER(_I), _c.POINTER(_I)],
     "uv_vae_split_f16": [_P, _L, _P, _L, _L, _I, _P, _P],
     "uv_split_weights_f16x3": [_P, _P, _L, _F, _P],
     "uv_split_weights_bf16x3": [_P, _P, _L, _P],
@@ -423,6 +424,19 @@ def attn_plan(Lq, Lk, D, batch=1, H=1, f16=False):
     if lib.uv_flash_attn_plan(batch, Lq, Lk, H, D, H * D, ldvt, int(f16), buf, 96, ctypes.byref(qb), ctypes.byref(n12), ctypes.byref(grid)) != 0:
         raise UnividHipError(lib.uv_last_error().decode())
     return dict(kernel=buf.value.decode(), q_blocks=qb.value, n12=n12.value, grid=grid.value)
+
+
+def conv_plan(prec, Tout, Hout, Wout, Hin, Win, Cin, Cout, kt, kh, kw, st=1, sh=1, sw=1, ph=0, pw=0, up=0, interleave=0):
+    """Launch plan of a uv_conv3d_* call of this geometry on the current device - 256 CUs without one - under the current OPT_CONV_HALO:
+    dict(kernel=name, tiles_m=row tiles or pixel patches, tiles_n=output-channel tiles). prec: 0 f32, 1 / 2 bf16x3 without / with
+    in_split, 3 bf16x6, 4 f16x3."""
+    buf = ctypes.create_string_buffer(32)
+    tm, tn = _I(0), _I(0)
+    lib = load()
+    if lib.uv_conv3d_plan(prec, Tout, Hout, Wout, Hin, Win, Cin, Cout, kt, kh, kw, st, sh, sw, ph, pw, up, interleave, buf, 32,
+                          ctypes.byref(tm), ctypes.byref(tn)) != 0:
+        raise UnividHipError(lib.uv_last_error().decode())
+    return dict(kernel=buf.value.decode(), tiles_m=tm.value, tiles_n=tn.value)
 
 
 def layernorm_mod(x, out, L, C, eps, mode=0, tab=None, shift_off=0, scale_off=0, tid=None, w=None, b=None,

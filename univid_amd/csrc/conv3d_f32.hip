@@ -393,29 +393,38 @@ static int conv_common(const float* in, long ld_in, int Tin, int Hin, int Win, c
                        int sw, int t_off, int ph, int pw, int up, int interleave, const float* resid, long ldr, int prec,
                        void* stream, float out_scale = 1.0f, const float* act_scale = nullptr) {
     UV_CHECK_ARG(in && w && out, "uv_conv3d: null pointer");
-    UV_CHECK_ARG(Cin % 32 == 0, "uv_conv3d: Cin=%d must be a multiple of 32 (pad channels with zeros)", Cin);
-    UV_CHECK_ARG(Cout % 4 == 0, "uv_conv3d: Cout=%d must be a multiple of 4", Cout);
+    ConvArgs a;
+    if (conv_geometry(a, Tout, Hout, Wout, Hin, Win, Cin, Cout, kt, kh, kw, st, sh, sw, ph, pw, up, interleave) != 0) return -1;
     UV_CHECK_ARG(ld_in % 4 == 0 && ldo % 4 == 0 && ldr % 4 == 0 && ld_in >= Cin, "uv_conv3d: bad leading dimensions");
-    UV_CHECK_ARG(Tout > 0 && Hout > 0 && Wout > 0 && kt > 0 && kh > 0 && kw > 0, "uv_conv3d: bad geometry");
-    UV_CHECK_ARG(!interleave || (Cout % 8 == 0 && !resid), "uv_conv3d: interleave needs Cout %% 8 == 0 and no residual");
-    UV_CHECK_ARG(up >= 0 && up <= 5, "uv_conv3d: up=%d (0 plain, 1 nearest-2x folded into the gather, 2..5 one output phase of it)", up);
-    UV_CHECK_ARG(up < 2 || (!resid && !interleave && sh == 1 && sw == 1 && st == 1), "uv_conv3d: an output-phase launch (up >= 2) takes no residual, interleave or stride");
+    UV_CHECK_ARG(!interleave || !resid, "uv_conv3d: interleave needs Cout %% 8 == 0 and no residual");
+    UV_CHECK_ARG(up < 2 || !resid, "uv_conv3d: an output-phase launch (up >= 2) takes no residual, interleave or stride");
     UV_CHECK_ARG((((uintptr_t)in | (uintptr_t)w | (uintptr_t)out | (uintptr_t)bias | (uintptr_t)resid) & 15) == 0,
                  "uv_conv3d: pointers must be 16-byte aligned");
-    ConvArgs a;
     a.in = in; a.w = (const float*)w; a.bias = bias; a.resid = resid; a.out = out; a.zeros = uv_zero_page();
     UV_CHECK_ARG(a.zeros, "uv_conv3d: zero page missing (call uv_init)");
     a.ld_in = ld_in; a.ldo = ldo; a.ldr = ldr;
-    a.Tout = Tout; a.Hout = Hout; a.Wout = Wout; a.Tin = Tin; a.Hin = Hin; a.Win = Win;
-    a.Cin = Cin; a.Cout = Cout; a.kt = kt; a.kh = kh; a.kw = kw; a.st = st; a.sh = sh; a.sw = sw;
-    a.t_off = t_off; a.ph = ph; a.pw = pw; a.up = up == 1; a.ophase = up >= 2 ? up - 2 : -1; a.interleave = interleave;
-    a.M = Tout * Hout * Wout;
+    a.Tin = Tin; a.t_off = t_off;
     a.out_scale = out_scale;
     a.act_scale = act_scale;
     const ConvPlan plan = plan_conv(a, prec, uv_option(UV_OPT_CONV_HALO), uv_num_cus());
     const bool halo16 = plan.kernel >= HALO_F16_N16, halo = !halo16 && plan.kernel >= HALO_BF16X6;
     (halo16 ? launch_conv_halo16 : halo ? launch_conv_halo : launch_conv_gather)(a, plan, (hipStream_t)stream);
     UV_CHECK_LAUNCH(halo16 ? "uv_conv3d_f16x3 (halo)" : halo ? "uv_conv3d (halo)" : "uv_conv3d");
+    return 0;
+}
+
+// The plan a uv_conv3d_* call of this geometry launches on the current device (256 CUs without one) under the current UV_OPT_CONV_HALO:
+// kernel name (kConvKernelName) and the grid, row tiles x output-channel tiles. prec = the PREC above: 0 uv_conv3d_f32, 1 / 2
+// uv_conv3d_bf16x3 without / with in_split, 3 uv_conv3d_bf16x6, 4 uv_conv3d_f16x3. Host only.
+extern "C" int uv_conv3d_plan(int prec, int Tout, int Hout, int Wout, int Hin, int Win, int Cin, int Cout, int kt, int kh, int kw, int st,
+                              int sh, int sw, int ph, int pw, int up, int interleave, char* kernel, int len, int* tiles_m, int* tiles_n) {
+    UV_CHECK_ARG(kernel && len > 0 && tiles_m && tiles_n, "uv_conv3d_plan: null pointer");
+    UV_CHECK_ARG(prec >= 0 && prec <= 4, "uv_conv3d_plan: prec=%d (0 f32, 1 / 2 bf16x3 without / with in_split, 3 bf16x6, 4 f16x3)", prec);
+    ConvArgs a;
+    if (conv_geometry(a, Tout, Hout, Wout, Hin, Win, Cin, Cout, kt, kh, kw, st, sh, sw, ph, pw, up, interleave) != 0) return -1;
+    const ConvPlan plan = plan_conv(a, prec, uv_option(UV_OPT_CONV_HALO), uv_num_cus());
+    snprintf(kernel, len, "%s", kConvKernelName[plan.kernel]);
+    *tiles_m = plan.tiles_m; *tiles_n = plan.tiles_n;
     return 0;
 }
 

@@ -28,9 +28,35 @@ enum ConvKernel {
     HALO_BF16X6 = 40, HALO_F32_160, HALO_F32_128,                      // conv3d_halo.hip
     HALO_F16_N16, HALO_F16_160, HALO_F16_SQUARE, HALO_F16_128,         // conv3d_halo16.hip
 };
+// their names, as uv_conv3d_plan reports them (gather: tile + PREC; 0 where the sum names no kernel)
+static const char* const kConvKernelName[HALO_F16_128 + 1] = {
+    "G256x16+0", 0, 0, "G256x16+3", "G256x16+4", 0, 0, 0,
+    "G160+0", 0, 0, "G160+3", 0, 0, 0, 0,
+    "G128x128+0", "G128x128+1", "G128x128+2", "G128x128+3", "G128x128+4", 0, 0, 0,
+    0, "G256x128+1", "G256x128+2", 0, "G256x128+4", 0, 0, 0,
+    0, "G256x256+1", "G256x256+2", 0, "G256x256+4", 0, 0, 0,
+    "HALO_BF16X6", "HALO_F32_160", "HALO_F32_128", "HALO_F16_N16", "HALO_F16_160", "HALO_F16_SQUARE", "HALO_F16_128",
+};
 struct ConvPlan {
     int kernel, tiles_m, tiles_n;
 };
+
+// The geometry checks of a uv_conv3d_* call and the geometry part of its ConvArgs (everything plan_conv reads): the ONE fill that
+// conv_common (conv3d_f32.hip) and the plan query uv_conv3d_plan share, so that the query plans what the call launches.
+static inline int conv_geometry(ConvArgs& a, int Tout, int Hout, int Wout, int Hin, int Win, int Cin, int Cout, int kt, int kh, int kw,
+                                int st, int sh, int sw, int ph, int pw, int up, int interleave) {
+    UV_CHECK_ARG(Cin % 32 == 0, "uv_conv3d: Cin=%d must be a multiple of 32 (pad channels with zeros)", Cin);
+    UV_CHECK_ARG(Cout % 4 == 0, "uv_conv3d: Cout=%d must be a multiple of 4", Cout);
+    UV_CHECK_ARG(Tout > 0 && Hout > 0 && Wout > 0 && kt > 0 && kh > 0 && kw > 0, "uv_conv3d: bad geometry");
+    UV_CHECK_ARG(!interleave || Cout % 8 == 0, "uv_conv3d: interleave needs Cout %% 8 == 0 and no residual");
+    UV_CHECK_ARG(up >= 0 && up <= 5, "uv_conv3d: up=%d (0 plain, 1 nearest-2x folded into the gather, 2..5 one output phase of it)", up);
+    UV_CHECK_ARG(up < 2 || (!interleave && sh == 1 && sw == 1 && st == 1), "uv_conv3d: an output-phase launch (up >= 2) takes no residual, interleave or stride");
+    a.Tout = Tout; a.Hout = Hout; a.Wout = Wout; a.Hin = Hin; a.Win = Win;
+    a.Cin = Cin; a.Cout = Cout; a.kt = kt; a.kh = kh; a.kw = kw; a.st = st; a.sh = sh; a.sw = sw;
+    a.ph = ph; a.pw = pw; a.up = up == 1; a.ophase = up >= 2 ? up - 2 : -1; a.interleave = interleave;
+    a.M = Tout * Hout * Wout;
+    return 0;
+}
 
 static inline long conv_patches(const ConvArgs& a, int th, int tw) { return (long)((a.Hout + th - 1) / th) * ((a.Wout + tw - 1) / tw); }
 
