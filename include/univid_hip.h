@@ -75,6 +75,13 @@ int uv_gemm_bf16_nt_ws(const void* A, long lda, const void* W, long ldw, const v
                        int epilogue, void* out, long ldo, const float* gate, const int32_t* gate_tid, long gate_stride,
                        int tile_cfg, void* workspace, long workspace_bytes, void* stream);
 long uv_gemm_splitk_ws_bytes(int M, int N, int K);   /* 0: tile_cfg 0 has no split-K strip for this shape */
+/* The launch plan of a uv_gemm_bf16_nt / _ws / _ssq call (f16 != 0: uv_gemm_f16_nt) of this shape on the current device (256 CUs without
+ * one), before anything is launched: *steps = 1 or 2, and for step i the kernel's name at kernels + i * len (PERSIST, PINGPONG, RING128,
+ * T128, T256, T256x192, SPLITK4, SPLITK2, or DIAG<tile_cfg> for the configurations only tests and tools select) and the rows
+ * m0[i] .. m0[i] + rows[i] - 1 it computes. ws_bytes: the workspace the call would pass (0: none; a non-zero size counts as aligned).
+ * The same shape checks as the call itself. Host only. */
+int uv_gemm_plan(int M, int N, int K, int epilogue, long ldo, int tile_cfg, int f16, long ws_bytes, int* steps, char* kernels, int len,
+                 int* m0, int* rows);
 
 /* uv_gemm_bf16_nt with IEEE fp16 operands, bias and 16-bit outputs (fp32 accumulate): the dtype the reference runs the SigLIP2
  * ranker in (models/BAGEL/eval_understanding.py:172,181,191: fp16 autocast). Same epilogues; tile_cfg must be 0. */

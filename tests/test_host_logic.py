@@ -573,7 +573,8 @@ def test_ffn0_row_padding_never_adds_a_round_of_tiles():
 
 
 def test_splitk_workspace_size_follows_the_gemm_plan():
-    """uv_gemm_splitk_ws_bytes is the GEMM launch plan's one externally visible output: the bytes the split-K strip of a tile_cfg 0
+    """uv_gemm_splitk_ws_bytes is one of the GEMM launch plan's two externally visible outputs (the other: uv_gemm_plan, pinned in
+    test_gemm_launch_plan_is_pinned): the bytes the split-K strip of a tile_cfg 0
     call needs (4 096 + strip tiles x 4 slices x 256 KiB), 0 where the plan has no such strip. Without a device the library plans
     for 256 CUs, which is also what an MI355X reports."""
     lib = _lib.load()
@@ -587,6 +588,143 @@ def test_splitk_workspace_size_follows_the_gemm_plan():
         (22880, 3000, 14336, 0),            # N not in whole tiles
     ]:
         assert lib.uv_gemm_splitk_ws_bytes(M, N, K) == want, (M, N, K)
+
+
+def test_gemm_launch_plan_is_pinned():
+    """uv_gemm_plan is plan_gemm's (csrc/gemm_bf16.hip) externally visible output: which rows of a uv_gemm_bf16_nt / uv_gemm_f16_nt call go to
+    which kernel, in one or two steps. Without a device the library plans for 256 CUs, which is also what an MI355X reports.
+    tests/test_gemm_kernels.py asserts the plan of every case it launches; here every threshold of plan_gemm is pinned from both sides."""
+    lib = _lib.load()
+    BF, GELU, F32, RES, GATE, TR, SSQ = range(7)
+    BIG = 1 << 40
+
+    def plan(M, N, K, epi=BF, ldo=None, cfg=0, f16=False, ws=0):
+        return [(s["kernel"], s["m0"], s["rows"]) for s in _lib.gemm_plan(M, N, K, epi, ldo, cfg, f16, ws)]
+
+    # the name table next to enum GemmKernel
+    src = open(os.path.join(os.path.dirname(_lib.LIB_PATH), "csrc", "gemm_bf16.hip")).read()
+    names = re.findall(r'"([^"]+)"', re.search(r"kGemmKernelName\[[^\]]*\]\s*=\s*\{(.*?)\};", src, flags=re.S).group(1))
+    assert names == ["PERSIST", "PINGPONG", "RING128", "T128", "T256", "T256x192", "SPLITK4", "SPLITK2", "DIAG"]
+
+    # ---- the numbered configurations: the whole problem on one kernel, whatever the shape
+    for cfg, name in ((1, "T128"), (5, "T256"), (6, "T256x192"), (7, "PINGPONG"), (12, "RING128"), (17, "PERSIST"), (19, "SPLITK4"), (20, "SPLITK2"),
+                      (2, "DIAG2"), (3, "DIAG3"), (4, "DIAG4"), (10, "DIAG10"), (11, "DIAG11"), (13, "DIAG13"), (14, "DIAG14")):
+        for M, N, K in ((1, 16, 64), (4156, 4096, 384)):
+            assert plan(M, N, K, cfg=cfg) == [(name, 0, M)], (cfg, M, N, K)
+    # 8 / 9: the whole rounds of 256 x 256 tiles, the rest as a strip. 17 x 16 tiles = one round of 256 and 16 tiles: 4 096 rows + 60
+    assert plan(4156, 4096, 256, cfg=8) == [("PINGPONG", 0, 4096), ("RING128", 4096, 60)]
+    assert plan(4156, 4096, 256, cfg=9) == [("T256", 0, 4096), ("RING128", 4096, 60)]
+    assert plan(4352, 4096, 256, cfg=8) == [("PINGPONG", 0, 4096), ("RING128", 4096, 256)]
+    assert plan(1000, 512, 256, cfg=8) == [("PINGPONG", 0, 1000)]            # under one round: a cut of 0
+    assert plan(4095, 4096, 256, cfg=9) == [("T256", 0, 4095)]               # 255 tiles: a cut of 0
+    assert plan(4096, 4096, 256, cfg=8) == [("PINGPONG", 0, 4096)]           # exactly one round: the cut is M
+    assert plan(4000, 4096, 256, cfg=9) == [("T256", 0, 4000)]               # 16 x 16 tiles, the last row tile ragged: cut 4 096 >= M
+    # 18: the persistent kernel on the whole 256-row tiles; in whole tiles, the whole-rounds cut
+    assert plan(4156, 4096, 384, cfg=18) == [("PERSIST", 0, 4096), ("RING128", 4096, 60)]
+    assert plan(700, 1024, 384, cfg=18) == [("PERSIST", 0, 512), ("RING128", 512, 188)]
+    assert plan(4352, 4096, 384, cfg=18) == [("PERSIST", 0, 4096), ("RING128", 4096, 256)]
+    assert plan(200, 1024, 384, cfg=18) == [("PERSIST", 0, 200)]             # no whole tile, under one round: a cut of 0
+    assert plan(4096, 4096, 384, cfg=18) == [("PERSIST", 0, 4096)]           # whole tiles, exactly one round: the cut is M
+
+    # ---- tile_cfg 0, the large path (persistent / ping-pong kernel): on and off at each of its conditions
+    assert plan(2048, 1024, 384) == [("PINGPONG", 0, 2048)]
+    assert plan(2047, 1024, 384) == [("RING128", 0, 2047)]                   # M < 2 048: 16 x 8 tiles of 128
+    assert plan(2048, 768, 384) == [("RING128", 0, 2048)]                    # N < 1 024
+    assert plan(2048, 1280, 384) == [("PINGPONG", 0, 2048)]
+    assert plan(2048, 1264, 384) == [("T256", 0, 2048)]                      # N % 256
+    assert plan(2048, 1024, 448) == [("T256", 0, 2048)]                      # K % 128
+    assert plan(2048, 1024, 256) == [("T256", 0, 2048)]                      # K < 384
+    # ldo % 8 by epilogue class: 16-bit row-major outputs need it, the f32 ones and the transposed one do not (the transposed one falls
+    # back from the persistent to the one-tile kernel instead)
+    for epi in (BF, GELU):
+        assert plan(8192, 4096, 384, epi, ldo=4096 + 8) == [("PERSIST", 0, 8192)]
+        assert plan(8192, 4096, 384, epi, ldo=4096 + 4) == [("T256", 0, 8192)]
+    for epi in (F32, RES, GATE):
+        assert plan(8192, 4096, 384, epi, ldo=4096 + 4) == [("PERSIST", 0, 8192)]
+    assert plan(8192, 4096, 384, SSQ, ldo=4096 + 8) == [("PERSIST", 0, 8192)]
+    with pytest.raises(_lib.UnividHipError, match="ldo"):
+        plan(8192, 4096, 384, SSQ, ldo=4096 + 4)
+    assert plan(8192, 4096, 384, TR, ldo=8192 + 8) == [("PERSIST", 0, 8192)]
+    assert plan(8192, 4096, 384, TR, ldo=8192 + 4) == [("PINGPONG", 0, 8192)]
+    # two rounds of whole tiles: 511 tiles (73 x 7) the one-tile kernel, 512 (64 x 8) the persistent one
+    assert plan(18688, 1792, 384) == [("PINGPONG", 0, 18688)]
+    assert plan(16384, 2048, 384) == [("PERSIST", 0, 16384)]
+    assert plan(18944, 1792, 384) == [("PINGPONG", 0, 18688), ("RING128", 18688, 256)]       # 518 tiles = 2 rounds + 6: short round, 511 tiles before the cut
+    assert plan(8292, 4096, 384) == [("PERSIST", 0, 8192), ("RING128", 8192, 100)]           # 33 x 16 = 2 rounds + 16
+    assert plan(4156, 4096, 384) == [("PINGPONG", 0, 4096), ("RING128", 4096, 60)]           # 17 x 16 = 1 round + 16
+    assert plan(8392, 4096, 384) == [("PERSIST", 0, 8192), ("RING128", 8192, 200)]           # no short round without a whole round: rows beyond the last whole tile
+    assert plan(2100, 1024, 384) == [("PINGPONG", 0, 2100)]                                  # under one round: never a short round
+    # the short round: a partial round under 45 % of the CUs (115 of 256 tiles) is cut off with its rows, 116 tiles are not
+    assert plan(17152, 4352, 384) == [("PERSIST", 0, 15360), ("RING128", 15360, 1792)]       # 67 x 17 = 4 x 256 + 115
+    assert plan(24320, 3072, 384) == [("PERSIST", 0, 24320)]                                 # 95 x 12 = 4 x 256 + 116
+    assert plan(24300, 3072, 384) == [("PERSIST", 0, 24064), ("RING128", 24064, 236)]        # the same tiles, ragged: only the rows beyond the last whole tile
+
+    # ---- the split-K strip (needs a workspace; K >= 8 192, K % 512 == 0, 4 x strip tiles <= CUs, epilogues 0 / 3 / 4, bf16)
+    need = 4096 + 5 * 12 * 4 * 262144
+    for epi in (BF, RES, GATE):
+        assert plan(22880, 3072, 14336, epi, ws=need) == [("PERSIST", 0, 21760), ("SPLITK4", 21760, 1120)]
+    for epi in (GELU, F32, TR, SSQ):
+        assert plan(22880, 3072, 14336, epi, ldo=22880 if epi == TR else None, ws=need) == [("PERSIST", 0, 21760), ("RING128", 21760, 1120)]
+    assert plan(22880, 3072, 14336, RES, ws=need - 1) == [("PERSIST", 0, 21760), ("RING128", 21760, 1120)]
+    assert plan(22880, 3072, 14336, RES) == [("PERSIST", 0, 21760), ("RING128", 21760, 1120)]
+    assert plan(22880, 3072, 14336, RES, f16=True, ws=need) == [("PERSIST", 0, 21760), ("RING128", 21760, 1120)]
+    assert plan(22880, 3072, 8192, RES, ws=need) == [("PERSIST", 0, 21760), ("SPLITK4", 21760, 1120)]
+    assert plan(22880, 3072, 8064, RES, ws=need) == [("PERSIST", 0, 21760), ("RING128", 21760, 1120)]          # K < 8 192
+    assert plan(22880, 3072, 8192 + 128, RES, ws=need) == [("PERSIST", 0, 21760), ("RING128", 21760, 1120)]    # K % 512
+    assert plan(54560, 3072, 14336, GATE, ws=BIG) == [("PERSIST", 0, 54528), ("SPLITK4", 54528, 32)]           # no short round: the ragged rows
+    assert plan(9216, 4096, 8192, RES, ws=BIG) == [("PERSIST", 0, 8192), ("SPLITK4", 8192, 1024)]              # 4 x 16 = 64 strip tiles: 256 workgroups
+    assert plan(16384, 3328, 8192, RES, ws=BIG) == [("PERSIST", 0, 15104), ("RING128", 15104, 1280)]           # 5 x 13 = 65 strip tiles
+    # the seven sizes test_splitk_workspace_size_follows_the_gemm_plan pins: the workspace of the plan's last step
+    for M, N, K, want in [(22880, 3072, 14336, 62918656), (22880, 3072, 3072, 0), (1024, 3072, 14336, 0), (54560, 3072, 14336, 12587008),
+                          (22784, 3072, 14336, 50335744), (22235, 3072, 14336, 25169920), (22880, 3000, 14336, 0)]:
+        if N % 16:              # a shape the call itself refuses (uv_gemm_splitk_ws_bytes has no error return: 0)
+            with pytest.raises(_lib.UnividHipError, match="multiple of 16"):
+                plan(M, N, K, RES, ws=BIG)
+            last = (None, 0, 0)
+        else:
+            last = plan(M, N, K, RES, ws=BIG)[-1]
+        size = 4096 + -(-last[2] // 256) * -(-N // 256) * 4 * 262144 if last[0] == "SPLITK4" else 0
+        assert size == want == lib.uv_gemm_splitk_ws_bytes(M, N, K), (M, N, K, last)
+
+    # ---- tile_cfg 0, M < 2 048 or N < 1 024
+    # tall and narrow: whole 256-row tiles, M >= 4 096, 512 <= N, K % 128 == 0, K >= 256, ldo % 8 == 0 and at least half a round of tiles
+    assert plan(16384, 512, 256) == [("PINGPONG", 0, 16384)]                 # 2 x 64 x 2 = 256
+    assert plan(16128, 512, 256) == [("RING128", 0, 16128)]                  # 2 x 63 x 2 = 252 (an even number: 255 cannot occur); 126 x 4 = 504 tiles of 128
+    assert plan(11008, 768, 256) == [("PINGPONG", 0, 11008)]                 # 2 x 43 x 3 = 258
+    assert plan(10752, 768, 256) == [("RING128", 0, 10752)]                  # 2 x 42 x 3 = 252; 84 x 6 = 504
+    assert plan(11008, 768, 256, ldo=772) == [("T128", 0, 11008)]            # 86 x 6 = 516 tiles of 128
+    assert plan(11008, 768, 192) == [("T128", 0, 11008)]
+    assert plan(11009, 768, 256) == [("T128", 0, 11009)]
+    assert plan(16384, 528, 256) == [("T128", 0, 16384)]
+    assert plan(16384, 256, 256) == [("RING128", 0, 16384)]                  # N < 512: 128 x 2 tiles of 128
+    # tiles of 128: at most two per CU on the 8-wave ring, more on the 4-wave kernel
+    assert plan(1024, 8192, 64) == [("RING128", 0, 1024)]                    # 8 x 64 = 512
+    assert plan(1152, 7296, 64) == [("T128", 0, 1152)]                       # 9 x 57 = 513
+    assert plan(1, 16, 64) == [("RING128", 0, 1)]
+
+    # ---- tile_cfg 0, everything else: 256 x 192 tiles where they cost less than 256 x 256
+    assert plan(2048, 1152, 64) == [("T256x192", 0, 2048)]
+    assert plan(2048, 1168, 64) == [("T256", 0, 2048)]                       # N % 192
+    assert plan(2048, 1152, 4096) == [("T256x192", 0, 2048)]
+    assert plan(2048, 1152, 4160) == [("T256", 0, 2048)]                     # K > 4 096
+    assert plan(2048, 1152, 64, SSQ) == [("T256", 0, 2048)]                  # 48 columns per wave: no whole 32-column groups
+    assert plan(2048, 1152, 64, f16=True) == [("T256", 0, 2048)]             # not built for fp16
+    assert plan(4096, 3072, 64) == [("T256x192", 0, 4096)]                   # 16 x 16 = 256 tiles of 192 columns: one round x 0.78
+    assert plan(4352, 3072, 64) == [("T256", 0, 4352)]                       # 17 x 16 = 272: two rounds x 0.78 against one of 256 x 256
+    # fp16: the same plan on the five kernels built for it
+    assert plan(8292, 4096, 384, f16=True) == [("PERSIST", 0, 8192), ("RING128", 8192, 100)]
+    assert plan(1152, 7296, 64, f16=True) == [("T128", 0, 1152)]
+    assert plan(2048, 1024, 384, f16=True) == [("PINGPONG", 0, 2048)]
+
+    # ---- the shape checks of the call itself
+    for bad, match in ((dict(M=0), "bad shape"), (dict(K=96), "multiple of 64"), (dict(N=24), "multiple of 16"), (dict(ldo=514), "ldo"),
+                       (dict(epi=7), "epilogue"), (dict(epi=SSQ, N=528, ldo=528), "N %"), (dict(f16=True, cfg=7), "fp16")):
+        a = dict(M=300, N=512, K=256)
+        a.update(bad)
+        with pytest.raises(_lib.UnividHipError, match=match):
+            plan(**a)
+    n = ctypes.c_int()
+    assert lib.uv_gemm_plan(300, 512, 256, 0, 512, 0, 0, 0, ctypes.byref(n), None, 32, None, None) != 0
 
 
 def test_attention_launch_plan_is_pinned():

@@ -29,6 +29,7 @@ SIGNATURES = {
     "uv_gemm_bf16_nt": [_P, _L, _P, _L, _P, _I, _I, _I, _I, _P, _L, _P, _P, _L, _I, _P],
     "uv_gemm_bf16_nt_ws": [_P, _L, _P, _L, _P, _I, _I, _I, _I, _P, _L, _P, _P, _L, _I, _P, _L, _P],
     "uv_gemm_splitk_ws_bytes": [_I, _I, _I],
+    "uv_gemm_plan": [_I, _I, _I, _I, _L, _I, _I, _L, _c.POINTER(_I), _c.c_char_p, _I, _c.POINTER(_I), _c.POINTER(_I)],
     "uv_gemm_f16_nt": [_P, _L, _P, _L, _P, _I, _I, _I, _I, _P, _L, _P, _P, _L, _I, _P],
     "uv_mx_quant_bf16": [_P, _L, _P, _L, _P, _L, _I, _I, _P],
     "uv_gemm_mxfp8_nt": [_P, _L, _P, _L, _P, _L, _P, _L, _P, _I, _I, _I, _I, _P, _L, _P, _P, _L, _P],
@@ -273,6 +274,19 @@ def gemm_splitk_ws_bytes(M, N, K, device=None):
     lib = init(idx)
     with torch.cuda.device(idx):
         return int(lib.uv_gemm_splitk_ws_bytes(int(M), int(N), int(K)))
+
+
+def gemm_plan(M, N, K, epi=0, ldo=None, tile_cfg=0, f16=False, ws_bytes=0):
+    """Launch plan of a gemm_bf16 / gemm_bf16_ssq call of this shape (ldo: the output's leading dimension, default N; ws_bytes: the size
+    of the workspace it would pass) on the current device - 256 CUs without one: [dict(kernel=name, m0=first row, rows=count)], one or
+    two steps (include/univid_hip.h: uv_gemm_plan)."""
+    n, m0, rows = _I(0), (_I * 2)(), (_I * 2)()
+    buf = ctypes.create_string_buffer(64)
+    lib = load()
+    if lib.uv_gemm_plan(int(M), int(N), int(K), int(epi), int(N if ldo is None else ldo), int(tile_cfg), int(f16), int(ws_bytes), ctypes.byref(n),
+                        buf, 32, m0, rows) != 0:
+        raise UnividHipError(lib.uv_last_error().decode())
+    return [dict(kernel=buf.raw[32 * i:32 * i + 32].split(b"\0", 1)[0].decode(), m0=m0[i], rows=rows[i]) for i in range(n.value)]
 
 
 def gemm_bf16(a, w, bias, out, epi, M=None, gate=None, gate_tid=None, tile_cfg=0, ws=None):

@@ -23,6 +23,8 @@ enum GemmKernel {
     GK_SPLITK2,
     GK_DIAG,         // pass tile_cfg on to gemm_bf16_diag.hip
 };
+// their names, as uv_gemm_plan reports them (GK_DIAG: followed by the tile_cfg it passes on, "DIAG14")
+static const char* const kGemmKernelName[] = {"PERSIST", "PINGPONG", "RING128", "T128", "T256", "T256x192", "SPLITK4", "SPLITK2", "DIAG"};
 struct GemmStep { GemmKernel kernel; int m0, rows; };      // rows m0 .. m0 + rows - 1
 struct GemmPlan { int n; GemmStep step[2]; };
 
@@ -204,6 +206,33 @@ extern "C" long uv_gemm_splitk_ws_bytes(int M, int N, int K) {
     const GemmPlan plan = plan_gemm(M, N, K, UV_EPI_RESID_F32, N, 0, false, uv_num_cus(), LONG_MAX, true);
     const GemmStep& strip = plan.step[plan.n - 1];
     return strip.kernel == GK_SPLITK4 ? splitk_ws_bytes(strip.rows, N, 4) : 0;
+}
+
+// The plan a uv_gemm_bf16_nt / _ws / _ssq (f16 != 0: uv_gemm_f16_nt) call of this shape runs on the current device (256 CUs without one):
+// exactly what plan_gemm returns to gemm_entry. ws_bytes: the workspace the caller would pass (0: none); a non-zero size counts as
+// 256-byte aligned. *steps = 1 or 2; step i: its kernel's name (kGemmKernelName) at kernels + i * len, and its rows m0[i] ..
+// m0[i] + rows[i] - 1. The shape checks are gemm_entry's. Host only.
+extern "C" int uv_gemm_plan(int M, int N, int K, int epilogue, long ldo, int tile_cfg, int f16, long ws_bytes, int* steps, char* kernels,
+                            int len, int* m0, int* rows) {
+    UV_CHECK_ARG(steps && kernels && len > 0 && m0 && rows, "uv_gemm_plan: null pointer");
+    UV_CHECK_ARG(M > 0 && N > 0 && K > 0, "uv_gemm_plan: bad shape M=%d N=%d K=%d", M, N, K);
+    UV_CHECK_ARG(K % UV_BK == 0, "uv_gemm_plan: K=%d must be a multiple of %d", K, UV_BK);
+    UV_CHECK_ARG(N % 16 == 0, "uv_gemm_plan: N=%d must be a multiple of 16", N);
+    UV_CHECK_ARG(ldo % 4 == 0, "uv_gemm_plan: ldo must be a multiple of 4 elements");
+    UV_CHECK_ARG(epilogue >= UV_EPI_BF16 && epilogue <= UV_EPI_BF16_SSQ, "uv_gemm_plan: unknown epilogue %d", epilogue);
+    if (epilogue == UV_EPI_BF16_SSQ)
+        UV_CHECK_ARG(N % 32 == 0 && ldo % 8 == 0, "uv_gemm_plan: the sums of squares need N %% 32 == 0, ldo %% 8 == 0 (N=%d ldo=%ld)", N, ldo);
+    UV_CHECK_ARG(!f16 || tile_cfg == 0, "uv_gemm_plan: only tile_cfg 0 (automatic) is built for fp16 operands");
+    UV_CHECK_ARG(ws_bytes >= 0, "uv_gemm_plan: bad workspace");
+    const GemmPlan plan = plan_gemm(M, N, K, epilogue, ldo, tile_cfg, f16 != 0, uv_num_cus(), ws_bytes, true);
+    *steps = plan.n;
+    for (int i = 0; i < plan.n; ++i) {
+        const GemmStep& st = plan.step[i];
+        if (st.kernel == GK_DIAG) snprintf(kernels + (long)i * len, len, "%s%d", kGemmKernelName[st.kernel], tile_cfg);
+        else snprintf(kernels + (long)i * len, len, "%s", kGemmKernelName[st.kernel]);
+        m0[i] = st.m0; rows[i] = st.rows;
+    }
+    return 0;
 }
 
 // UV_EPI_BF16 plus the output's sums of squares per aligned 32-column group (see include/univid_hip.h): the q projection whose RMSNorm is applied

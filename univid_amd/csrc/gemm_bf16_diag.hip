@@ -10,7 +10,9 @@ int uv_gemm_diag_launch(const GemmArgs& a, int epilogue, int tile_cfg, hipStream
         case 10: return launch_cfg<128, 128, 2, 2, 4>(a, epilogue, s);
         case 11: return launch_cfg<128, 128, 2, 4, 4>(a, epilogue, s);
         case 13: return launch_cfg<128, 128, 2, 4, 2>(a, epilogue, s);
-        case 14: return launch_8ph<0>(a, epilogue, s);   // 4-phase schedule + fragment-wise read-modify-write epilogue (A/B reference)
+        case 14:      // 4-phase schedule + fragment-wise read-modify-write epilogue (A/B reference); K tiles in pairs, as tile_cfg 7
+            UV_CHECK_ARG(a.K % 128 == 0 && a.K >= 256, "uv_gemm_bf16_nt: tile_cfg 14 needs K %% 128 == 0 and K >= 256 (K=%d)", a.K);
+            return launch_8ph<0>(a, epilogue, s);
         default:
             uv_set_error("uv_gemm_bf16_nt: unknown tile_cfg %d", tile_cfg);
             return -1;
