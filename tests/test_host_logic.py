@@ -964,3 +964,155 @@ def test_rank_host_policy_is_explicit_and_a_no_op_without_a_gpu():
     par.host_policy("cpu")
     par.host_policy(torch.device("cpu"), blocking_sync=False)
     assert dict(os.environ) == before and not par._blocking_set
+
+
+def test_raw_pointer_calls_are_confined_to_lib():
+    """univid_amd/_lib.py is the only file of the package that marshals pointers, leading dimensions and the stream: nothing else under
+    univid_amd/ calls the C ABI raw, and every entry point of the signature table is reached by a wrapper or helper inside _lib.py."""
+    pkg = os.path.join(ROOT, "univid_amd")
+    for d, _, files in os.walk(pkg):
+        for f in files:
+            path = os.path.join(d, f)
+            if f.endswith(".py") and path != os.path.join(pkg, "_lib.py"):
+                txt = open(path).read()
+                for raw in ("_lib.call(", "_lib.ptr(", "stream_ptr("):
+                    assert raw not in txt, f"{os.path.relpath(path, ROOT)} contains {raw}"
+    src = open(os.path.join(pkg, "_lib.py")).read()
+    code = src[src.index("_RESTYPE ="):].split("\n", 1)[1]         # behind the signature tables
+    for name in set(_lib.SIGNATURES) - {"uv_version"}:      # (read by the loaders' own sanity checks, nothing to wrap)
+        assert re.search(rf'"{name}"|\.{name}\(', code), f"{name}: no wrapper or helper in _lib.py reaches it"
+
+
+def _short(t, need):
+    """t's shape and strides over a storage of need - 1 elements (one row fewer in the shape, so that the view itself is legal)."""
+    shape = (t.shape[0] - 1,) + tuple(t.shape[1:])
+    return torch.empty(need - 1, dtype=t.dtype).as_strided(shape, t.stride())
+
+
+def _checker_cases():
+    """(wrapper, positional arguments, {index of the argument to spoil: its name}, index and extent of the argument to shorten), one per
+    shape class: rows + leading dimension, flat n, the convolution, the epilogue-dependent GEMM output."""
+    f32, bf16 = torch.float32, torch.bfloat16
+    z = torch.zeros
+    w1 = z(4, 32)
+    return {
+        "linear_rows": (_lib.linear_rows, [z(3, 8), z(4, 8), z(4), z(3, 4)], {0: "x", 1: "W", 2: "b", 3: "out"}, (3, 12)),
+        "vae_rms_silu": (_lib.vae_rms_silu, [z(2, 3, 2, 8), z(8), z(2, 3, 2, 8)], {0: "x", 1: "gamma", 2: "out"}, (2, 96)),
+        "add_bf16": (_lib.add_bf16, [z(4, 8, dtype=bf16), z(4, 8, dtype=bf16), z(4, 8, dtype=bf16)], {0: "x", 1: "y"}, (0, 32)),
+        "cfg_convert": (_lib.cfg_convert, [z(2, 4, 4), z(2, 4, 4), z(2, 4, 4), 3.0, 0.5, None, z(2, 4, 4)], {0: "cond", 1: "uncond", 2: "sample"},
+                        (1, 32)),
+        "conv3d": (lambda src, w, b, out, resid: _lib.conv3d("fp32", src, lambda kind: (w, 1.0), b, out, 3, 2, 2, 3, 2, 2, 32, 4, 1, 1, 1, resid=resid),
+                   [z(3, 2, 2, 32), w1, z(4), z(3, 2, 2, 4), None], {0: "src", 1: "weights", 2: "bias", 3: "out"}, (3, 48)),
+        "gemm_bf16": (lambda a, w, bias, out: _lib.gemm_bf16(a, w, bias, out, _lib.EPI_BF16),
+                      [z(4, 64, dtype=bf16), z(16, 64, dtype=bf16), None, z(4, 16, dtype=bf16)], {0: "a", 1: "w", 3: "out"}, (3, 64)),
+    }
+
+
+@pytest.mark.parametrize("case", sorted(_checker_cases()))
+def test_wrappers_check_dtype_layout_and_extent_before_the_library_is_touched(case, monkeypatch):
+    """Every pointer argument of a wrapper is checked from tensor metadata - dtype, then layout, then that the extent the kernel addresses
+    fits in the tensor's STORAGE - and only then the device, so CPU tensors exercise the first three: each failure is a UnividHipError that
+    names wrapper and argument, optional arguments may be None, and nothing is launched or even loaded."""
+    monkeypatch.setattr(_lib, "call", lambda *a, **k: pytest.fail("a rejected call reached the library"))
+    fn, args, names, (si, need) = _checker_cases()[case]
+    E = _lib.UnividHipError
+    with pytest.raises(E, match=rf"{case}\.{names[0]}: tensor must live on the GPU"):      # well-formed: only the device is wrong
+        fn(*args)
+    for i, name in names.items():
+        bad = list(args)
+        bad[i] = args[i].to(torch.float64)
+        with pytest.raises(E, match=rf"{case}\.{name}: expected"):
+            fn(*bad)
+        if args[i].dim() >= 2:
+            bad[i] = args[i].transpose(-1, -2).contiguous().transpose(-1, -2)             # same shape, innermost stride != 1
+            with pytest.raises(E, match=rf"{case}\.{name}: (innermost dimension )?must be contiguous"):
+                fn(*bad)
+    bad = list(args)
+    bad[si] = _short(args[si], need)
+    with pytest.raises(E, match=rf"{case}\.{names[si]}: the kernel addresses {need} elements, the tensor's storage holds {need - 1}"):
+        fn(*bad)
+    bad[si] = torch.empty(need, dtype=args[si].dtype).as_strided(bad[si].shape, bad[si].stride())    # the same view over enough storage
+    with pytest.raises(E, match="must live on the GPU"):
+        fn(*bad)
+
+
+def test_gemm_output_dtype_and_shape_follow_the_epilogue():
+    """gemm_bf16's `out` is checked against what the epilogue writes: 16-bit rows, f32 rows, or the [N, M] transpose."""
+    bf16 = torch.bfloat16
+    a, w = torch.zeros(4, 64, dtype=bf16), torch.zeros(16, 64, dtype=bf16)
+    o16, o32, oT = torch.zeros(4, 16, dtype=bf16), torch.zeros(4, 16), torch.zeros(16, 4, dtype=bf16)
+    E = _lib.UnividHipError
+    for epi, good, wrong in ((_lib.EPI_BF16, o16, o32), (_lib.EPI_GELU_BF16, o16, o32), (_lib.EPI_F32_FROM_BF16, o32, o16),
+                             (_lib.EPI_RESID_F32, o32, o16), (_lib.EPI_GATE_RESID_F32, o32, o16), (_lib.EPI_BF16_T, oT, o32)):
+        with pytest.raises(E, match="gemm_bf16.out: expected"):
+            _lib.gemm_bf16(a, w, None, wrong, epi)
+        with pytest.raises(E, match="gemm_bf16.a: tensor must live on the GPU"):
+            _lib.gemm_bf16(a, w, None, good, epi)
+    with pytest.raises(E, match="gemm_bf16.out: the kernel addresses 64 elements"):      # [N, M]: 15 rows of 4 apart + 4
+        _lib.gemm_bf16(a, w, None, torch.zeros(15, 4, dtype=bf16), _lib.EPI_BF16_T)
+    with pytest.raises(E, match="gemm_bf16.out: the kernel addresses 244 elements"):     # [M, N] where [N, M] is written
+        _lib.gemm_bf16(a, w, None, o16, _lib.EPI_BF16_T)
+    with pytest.raises(E, match="gemm_bf16.gate_tid: expected torch.int32"):
+        _lib.gemm_bf16(a, w, None, o32, _lib.EPI_GATE_RESID_F32, gate=torch.zeros(2, 16), gate_tid=torch.zeros(4, dtype=torch.int64))
+    with pytest.raises(E, match="gemm_bf16.bias: the kernel addresses 16 elements"):
+        _lib.gemm_bf16(a, w, torch.zeros(15, dtype=bf16), o16, _lib.EPI_BF16)
+
+
+def test_wrappers_measure_views_against_their_storage_and_keep_optionals_optional():
+    """A correctly sized view whose rows are wider than its shape - the LoRA slot buf[:, K:], V^T columns vt[:, col0:], the row tail
+    a[j * L:] - passes dtype, layout and extent (measured to the end of the storage, not numel()) and fails only for living on the CPU;
+    the same view one column further along is one element short. None stays accepted for optional arguments."""
+    bf16 = torch.bfloat16
+    E = _lib.UnividHipError
+    buf, A, scale = torch.zeros(4, 64 + 128, dtype=bf16), torch.zeros(3, 64, dtype=bf16), torch.zeros(3)
+    with pytest.raises(E, match="lora_down.buf: tensor must live on the GPU"):
+        _lib.lora_down(buf, 64, A, scale)
+    a, w = buf[:, 128:], torch.zeros(16, 64, dtype=bf16)                # 4 rows of 64 columns, 192 apart: ends with the storage
+    out = torch.zeros(4, 24, dtype=bf16)[:, 8:]
+    for kw in ({}, dict(gate=None, gate_tid=None, ws=None)):
+        with pytest.raises(E, match="gemm_bf16.a: tensor must live on the GPU"):
+            _lib.gemm_bf16(a, w, None, out, _lib.EPI_BF16, **kw)
+    with pytest.raises(E, match="gemm_bf16.a: the kernel addresses 640 elements, the tensor's storage holds 639"):
+        _lib.gemm_bf16(buf[:, 129:], w, None, out, _lib.EPI_BF16, M=4)
+    vt = torch.zeros(8, 64 + 24, dtype=bf16)
+    with pytest.raises(E, match="transpose_16.rows: tensor must live on the GPU"):
+        _lib.transpose_16(torch.zeros(24, 8, dtype=bf16), vt[:, 24:], 24, 8, 64)
+    with pytest.raises(E, match="transpose_16.out: the kernel addresses"):
+        _lib.transpose_16(torch.zeros(24, 8, dtype=bf16), vt[:, 25:], 24, 8, 64)
+    rows = torch.zeros(6, 16, dtype=bf16)
+    with pytest.raises(E, match="patchify.x: tensor must live on the GPU"):
+        _lib.patchify(torch.zeros(4, 1, 2, 4), rows[4:], (1, 2, 2))                       # 2 patches -> the last 2 rows
+    with pytest.raises(E, match="patchify.out: the kernel addresses 32 elements, the tensor's storage holds 16"):
+        _lib.patchify(torch.zeros(4, 1, 2, 4), rows[5:], (1, 2, 2))
+    x = torch.zeros(2, 4, 4)
+    for fn, args in ((_lib.unipc_predictor, (x, x, None, x, 1., 1., 1., 1., 1)), (_lib.dpmpp_update, (x, x, None, x, 1., 1., 1., 1)),
+                     (_lib.unipc_corrector, (x, x, None, x, x, 1., 1., 1., 1., 1., 1., 1)),
+                     (_lib.layernorm_mod, (torch.zeros(4, 256), torch.zeros(4, 256, dtype=bf16), 4, 256, 1e-6))):
+        with pytest.raises(E, match="must live on the GPU"):
+            fn(*args)
+    with pytest.raises(E, match="unipc_predictor.m_prev: a tensor is required"):             # order 2 reads the older x0
+        _lib.unipc_predictor(x, x, None, x, 1., 1., 1., 1., 2)
+
+
+def test_vae_arena_pauses_the_collector_and_restores_it():
+    """WanVAE_._arena runs with Python's cyclic collector off (a dropped VAE's memory pool must not be finalised while allocations are
+    routed to another pool) and puts back whatever state it found, also when the body raises."""
+    import contextlib
+    import gc
+    from univid_amd.wan.vae2_2 import _gc_paused
+    seen = []
+    inner = contextlib.contextmanager(lambda: (yield seen.append("in")))
+    was = gc.isenabled()
+    try:
+        for state in (True, False):
+            gc.enable() if state else gc.disable()
+            with _gc_paused(inner()):
+                assert not gc.isenabled()
+            assert gc.isenabled() == state
+            with pytest.raises(KeyError):
+                with _gc_paused(inner()):
+                    raise KeyError("body")
+            assert gc.isenabled() == state
+        assert seen == ["in"] * 4
+    finally:
+        gc.enable() if was else gc.disable()

@@ -15,10 +15,9 @@ def run(name, x_cl, wp, b, out, T, H, W, C, co):
         key = wp.data_ptr()
         if key not in _SPLIT:
             _SPLIT[key] = torch.empty(wp.numel() * 3, dtype=torch.bfloat16, device=dev)
-            _lib.call("uv_split_weights_bf16x6", _lib.ptr(wp), _lib.ptr(_SPLIT[key]), wp.numel(), _lib.stream_ptr())
+            _lib.split_weights_bf16x6(wp, _SPLIT[key])
         wp = _SPLIT[key]
-    _lib.call(name, _lib.ptr(x_cl), C, T + 2, H, W, _lib.ptr(wp), _lib.ptr(b), _lib.ptr(out), co, T, H, W, C, co, 3, 3, 3, 1, 1, 1, 0, 1, 1,
-              0, 0, None, 0, _lib.stream_ptr())
+    _lib.conv3d("bf16x6" if name.endswith("x6") else "fp32", x_cl, lambda kind: (wp, 1.0), b, out, T + 2, H, W, T, H, W, C, co, 3, 3, 3, ph=1, pw=1)
 
 
 # accuracy: small spatial size, production channel counts, against fp64 on the CPU

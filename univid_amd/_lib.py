@@ -1,8 +1,11 @@
 """ctypes binding of libunivid_hip.so (the C ABI declared in include/univid_hip.h).
 
-PyTorch-ROCm tensors in, raw device pointers out: this module is the only place that turns a tensor into
-`data_ptr()` + sizes + the current HIP stream. There is NO fallback: if the shared library is missing or a
-call is rejected, a RuntimeError is raised.
+PyTorch-ROCm tensors in, raw device pointers out: this module is the only place in the package that turns a tensor into
+`data_ptr()` + sizes + the current HIP stream. Every launching entry point has ONE plain wrapper function below, and every
+pointer argument of every wrapper passes `_check` (dtype, layout, addressed extent against the tensor's storage, device) before
+the library is touched; the rest of the package calls the wrappers only. `call` / `ptr` / `stream_ptr` stay public for tests
+and tools that drive the C ABI with deliberately odd buffers. There is NO fallback: if the shared library is missing or a
+call is rejected, a RuntimeError (UnividHipError) is raised.
 """
 import ctypes
 import os
@@ -244,16 +247,7 @@ def call(name, *args, flops=0):
         prof.setdefault(name, []).append((s, e, flops))
 
 
-# ---- thin typed wrappers (tensor checks live here so the C side only sees valid pointers) -----------------------
-
-def _chk(t, dtype, name):
-    if t.device.type != "cuda":
-        raise UnividHipError(f"{name}: tensor must live on the GPU (got {t.device})")
-    if t.dtype != dtype:
-        raise UnividHipError(f"{name}: expected {dtype}, got {t.dtype}")
-    if t.stride(-1) != 1:
-        raise UnividHipError(f"{name}: innermost dimension must be contiguous")
-
+# ---- host-side helpers (no tensors) -------------------------------------------------------------------------------
 
 def host_blocking_sync(on=True, device=None):
     """uv_host_blocking_sync for `device` (default: the current one): a host thread waiting in synchronize sleeps instead of spinning.
@@ -289,74 +283,123 @@ def gemm_plan(M, N, K, epi=0, ldo=None, tile_cfg=0, f16=False, ws_bytes=0):
     return [dict(kernel=buf.raw[32 * i:32 * i + 32].split(b"\0", 1)[0].decode(), m0=m0[i], rows=rows[i]) for i in range(n.value)]
 
 
+# ---- one checked wrapper per launching entry point ----------------------------------------------------------------
+# Each takes tensors and scalars, derives sizes / leading dimensions / the stream itself, passes EVERY pointer argument through _check and
+# makes the one call(): the C side only sees pointers whose dtype, layout and addressed extent were verified.
+
+F32, BF16, F16, U8, I32 = torch.float32, torch.bfloat16, torch.float16, torch.uint8, torch.int32
+_16 = (BF16, F16)
+
+
+def _check(fn, *args):
+    """The one check of a wrapper's pointer arguments, each given as (tensor, name, dtype, n[, rows[, optional]]): first every tensor's
+    dtype, layout and extent, in that order, then every tensor's device - all before the library is touched and from tensor metadata only
+    (no sync, no allocation: every wrapper runs inside HIP-graph capture). dtype: one dtype or a tuple of them. rows None / absent: a
+    flat kernel reads / writes `n` consecutive elements, so the tensor must be contiguous. Otherwise the kernel addresses `rows` rows of
+    `n` elements, stride(-2) apart: the innermost dimension must be contiguous and the leading ones one run of rows. The extent must fit
+    between the tensor's first element and the end of its STORAGE, not numel(): a view whose rows are wider than its shape (the LoRA
+    slot buf[:, K:], vt[:, col0:], a[j * L:]) is legitimate. optional: None is accepted."""
+    args = [(a + (None, False))[:6] for a in args]
+    for t, name, dtype, n, rows, optional in args:
+        name = f"{fn}.{name}"
+        if t is None:
+            if optional:
+                continue
+            raise UnividHipError(f"{name}: a tensor is required, got None")
+        if t.dtype != dtype and not (isinstance(dtype, tuple) and t.dtype in dtype):
+            raise UnividHipError(f"{name}: expected {dtype}, got {t.dtype}")
+        if rows is None:
+            if not t.is_contiguous():
+                raise UnividHipError(f"{name}: must be contiguous (shape {tuple(t.shape)}, strides {t.stride()})")
+            need = n
+        else:
+            if t.dim() < 2:
+                raise UnividHipError(f"{name}: rows of a matrix are expected, got shape {tuple(t.shape)}")
+            if t.stride(-1) != 1:
+                raise UnividHipError(f"{name}: innermost dimension must be contiguous (shape {tuple(t.shape)}, strides {t.stride()})")
+            if any(t.shape[d] != 1 and t.stride(d) != t.stride(d + 1) * t.shape[d + 1] for d in range(t.dim() - 2)):
+                raise UnividHipError(f"{name}: leading dimensions must form one run of rows (shape {tuple(t.shape)}, strides {t.stride()})")
+            need = (rows - 1) * t.stride(-2) + n if rows > 0 and n > 0 else 0
+        have = t.untyped_storage().nbytes() // t.element_size() - t.storage_offset()
+        if need > have:
+            raise UnividHipError(f"{name}: the kernel addresses {need} elements, the tensor's storage holds {have} from its first element")
+    for t, name, *_ in args:
+        if t is not None and t.device.type != "cuda":
+            raise UnividHipError(f"{fn}.{name}: tensor must live on the GPU (got {t.device})")
+
+
+def _epilogue_args(a, bias, out, epi, M, N, gate, gate_tid):
+    """bias / out / gate / gate_tid of the GEMMs that share uv_gemm_bf16_nt's epilogues: out's dtype and shape follow the epilogue."""
+    half = a.dtype if a.dtype in _16 else BF16
+    if epi not in range(6):
+        raise UnividHipError(f"gemm: unknown epilogue {epi} (include/univid_hip.h: UV_EPI_*)")
+    o = (out, "out", half, M, N) if epi == EPI_BF16_T else (out, "out", half if epi in (EPI_BF16, EPI_GELU_BF16) else F32, N, M)
+    return ((bias, "bias", half, N, None, True), o, (gate, "gate", F32, N, 0 if gate is None else gate.shape[0], True),
+            (gate_tid, "gate_tid", I32, M, None, True))
+
+
+# -- DiT: GEMMs --
 def gemm_bf16(a, w, bias, out, epi, M=None, gate=None, gate_tid=None, tile_cfg=0, ws=None):
     """a [M,K] bf16, w [N,K] bf16, bias bf16 [N] | None; out per epilogue (see include/univid_hip.h).
     ws: uint8 scratch tensor of >= gemm_splitk_ws_bytes(M, N, K) bytes (uv_gemm_bf16_nt_ws), or None."""
-    f16 = a.dtype == torch.float16      # IEEE fp16 operands (SigLIP2 ranker): same kernels, fp16 MFMA / conversions
-    _chk(a, torch.float16 if f16 else torch.bfloat16, "gemm_bf16.a")
-    _chk(w, a.dtype, "gemm_bf16.w")
+    f16 = a.dtype == F16      # IEEE fp16 operands (SigLIP2 ranker): same kernels, fp16 MFMA / conversions
     M = a.shape[0] if M is None else M
     N, K = w.shape
+    _check("gemm_bf16", (a, "a", _16, K, M), (w, "w", a.dtype, K, N), *_epilogue_args(a, bias, out, epi, M, N, gate, gate_tid),
+           (ws, "ws", U8, 0 if ws is None else ws.numel(), None, True))
     if ws is not None and not f16:
-        _chk(ws, torch.uint8, "gemm_bf16.ws")
-        call("uv_gemm_bf16_nt_ws", ptr(a), a.stride(0), ptr(w), w.stride(0), ptr(bias), M, N, K, epi, ptr(out), out.stride(0),
-             ptr(gate), ptr(gate_tid), 0 if gate is None else gate.stride(0), tile_cfg, ptr(ws), ws.numel(), stream_ptr(), flops=2 * M * N * K)
+        call("uv_gemm_bf16_nt_ws", ptr(a), a.stride(-2), ptr(w), w.stride(-2), ptr(bias), M, N, K, epi, ptr(out), out.stride(-2),
+             ptr(gate), ptr(gate_tid), 0 if gate is None else gate.stride(-2), tile_cfg, ptr(ws), ws.numel(), stream_ptr(), flops=2 * M * N * K)
         return out
-    call("uv_gemm_f16_nt" if f16 else "uv_gemm_bf16_nt", ptr(a), a.stride(0), ptr(w), w.stride(0), ptr(bias), M, N, K, epi, ptr(out), out.stride(0),
-         ptr(gate), ptr(gate_tid), 0 if gate is None else gate.stride(0), tile_cfg, stream_ptr(), flops=2 * M * N * K)
+    call("uv_gemm_f16_nt" if f16 else "uv_gemm_bf16_nt", ptr(a), a.stride(-2), ptr(w), w.stride(-2), ptr(bias), M, N, K, epi, ptr(out), out.stride(-2),
+         ptr(gate), ptr(gate_tid), 0 if gate is None else gate.stride(-2), tile_cfg, stream_ptr(), flops=2 * M * N * K)
     return out
 
 
 def mx_quant(x, codes, scales, M=None, K=None):
     """x bf16 [rows, >= K] -> OCP MXFP8: codes uint8 [rows, >= K] (e4m3fn) and scales uint8 [rows, >= K / 32] (one e8m0 byte per 32
     consecutive K elements of a row; include/univid_hip.h states the rule). Quantises the first M rows / K columns (defaults: all of x)."""
-    _chk(x, torch.bfloat16, "mx_quant.x")
-    _chk(codes, torch.uint8, "mx_quant.codes")
-    _chk(scales, torch.uint8, "mx_quant.scales")
     M = x.shape[0] if M is None else M
     K = x.shape[1] if K is None else K
+    _check("mx_quant", (x, "x", BF16, K, M), (codes, "codes", U8, K, M), (scales, "scales", U8, K // 32, M))
     if x.dim() != 2 or codes.dim() != 2 or scales.dim() != 2 or M > min(x.shape[0], codes.shape[0], scales.shape[0]) or \
             K > min(x.shape[1], codes.shape[1]) or K > 32 * scales.shape[1]:
         raise UnividHipError(f"mx_quant: x {tuple(x.shape)} / codes {tuple(codes.shape)} / scales {tuple(scales.shape)} do not fit M = {M}, K = {K}")
-    call("uv_mx_quant_bf16", ptr(x), x.stride(0), ptr(codes), codes.stride(0), ptr(scales), scales.stride(0), M, K, stream_ptr())
+    call("uv_mx_quant_bf16", ptr(x), x.stride(-2), ptr(codes), codes.stride(-2), ptr(scales), scales.stride(-2), M, K, stream_ptr())
     return codes, scales
 
 
 def gemm_mxfp8(a, a_scale, w, w_scale, bias, out, epi, M=None, gate=None, gate_tid=None):
     """gemm_bf16 for MXFP8 operands: a [M,K] / w [N,K] uint8 e4m3fn codes with their e8m0 scales [rows, >= K / 32] uint8 (mx_quant);
     bias bf16 [N] | None; out per epilogue, EPI_BF16 ... EPI_GATE_RESID_F32 (see include/univid_hip.h)."""
-    for t, n in ((a, "a"), (a_scale, "a_scale"), (w, "w"), (w_scale, "w_scale")):
-        _chk(t, torch.uint8, "gemm_mxfp8." + n)
-    if bias is not None:
-        _chk(bias, torch.bfloat16, "gemm_mxfp8.bias")
     M = a.shape[0] if M is None else M
     N, K = w.shape
+    _check("gemm_mxfp8", (a, "a", U8, K, M), (a_scale, "a_scale", U8, K // 32, M), (w, "w", U8, K, N), (w_scale, "w_scale", U8, K // 32, N),
+           *_epilogue_args(a, bias, out, epi, M, N, gate, gate_tid))
     if a.shape[1] < K or M > min(a.shape[0], a_scale.shape[0]) or a_scale.shape[1] * 32 < K or w_scale.shape[1] * 32 < K or w_scale.shape[0] < N:
         raise UnividHipError(f"gemm_mxfp8: a {tuple(a.shape)} / a_scale {tuple(a_scale.shape)} / w {tuple(w.shape)} / w_scale "
                              f"{tuple(w_scale.shape)} do not fit M = {M}")
-    call("uv_gemm_mxfp8_nt", ptr(a), a.stride(0), ptr(a_scale), a_scale.stride(0), ptr(w), w.stride(0), ptr(w_scale), w_scale.stride(0),
-         ptr(bias), M, N, K, epi, ptr(out), out.stride(0), ptr(gate), ptr(gate_tid), 0 if gate is None else gate.stride(0), stream_ptr(),
+    call("uv_gemm_mxfp8_nt", ptr(a), a.stride(-2), ptr(a_scale), a_scale.stride(-2), ptr(w), w.stride(-2), ptr(w_scale), w_scale.stride(-2),
+         ptr(bias), M, N, K, epi, ptr(out), out.stride(-2), ptr(gate), ptr(gate_tid), 0 if gate is None else gate.stride(-2), stream_ptr(),
          flops=2 * M * N * K)
     return out
 
 
 def gemm_bf16_ssq(a, w, bias, out, ssq, M=None, tile_cfg=0):
     """out = bf16(a w^T + bias) and ssq[m][g] = the output row's sum of squares over columns [32 g, 32 g + 32) (f32 [M, N / 32])."""
-    _chk(a, torch.bfloat16, "gemm_bf16_ssq.a")
-    _chk(w, torch.bfloat16, "gemm_bf16_ssq.w")
-    _chk(ssq, torch.float32, "gemm_bf16_ssq.ssq")
     M = a.shape[0] if M is None else M
     N, K = w.shape
-    call("uv_gemm_bf16_nt_ssq", ptr(a), a.stride(0), ptr(w), w.stride(0), ptr(bias), M, N, K, ptr(out), out.stride(0), ptr(ssq), ssq.stride(0),
+    _check("gemm_bf16_ssq", (a, "a", BF16, K, M), (w, "w", BF16, K, N), (bias, "bias", BF16, N, None, True), (out, "out", BF16, N, M),
+           (ssq, "ssq", F32, N // 32, M))
+    call("uv_gemm_bf16_nt_ssq", ptr(a), a.stride(-2), ptr(w), w.stride(-2), ptr(bias), M, N, K, ptr(out), out.stride(-2), ptr(ssq), ssq.stride(-2),
          tile_cfg, stream_ptr(), flops=2 * M * N * K)
     return out
 
 
 def rms_scale_from_ssq(ssq, rs, M, C, eps):
     """rs[m] = 1 / sqrt(sum(ssq[m]) / C + eps): the RMSNorm scale of row m from its per-group sums of squares."""
-    _chk(ssq, torch.float32, "rms_scale_from_ssq.ssq")
-    _chk(rs, torch.float32, "rms_scale_from_ssq.rs")
-    call("uv_rms_scale_from_ssq", ptr(ssq), ssq.stride(0), M, ssq.shape[1], C, float(eps), ptr(rs), stream_ptr())
+    _check("rms_scale_from_ssq", (ssq, "ssq", F32, ssq.shape[1], M), (rs, "rs", F32, M))
+    call("uv_rms_scale_from_ssq", ptr(ssq), ssq.stride(-2), M, ssq.shape[1], C, float(eps), ptr(rs), stream_ptr())
     return rs
 
 
@@ -364,55 +407,55 @@ def lora_down(buf, K, A, scale, M=None, Rpad=None):
     """The un-merged LoRA slot of an activation buffer, in place: buf bf16 [rows, >= K + Rpad] holds x in its first K columns;
     columns [K, K + Rpad) of its first M rows become bf16(scale * (x A^T)), zero beyond A's R rows (include/univid_hip.h).
     A bf16 [R, K] (stacked lora_A weights), scale f32 [R]. Rpad defaults to R rounded up to whole 128-column groups."""
-    _chk(buf, torch.bfloat16, "lora_down.buf")
-    _chk(A, torch.bfloat16, "lora_down.A")
-    _chk(scale, torch.float32, "lora_down.scale")
     R = A.shape[0]
     M = buf.shape[0] if M is None else M
     Rpad = (R + 127) // 128 * 128 if Rpad is None else Rpad
+    _check("lora_down", (buf, "buf", BF16, K + Rpad, M), (A, "A", BF16, K, R), (scale, "scale", F32, R))
     if buf.dim() != 2 or A.dim() != 2 or A.shape[1] != K or scale.numel() != R or buf.shape[1] < K + Rpad or M > buf.shape[0]:
         raise UnividHipError(f"lora_down: buffer {tuple(buf.shape)} / A {tuple(A.shape)} / scale {tuple(scale.shape)} do not fit K = {K}, "
                              f"slot = {Rpad}, M = {M}")
     out = buf[:, K:]
-    call("uv_lora_down_bf16", ptr(buf), buf.stride(0), ptr(A), A.stride(0), ptr(scale), M, K, R, ptr(out), buf.stride(0), Rpad, stream_ptr(),
+    call("uv_lora_down_bf16", ptr(buf), buf.stride(-2), ptr(A), A.stride(-2), ptr(scale), M, K, R, ptr(out), buf.stride(-2), Rpad, stream_ptr(),
          flops=2 * M * R * K)
     return buf
 
 
 def cast_f32_bf16(x, out, R, C):
     """out[:R, :C] = bf16(x[:R, :C]); the contiguous entry point when neither side has a wider leading dimension."""
-    _chk(x, torch.float32, "cast_f32_bf16.x")
-    _chk(out, torch.bfloat16, "cast_f32_bf16.out")
-    if x.stride(0) == C and out.stride(0) == C:
+    _check("cast_f32_bf16", (x, "x", F32, C, R), (out, "out", BF16, C, R))
+    if x.stride(-2) == C and out.stride(-2) == C:
         call("uv_cast_f32_bf16", ptr(x), ptr(out), R * C, stream_ptr())
     else:
-        call("uv_cast_f32_bf16_rows", ptr(x), x.stride(0), ptr(out), out.stride(0), R, C, stream_ptr())
+        call("uv_cast_f32_bf16_rows", ptr(x), x.stride(-2), ptr(out), out.stride(-2), R, C, stream_ptr())
     return out
 
 
 def gemm_f32(a, w, bias, out, resid=None, M=None):
-    _chk(a, torch.float32, "gemm_f32.a")
-    _chk(w, torch.float32, "gemm_f32.w")
-    M = a.shape[0] if M is None else M
+    """out = a w^T + bias (+ resid), all f32: a [..., K] (M rows, default every leading dimension: a channels-last [T, H, W, C] view is
+    its pixel rows), w [N, K], bias [N] | None, out / resid [..., N]."""
+    M = a.numel() // a.shape[-1] if M is None else M
     N, K = w.shape
-    call("uv_gemm_f32_nt", ptr(a), a.stride(0), ptr(w), w.stride(0), ptr(bias), M, N, K, ptr(out), out.stride(0),
-         ptr(resid), 0 if resid is None else resid.stride(0), stream_ptr())
+    _check("gemm_f32", (a, "a", F32, K, M), (w, "w", F32, K, N), (bias, "bias", F32, N, None, True), (out, "out", F32, N, M),
+           (resid, "resid", F32, N, M, True))
+    call("uv_gemm_f32_nt", ptr(a), a.stride(-2), ptr(w), w.stride(-2), ptr(bias), M, N, K, ptr(out), out.stride(-2),
+         ptr(resid), 0 if resid is None else resid.stride(-2), stream_ptr())
     return out
 
 
+# -- DiT: attention and its operator seam --
 def flash_attn(q, k, vt, out, Lq, Lk, H, D, scale, batch=1, q_rs=None, q_weight=None):
     """q [batch*Lq, C], k [batch*Lk, C], vt [C, >= (batch-1)*Lk + roundup(Lk, 64)] (sample b = columns b*Lk..), out [batch*Lq, C].
     q_rs / q_weight: q is the RAW projection and the kernel's Q prologue applies norm_q (per-row scale f32 [batch*Lq], weight f32 [C])."""
-    f16 = q.dtype == torch.float16
-    for t, n in ((q, "q"), (k, "k"), (vt, "vt"), (out, "out")):
-        _chk(t, q.dtype if f16 else torch.bfloat16, "flash_attn." + n)
+    f16 = q.dtype == F16
+    C, half = H * D, F16 if f16 else BF16
+    _check("flash_attn", (q, "q", half, C, batch * Lq), (k, "k", half, C, batch * Lk),
+           (vt, "vt", half, (batch - 1) * Lk + (Lk + 63) // 64 * 64, C), (out, "out", half, C, batch * Lq),
+           (q_rs, "q_rs", F32, batch * Lq, None, True), (q_weight, "q_weight", F32, C, None, q_rs is None))
     if q_rs is not None:
-        _chk(q_rs, torch.float32, "flash_attn.q_rs")
-        _chk(q_weight, torch.float32, "flash_attn.q_weight")
-        call("uv_flash_attn_bf16_qnorm", ptr(q), q.stride(0), ptr(k), k.stride(0), ptr(vt), vt.stride(0), ptr(out), out.stride(0),
+        call("uv_flash_attn_bf16_qnorm", ptr(q), q.stride(-2), ptr(k), k.stride(-2), ptr(vt), vt.stride(-2), ptr(out), out.stride(-2),
              batch, Lq, Lk, H, D, float(scale), ptr(q_rs), ptr(q_weight), stream_ptr(), flops=4 * batch * Lq * Lk * H * D)
         return out
-    call("uv_flash_attn_f16" if f16 else "uv_flash_attn_bf16", ptr(q), q.stride(0), ptr(k), k.stride(0), ptr(vt), vt.stride(0), ptr(out), out.stride(0),
+    call("uv_flash_attn_f16" if f16 else "uv_flash_attn_bf16", ptr(q), q.stride(-2), ptr(k), k.stride(-2), ptr(vt), vt.stride(-2), ptr(out), out.stride(-2),
          batch, Lq, Lk, H, D, float(scale), stream_ptr(), flops=4 * batch * Lq * Lk * H * D)
     return out
 
@@ -453,38 +496,314 @@ def conv_plan(prec, Tout, Hout, Wout, Hin, Win, Cin, Cout, kt, kh, kw, st=1, sh=
     return dict(kernel=buf.value.decode(), tiles_m=tm.value, tiles_n=tn.value)
 
 
+def cast_f32_to16(x, out):
+    """out (bf16 or IEEE fp16) = x (f32), round to nearest even; contiguous tensors of x.numel() elements."""
+    _check("cast_f32_to16", (x, "x", F32, x.numel()), (out, "out", _16, x.numel()))
+    call("uv_cast_f32_to16", ptr(x), ptr(out), x.numel(), int(out.dtype == F16), stream_ptr())
+    return out
+
+
+def cast_16_to_f32(x, out):
+    """out (f32) = x (bf16 or IEEE fp16), exact; contiguous tensors of x.numel() elements."""
+    _check("cast_16_to_f32", (x, "x", _16, x.numel()), (out, "out", F32, x.numel()))
+    call("uv_cast_16_to_f32", ptr(x), ptr(out), x.numel(), int(x.dtype == F16), stream_ptr())
+    return out
+
+
+def transpose_16(rows, out, L, C, Lpad):
+    """out[c][l] = rows[l][c] for l < L, c < C (16-bit elements); columns L .. Lpad - 1 of out are written as zero."""
+    _check("transpose_16", (rows, "rows", _16, C, L), (out, "out", rows.dtype, Lpad, C))
+    call("uv_transpose_16", ptr(rows), rows.stride(-2), ptr(out), out.stride(-2), L, C, Lpad, stream_ptr())
+    return out
+
+
+# -- DiT: fused glue --
 def layernorm_mod(x, out, L, C, eps, mode=0, tab=None, shift_off=0, scale_off=0, tid=None, w=None, b=None,
                   round_ln=False):
-    _chk(x, torch.float32, "layernorm_mod.x")
-    call("uv_layernorm_mod", ptr(x), x.stride(0), ptr(out), out.stride(0), L, C, float(eps), mode, ptr(tab),
-         0 if tab is None else tab.stride(0), shift_off, scale_off, ptr(tid), ptr(w), ptr(b), int(round_ln),
-         2 if out.dtype == torch.float16 else int(out.dtype == torch.bfloat16), stream_ptr())
+    _check("layernorm_mod", (x, "x", F32, C, L), (out, "out", (F32, BF16, F16), C, L),
+           (tab, "tab", F32, max(shift_off, scale_off) + C, 0 if tab is None else tab.shape[0], True), (tid, "tid", I32, L, None, True),
+           (w, "w", F32, C, None, True), (b, "b", F32, C, None, True))
+    call("uv_layernorm_mod", ptr(x), x.stride(-2), ptr(out), out.stride(-2), L, C, float(eps), mode, ptr(tab),
+         0 if tab is None else tab.stride(-2), shift_off, scale_off, ptr(tid), ptr(w), ptr(b), int(round_ln),
+         2 if out.dtype == F16 else int(out.dtype == BF16), stream_ptr())
     return out
 
 
 def rmsnorm_rope(x, out, weight, L, C, D, eps, freqs=None, grid=(0, 0, 0), row0=0):
-    _chk(x, torch.bfloat16, "rmsnorm_rope.x")
-    _chk(out, torch.bfloat16, "rmsnorm_rope.out")
-    call("uv_rmsnorm_rope", ptr(x), x.stride(0), ptr(out), out.stride(0), ptr(weight), L, C, D, float(eps), ptr(freqs),
+    """freqs: the complex128 [1024, D / 2] RoPE table as float64 (re, im) pairs, or None (no rotary embedding)."""
+    _check("rmsnorm_rope", (x, "x", BF16, C, L), (out, "out", BF16, C, L), (weight, "weight", F32, C),
+           (freqs, "freqs", torch.float64, 1024 * D, None, True))
+    call("uv_rmsnorm_rope", ptr(x), x.stride(-2), ptr(out), out.stride(-2), ptr(weight), L, C, D, float(eps), ptr(freqs),
          int(grid[0]), int(grid[1]), int(grid[2]), int(row0), stream_ptr())
-    return out
-
-
-def text_weight_rows(x, out, n_scaled, w):
-    """out[r] = bf16(x[r] * bf16(w)) for the first n_scaled rows of one sample's embedded context [R, C] bf16, the other rows copied:
-    UniVid's dynamic text weight (model_pipeline.py:1787-1797)."""
-    _chk(x, torch.bfloat16, "text_weight_rows.x")
-    _chk(out, torch.bfloat16, "text_weight_rows.out")
-    R, C = x.shape
-    call("uv_text_weight_rows_bf16", ptr(x), x.stride(0), ptr(out), out.stride(0), R, int(n_scaled), C, float(w), stream_ptr())
     return out
 
 
 def rmsnorm_rope_qk(q, k, q_weight, k_weight, L, Ls, C, D, eps, freqs, grid, row0=0):
     """In-place QK RMSNorm + RoPE of q and k (same strides) in one launch; rows = L / Ls stacked samples of Ls tokens."""
-    _chk(q, torch.bfloat16, "rmsnorm_rope_qk.q")
-    _chk(k, torch.bfloat16, "rmsnorm_rope_qk.k")
-    if q.stride(0) != k.stride(0):
+    _check("rmsnorm_rope_qk", (q, "q", BF16, C, L), (k, "k", BF16, C, L), (q_weight, "q_weight", F32, C), (k_weight, "k_weight", F32, C),
+           (freqs, "freqs", torch.float64, 1024 * D, None, True))
+    if q.stride(-2) != k.stride(-2):
         raise UnividHipError("rmsnorm_rope_qk: q and k must have the same row stride")
-    call("uv_rmsnorm_rope_qk", ptr(q), ptr(q), ptr(q_weight), ptr(k), ptr(k), ptr(k_weight), q.stride(0), q.stride(0), L, Ls, C, D,
+    call("uv_rmsnorm_rope_qk", ptr(q), ptr(q), ptr(q_weight), ptr(k), ptr(k), ptr(k_weight), q.stride(-2), q.stride(-2), L, Ls, C, D,
          float(eps), ptr(freqs), int(grid[0]), int(grid[1]), int(grid[2]), int(row0), stream_ptr())
+
+
+def text_weight_rows(x, out, n_scaled, w):
+    """out[r] = bf16(x[r] * bf16(w)) for the first n_scaled rows of one sample's embedded context [R, C] bf16, the other rows copied:
+    UniVid's dynamic text weight (model_pipeline.py:1787-1797)."""
+    R, C = x.shape
+    _check("text_weight_rows", (x, "x", BF16, C, R), (out, "out", BF16, C, R))
+    call("uv_text_weight_rows_bf16", ptr(x), x.stride(-2), ptr(out), out.stride(-2), R, int(n_scaled), C, float(w), stream_ptr())
+    return out
+
+
+def patchify(x, out, patch):
+    """x f32 [Cin, F, H, W] (contiguous) -> out bf16 [L, Kpad]: the im2col rows of the patch embedding, one per (pt, ph, pw) patch."""
+    (Cin, F, H, W), (pt, ph, pw) = x.shape, patch
+    _check("patchify", (x, "x", F32, x.numel()), (out, "out", BF16, out.shape[1], F // pt * (H // ph) * (W // pw)))
+    call("uv_patchify_bf16", ptr(x), ptr(out), out.stride(-2), Cin, F, H, W, pt, ph, pw, out.shape[1], stream_ptr())
+    return out
+
+
+def unpatchify(rows, out, grid, patch):
+    """rows f32 [Fp * Hp * Wp, pt * ph * pw * Cout] (head output) -> out f32 [Cout, Fp * pt, Hp * ph, Wp * pw] (contiguous)."""
+    (Fp, Hp, Wp), (pt, ph, pw), Cout = grid, patch, out.shape[0]
+    _check("unpatchify", (rows, "rows", F32, pt * ph * pw * Cout, Fp * Hp * Wp), (out, "out", F32, Fp * Hp * Wp * pt * ph * pw * Cout))
+    call("uv_unpatchify_f32", ptr(rows), rows.stride(-2), ptr(out), Cout, Fp, Hp, Wp, pt, ph, pw, stream_ptr())
+    return out
+
+
+def sinusoid(t, out):
+    """out f32 [n, dim] (contiguous) = sinusoidal_embedding_1d of the n timesteps t (f32)."""
+    n, dim = t.numel(), out.shape[1]
+    _check("sinusoid", (t, "t", F32, n), (out, "out", F32, n * dim))
+    call("uv_sinusoid_f32", ptr(t), ptr(out), n, dim, stream_ptr())
+    return out
+
+
+def linear_rows(x, W, b, out, act_in=0):
+    """out[r] = act_in(x[r]) W^T + b, f32, for a few rows: x [R, K], W [N, K] contiguous, b [N] | None, out [R, N]. act_in: 0 none, 1 SiLU."""
+    R, (N, K) = x.shape[0], W.shape
+    _check("linear_rows", (x, "x", F32, K, R), (W, "W", F32, N * K), (b, "b", F32, N, None, True), (out, "out", F32, N, R))
+    call("uv_linear_rows_f32", ptr(x), x.stride(-2), ptr(W), ptr(b), ptr(out), out.stride(-2), R, N, K, int(act_in), stream_ptr())
+    return out
+
+
+def add_rows(mod, e0, out):
+    """out[r] = mod + e0[r], f32: mod n elements, e0 / out [R, n], all contiguous."""
+    R, n = out.shape
+    _check("add_rows", (mod, "mod", F32, n), (e0, "e0", F32, R * n), (out, "out", F32, R * n))
+    call("uv_add_rows_f32", ptr(mod), ptr(e0), ptr(out), R, n, stream_ptr())
+    return out
+
+
+def add_bf16_resid(x, y, L, C):
+    """x f32 [L, C] += float(y bf16 [L, C])."""
+    _check("add_bf16_resid", (x, "x", F32, C, L), (y, "y", BF16, C, L))
+    call("uv_add_bf16_resid", ptr(x), x.stride(-2), ptr(y), y.stride(-2), L, C, stream_ptr())
+    return x
+
+
+def l2_normalize_rows(x, out, eps=1e-12):
+    """out[r] = x[r] / max(||x[r]||, eps), f32 [R, C]."""
+    R, C = x.shape
+    _check("l2_normalize_rows", (x, "x", F32, C, R), (out, "out", F32, C, R))
+    call("uv_l2_normalize_rows_f32", ptr(x), x.stride(-2), ptr(out), out.stride(-2), R, C, eps, stream_ptr())
+    return out
+
+
+# -- text encoder and ContextProjector (bf16) --
+def t5_attention(q, k, v, out, H, rel_bias, span):
+    """umT5 attention of one prompt: q, k, v, out bf16 [n, H * 64]; rel_bias f32 [H, 2 * span - 1] (contiguous), span >= n."""
+    n = q.shape[0]
+    _check("t5_attention", (q, "q", BF16, H * 64, n), (k, "k", BF16, H * 64, n), (v, "v", BF16, H * 64, n), (out, "out", BF16, H * 64, n),
+           (rel_bias, "rel_bias", F32, H * (2 * span - 1)))
+    call("uv_t5_attention_bf16", ptr(q), q.stride(-2), ptr(k), k.stride(-2), ptr(v), v.stride(-2), ptr(out), out.stride(-2), n, H,
+         ptr(rel_bias), span, stream_ptr())
+    return out
+
+
+def add_bf16(x, y, out):
+    """out = x + y: contiguous bf16 tensors of out.numel() elements (out may be x or y)."""
+    _check("add_bf16", (x, "x", BF16, out.numel()), (y, "y", BF16, out.numel()), (out, "out", BF16, out.numel()))
+    call("uv_add_bf16", ptr(x), ptr(y), ptr(out), out.numel(), stream_ptr())
+    return out
+
+
+def t5_gated_gelu(gate, fc1, out):
+    """out = fc1 * GELU(gate) with umT5's op-by-op bf16 roundings: contiguous bf16 tensors of out.numel() elements."""
+    _check("t5_gated_gelu", (gate, "gate", BF16, out.numel()), (fc1, "fc1", BF16, out.numel()), (out, "out", BF16, out.numel()))
+    call("uv_t5_gated_gelu_bf16", ptr(gate), ptr(fc1), ptr(out), out.numel(), stream_ptr())
+    return out
+
+
+def gelu_erf(x, out):
+    """out = exact (erf) GELU of x: contiguous bf16 tensors of out.numel() elements (out may be x)."""
+    _check("gelu_erf", (x, "x", BF16, out.numel()), (out, "out", BF16, out.numel()))
+    call("uv_gelu_erf_bf16", ptr(x), ptr(out), out.numel(), stream_ptr())
+    return out
+
+
+def interp_linear_rows(x, out):
+    """F.interpolate(mode='linear', align_corners=False) along the token axis: x bf16 [Lin, C] -> out bf16 [Lout, C]."""
+    (Lin, C), Lout = x.shape, out.shape[0]
+    _check("interp_linear_rows", (x, "x", BF16, C, Lin), (out, "out", BF16, C, Lout))
+    call("uv_interp_linear_rows_bf16", ptr(x), x.stride(-2), ptr(out), out.stride(-2), Lin, Lout, C, stream_ptr())
+    return out
+
+
+# -- sampler: contiguous f32 latents of out.numel() elements; the older x0 (m_prev / m1) only for order 2 --
+def cfg_convert(cond, uncond, sample, guide_scale, sigma, noise_pred, x0):
+    """noise_pred (| None) = uncond + guide_scale * (cond - uncond); x0 = sample - sigma * noise_pred."""
+    n = x0.numel()
+    _check("cfg_convert", (cond, "cond", F32, n), (uncond, "uncond", F32, n), (sample, "sample", F32, n),
+           (noise_pred, "noise_pred", F32, n, None, True), (x0, "x0", F32, n))
+    call("uv_cfg_convert", ptr(cond), ptr(uncond), ptr(sample), float(guide_scale), float(sigma), ptr(noise_pred), ptr(x0), x0.numel(),
+         stream_ptr())
+    return x0
+
+
+def unipc_corrector(x_last, m0, m_prev, model_t, out, r, c1, c2, rho0, rho_last, rk, order):
+    """multistep_uni_c_bh_update with host-computed coefficients."""
+    n = out.numel()
+    _check("unipc_corrector", (x_last, "x_last", F32, n), (m0, "m0", F32, n), (m_prev, "m_prev", F32, n, None, order != 2),
+           (model_t, "model_t", F32, n), (out, "out", F32, n))
+    call("uv_unipc_corrector", ptr(x_last), ptr(m0), ptr(m_prev), ptr(model_t), ptr(out), r, c1, c2, rho0, rho_last, rk, order, n, stream_ptr())
+    return out
+
+
+def unipc_predictor(x, m0, m_prev, out, r, c1, c2, rk, order):
+    """multistep_uni_p_bh_update with host-computed coefficients."""
+    n = out.numel()
+    _check("unipc_predictor", (x, "x", F32, n), (m0, "m0", F32, n), (m_prev, "m_prev", F32, n, None, order != 2), (out, "out", F32, n))
+    call("uv_unipc_predictor", ptr(x), ptr(m0), ptr(m_prev), ptr(out), r, c1, c2, rk, order, out.numel(), stream_ptr())
+    return out
+
+
+def dpmpp_update(x, m0, m1, out, r, c, inv_r0, order):
+    """DPM-Solver++ first-order / midpoint second-order update with host-computed coefficients."""
+    n = out.numel()
+    _check("dpmpp_update", (x, "x", F32, n), (m0, "m0", F32, n), (m1, "m1", F32, n, None, order != 2), (out, "out", F32, n))
+    call("uv_dpmpp_update", ptr(x), ptr(m0), ptr(m1), ptr(out), r, c, inv_r0, order, out.numel(), stream_ptr())
+    return out
+
+
+# -- VAE (f32, channels-last [T, H, W, C]: rows = pixels, leading dimension = stride(-2)) --
+def split_weights_bf16x3(w, out):
+    """w f32 [rows, K] -> out bf16, 2 w.numel() elements: hi | lo planes for uv_conv3d_bf16x3."""
+    _check("split_weights_bf16x3", (w, "w", F32, w.numel()), (out, "out", BF16, 2 * w.numel()))
+    call("uv_split_weights_bf16x3", ptr(w), ptr(out), w.numel(), stream_ptr())
+    return out
+
+
+def split_weights_bf16x6(w, out):
+    """w f32 [rows, K] -> out bf16, 3 w.numel() elements: the exact three-way split for uv_conv3d_bf16x6."""
+    _check("split_weights_bf16x6", (w, "w", F32, w.numel()), (out, "out", BF16, 3 * w.numel()))
+    call("uv_split_weights_bf16x6", ptr(w), ptr(out), w.numel(), stream_ptr())
+    return out
+
+
+def split_weights_f16x3(w, out, scale):
+    """w f32 [rows, K] -> out fp16, 2 w.numel() elements: hi | lo pieces of w * scale (a power of two) for uv_conv3d_f16x3."""
+    _check("split_weights_f16x3", (w, "w", F32, w.numel()), (out, "out", F16, 2 * w.numel()))
+    call("uv_split_weights_f16x3", ptr(w), ptr(out), w.numel(), float(scale), stream_ptr())
+    return out
+
+
+# conv3d's entry points: name, and the weight operand's (element dtype, elements per f32 weight)
+_CONV = {"f32": ("uv_conv3d_f32", F32, 1), "bf16x6": ("uv_conv3d_bf16x6", BF16, 3), "bf16x3": ("uv_conv3d_bf16x3", BF16, 2),
+         "f16x3": ("uv_conv3d_f16x3", F16, 2)}
+
+
+def conv3d(precision, src, weights, bias, out, Tin, Hin, Win, Tout, Hout, Wout, Cin, Cout, kt, kh, kw, st=1, sh=1, sw=1, t_off=0, ph=0, pw=0,
+           up=0, interleave=0, resid=None, in_split=0, act_scale=None, flops=0):
+    """One causal 3D / 2D convolution (include/univid_hip.h: uv_conv3d_*). The VAE's arithmetic `precision` ('fp32' | 'bf16x6' | 'f16x3' |
+    'bf16x3') and `in_split`, the format of src (0 f32 rows, 1 bf16 pieces, 2 fp16 pieces), select the entry: bf16x3 throughout its
+    mode; in f16x3 mode, f16x3 where src holds fp16 pieces and bf16x6 elsewhere. weights(kind) -> (the weight operand of entry `kind`:
+    the 'f32' [Cout, kt kh kw Cin] matrix or its 'bf16x6' | 'bf16x3' | 'f16x3' split, the scale of the f16x3 split).
+    src [Tin, Hin, Win, Cin]; out / resid: the output pixels' rows with Cout channels (interleave: Cout / 2 and twice the frames;
+    up >= 2: the [Tout, 2 Hout, 2 Wout] image of which this call writes one phase)."""
+    kind = "bf16x3" if precision == "bf16x3" else "f16x3" if precision == "f16x3" and in_split == 2 else \
+        "bf16x6" if precision in ("bf16x6", "f16x3") else "f32"
+    entry, wdtype, planes = _CONV[kind]
+    w, w_scale = weights(kind)
+    rows = Tout * Hout * Wout * (2 if interleave else 4 if up >= 2 else 1)
+    cols = Cout // 2 if interleave else Cout
+    _check("conv3d", (src, "src", F32, Cin, Tin * Hin * Win), (w, "weights", wdtype, planes * Cout * kt * kh * kw * Cin),
+           (bias, "bias", F32, Cout), (out, "out", F32, cols, rows), (resid, "resid", F32, cols, rows, True),
+           (act_scale, "act_scale", F32, 1, None, True))
+    tail = (int(in_split == 1),) if kind == "bf16x3" else (w_scale, ptr(act_scale)) if kind == "f16x3" else ()
+    call(entry, ptr(src), src.stride(-2), Tin, Hin, Win, ptr(w), ptr(bias), ptr(out), out.stride(-2), Tout, Hout, Wout, Cin, Cout, kt, kh, kw,
+         st, sh, sw, t_off, ph, pw, up, interleave, ptr(resid), 0 if resid is None else resid.stride(-2), *tail, stream_ptr(), flops=flops)
+    return out
+
+
+def vae_rms_silu(x, gamma, out, silu=True, split=0):
+    """RMS_norm (+ SiLU) per pixel: x f32 [..., C] -> out, the same bytes per pixel as f32 rows (split 0) or bf16 / fp16 pieces (1 / 2)."""
+    P, C = x.numel() // x.shape[-1], x.shape[-1]
+    _check("vae_rms_silu", (x, "x", F32, C, P), (gamma, "gamma", F32, C), (out, "out", F32, C, P))
+    call("uv_vae_rms_silu", ptr(x), x.stride(-2), ptr(gamma), ptr(out), out.stride(-2), P, C, int(silu), int(split), stream_ptr())
+    return out
+
+
+def vae_split_f16(x, out, scale):
+    """fp16 pieces of a raw feature map x f32 [..., C] under a device-found power-of-two scale; scale f32 [2] <- (1 / s, work space)."""
+    P, C = x.numel() // x.shape[-1], x.shape[-1]
+    _check("vae_split_f16", (x, "x", F32, C, P), (out, "out", F32, C, P), (scale, "scale", F32, 2))
+    call("uv_vae_split_f16", ptr(x), x.stride(-2), ptr(out), out.stride(-2), P, C, ptr(scale), stream_ptr())
+    return out
+
+
+def softmax_rows(x, R, n, scale):
+    """In-place softmax of x[:R, :n] * scale, f32."""
+    _check("softmax_rows", (x, "x", F32, n, R))
+    call("uv_softmax_rows_f32", ptr(x), x.stride(-2), R, n, float(scale), stream_ptr())
+    return x
+
+
+def vae_dupup_add(x, out, ft, drop):
+    """out [T * ft - drop, 2 H, 2 W, Cout] += DupUp3D(x [T, H, W, Cin]); contiguous f32."""
+    (T, H, W, Cin), Cout = x.shape, out.shape[-1]
+    _check("vae_dupup_add", (x, "x", F32, x.numel()), (out, "out", F32, (T * ft - drop) * 2 * H * 2 * W * Cout))
+    call("uv_vae_dupup_add", ptr(x), ptr(out), T, H, W, Cin, Cout, ft, drop, stream_ptr())
+    return out
+
+
+def vae_avgdown_add(x, out, ft, fs):
+    """out [ceil(T / ft), H / fs, W / fs, Cout] += AvgDown3D(x [T, H, W, Cin]); contiguous f32."""
+    (T, H, W, Cin), Cout = x.shape, out.shape[-1]
+    _check("vae_avgdown_add", (x, "x", F32, x.numel()), (out, "out", F32, (T + ft - 1) // ft * (H // fs) * (W // fs) * Cout))
+    call("uv_vae_avgdown_add", ptr(x), ptr(out), T, H, W, Cin, Cout, ft, fs, stream_ptr())
+    return out
+
+
+def vae_latent_in(z, mean, inv_std, out):
+    """z f32 [Z, f, h, w] (contiguous) -> out f32 [f, h, w, >= Z] rows of z / inv_std + mean; mean, inv_std f32 [Z]."""
+    Z, P = z.shape[0], z.numel() // z.shape[0]
+    _check("vae_latent_in", (z, "z", F32, Z * P), (mean, "mean", F32, Z), (inv_std, "inv_std", F32, Z), (out, "out", F32, Z, P))
+    call("uv_vae_latent_in", ptr(z), ptr(mean), ptr(inv_std), ptr(out), out.stride(-2), Z, P, stream_ptr())
+    return out
+
+
+def vae_latent_out(mu, mean, inv_std, out, Z):
+    """The first Z channels of the rows mu f32 [f, h, w, >= Z] -> out f32 [Z, f, h, w] (contiguous) of (mu - mean) * inv_std."""
+    P = mu.numel() // mu.shape[-1]
+    _check("vae_latent_out", (mu, "mu", F32, Z, P), (mean, "mean", F32, Z), (inv_std, "inv_std", F32, Z), (out, "out", F32, Z * P))
+    call("uv_vae_latent_out", ptr(mu), mu.stride(-2), ptr(mean), ptr(inv_std), ptr(out), Z, P, stream_ptr())
+    return out
+
+
+def vae_video_in(vid, out, f0, T):
+    """Frames [f0, f0 + T) of vid f32 [3, F, H, W] (contiguous) -> the 12 patchified channels of out f32 [T, H / 2, W / 2, >= 12]."""
+    _, F, H, W = vid.shape
+    _check("vae_video_in", (vid, "vid", F32, 3 * F * H * W), (out, "out", F32, 12, T * (H // 2) * (W // 2)))
+    call("uv_vae_video_in", ptr(vid), ptr(out), out.stride(-2), F, H, W, f0, T, stream_ptr())
+    return out
+
+
+def vae_video_out(y, vid, f0, T):
+    """The 12 channels of y f32 [T, Hp, Wp, >= 12] -> frames [f0, f0 + T) of vid f32 [3, F, 2 Hp, 2 Wp] (contiguous), clamped to [-1, 1]."""
+    F, H, W = vid.shape[-3:]
+    _check("vae_video_out", (y, "y", F32, 12, T * (H // 2) * (W // 2)), (vid, "vid", F32, 3 * F * H * W))
+    call("uv_vae_video_out", ptr(y), y.stride(-2), ptr(vid), F, H // 2, W // 2, f0, T, stream_ptr())
+    return vid

@@ -295,7 +295,7 @@ class ContextProjector(torch.nn.Module):
             _lib.gemm_bf16(x, w1.contiguous(), l1.bias.detach(), h1, EPI_F32_FROM_BF16)        # bf16 Linear output, held as fp32
             y1 = torch.empty(L, w1.shape[0], dtype=bf, device=dev)
             _lib.layernorm_mod(h1, y1, L, w1.shape[0], n1.eps, mode=2, w=n1.weight.detach().float(), b=n1.bias.detach().float())
-            _lib.call("uv_gelu_erf_bf16", _lib.ptr(y1), _lib.ptr(y1), y1.numel(), _lib.stream_ptr())
+            _lib.gelu_erf(y1, y1)
             h2 = torch.empty(L, l2.weight.shape[0], dtype=torch.float32, device=dev)
             _lib.gemm_bf16(y1, l2.weight.detach(), l2.bias.detach(), h2, EPI_F32_FROM_BF16)
             y2 = torch.empty(L, l2.weight.shape[0], dtype=bf, device=dev)
@@ -303,9 +303,7 @@ class ContextProjector(torch.nn.Module):
             T = self.config.wan_text_length
             if L != T:
                 z = torch.empty(T, y2.shape[1], dtype=bf, device=dev)
-                _lib.call("uv_interp_linear_rows_bf16", _lib.ptr(y2), y2.stride(0), _lib.ptr(z), z.stride(0), L, T, y2.shape[1],
-                          _lib.stream_ptr())
-                y2 = z
+                y2 = _lib.interp_linear_rows(y2, z)
             out.append(y2)
         return out
 

@@ -16,10 +16,7 @@ from .siglip2 import Siglip2Model
 
 def _normalize(x: torch.Tensor) -> torch.Tensor:
     x = x.float().contiguous()
-    out = torch.empty_like(x)
-    _lib.call("uv_l2_normalize_rows_f32", _lib.ptr(x), x.stride(0), _lib.ptr(out), out.stride(0), x.shape[0], x.shape[1], 1e-12,
-              _lib.stream_ptr())
-    return out
+    return _lib.l2_normalize_rows(x, torch.empty_like(x))
 
 
 class Siglip2Scorer:
@@ -82,8 +79,7 @@ class Siglip2Scorer:
             v = self.emb_imgs(frames, bs=bs)
         sims = torch.empty(1, v.shape[0], dtype=torch.float32, device=v.device)
         # sims[0, i] = <t, v_i>: the fp32 row product kernel with the image embeddings as the "weight" rows
-        _lib.call("uv_linear_rows_f32", _lib.ptr(t), t.stride(0), _lib.ptr(v), None, _lib.ptr(sims), sims.stride(0), 1, v.shape[0],
-                  v.shape[1], 0, _lib.stream_ptr())
+        _lib.linear_rows(t, v, None, sims)
         sims = sims[0]
         k = min(topk, sims.shape[0])
         vals, idx = torch.topk(sims, k=k)

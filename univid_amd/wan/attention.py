@@ -35,7 +35,7 @@ def _half(x, dtype):
     x = x.contiguous()
     out = torch.empty(x.shape, dtype=dtype, device=x.device)
     if x.numel():
-        _lib.call("uv_cast_f32_to16", _lib.ptr(x), _lib.ptr(out), x.numel(), int(dtype == torch.float16), _lib.stream_ptr())
+        _lib.cast_f32_to16(x, out)
     return out
 
 
@@ -79,7 +79,6 @@ def flash_attention(q, k, v, q_lens=None, k_lens=None, dropout_p=0., softmax_sca
     qh, kh, vh = _half(q, dtype), _half(k, dtype), _half(v, dtype)
     if not (qh.dtype == kh.dtype == vh.dtype):          # attention.py:82-83 casts q and k to v's dtype
         raise NotImplementedError("flash_attention: q, k, v of different half dtypes; pass one dtype")
-    f16 = int(vh.dtype == torch.float16)
     C = n * c
     dev = q.device
     scale = float(softmax_scale) if softmax_scale is not None else c ** -0.5
@@ -88,9 +87,7 @@ def flash_attention(q, k, v, q_lens=None, k_lens=None, dropout_p=0., softmax_sca
 
     def vt_of(rows, L, vt, col0):
         """vt[:, col0 : col0 + roundup(L, 64)] = rows[:L]^T, zero beyond L."""
-        pad = (L + 63) // 64 * 64
-        dst = vt[:, col0:]
-        _lib.call("uv_transpose_16", _lib.ptr(rows), rows.stride(0), _lib.ptr(dst), vt.stride(0), L, C, pad, _lib.stream_ptr())
+        _lib.transpose_16(rows, vt[:, col0:], L, C, (L + 63) // 64 * 64)
 
     if len(set(kls)) == 1 and kls[0] == lk and (b == 1 or lk % 8 == 0):
         # every sample attends all Lk keys: ONE launch over the stacked samples (sample s = V^T columns [s*Lk, (s+1)*Lk))
@@ -110,8 +107,7 @@ def flash_attention(q, k, v, q_lens=None, k_lens=None, dropout_p=0., softmax_sca
         return out
     if out_dtype == torch.float32:                                            # attention.py:130
         wide = torch.empty(b, lq, n, c, dtype=torch.float32, device=dev)
-        _lib.call("uv_cast_16_to_f32", _lib.ptr(out), _lib.ptr(wide), out.numel(), f16, _lib.stream_ptr())
-        return wide
+        return _lib.cast_16_to_f32(out, wide)
     return out.type(out_dtype)   # fp64 / other-half callers: a dtype view change of the finished result, no arithmetic
 
 

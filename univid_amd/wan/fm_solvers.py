@@ -141,8 +141,7 @@ class FlowDPMSolverMultistepScheduler:
         r, c, inv_r0 = self._coeffs(order)
         out = torch.empty_like(sample)
         m1 = self.model_outputs[-2] if order == 2 else None
-        _lib.call("uv_dpmpp_update", _lib.ptr(sample), _lib.ptr(x0), _lib.ptr(m1), _lib.ptr(out), r, c, inv_r0, order,
-                  out.numel(), _lib.stream_ptr())
+        _lib.dpmpp_update(sample, x0, m1, out, r, c, inv_r0, order)
         if self.lower_order_nums < self.config.solver_order:
             self.lower_order_nums += 1
         self._step_index += 1
@@ -163,8 +162,7 @@ class FlowDPMSolverMultistepScheduler:
         x0 = torch.empty_like(sample)
         sigma = self.sigmas[self._step_index].item()
         # gs = 0 makes the CFG stage the identity: x0 = sample - sigma * model_output (:393-394)
-        _lib.call("uv_cfg_convert", _lib.ptr(model_output), _lib.ptr(model_output), _lib.ptr(sample), 0.0, sigma, None,
-                  _lib.ptr(x0), x0.numel(), _lib.stream_ptr())
+        _lib.cfg_convert(model_output, model_output, sample, 0.0, sigma, None, x0)
         prev = self._advance(x0, sample)
         return SchedulerOutput(prev_sample=prev) if return_dict else (prev,)
 
@@ -176,7 +174,6 @@ class FlowDPMSolverMultistepScheduler:
         x0 = torch.empty_like(sample)
         npred = torch.empty_like(sample) if want_noise_pred else None
         sigma = self.sigmas[self._step_index].item()
-        _lib.call("uv_cfg_convert", _lib.ptr(cond), _lib.ptr(uncond), _lib.ptr(sample), float(guide_scale), sigma,
-                  _lib.ptr(npred), _lib.ptr(x0), x0.numel(), _lib.stream_ptr())
+        _lib.cfg_convert(cond, uncond, sample, guide_scale, sigma, npred, x0)
         prev = self._advance(x0, sample)
         return (prev, npred) if want_noise_pred else prev

@@ -132,19 +132,14 @@ class FlowUniPCMultistepScheduler:
             rho0, rho_last = rhos[0].item(), rhos[-1].item()
         out = torch.empty_like(last_sample)
         m_prev = self.model_outputs[-2] if order == 2 else None
-        _lib.call("uv_unipc_corrector", _lib.ptr(last_sample), _lib.ptr(self.model_outputs[-1]), _lib.ptr(m_prev),
-                  _lib.ptr(x0), _lib.ptr(out), c["r"], c["c1"], c["c2"], rho0, rho_last, c["rk"], order, out.numel(),
-                  _lib.stream_ptr())
-        return out
+        return _lib.unipc_corrector(last_sample, self.model_outputs[-1], m_prev, x0, out, c["r"], c["c1"], c["c2"], rho0, rho_last, c["rk"], order)
 
     def _predict(self, sample, order):
         si = self._step_index
         c = self._coeffs(si + 1, si, order, [si - i for i in range(1, order)])
         out = torch.empty_like(sample)
         m_prev = self.model_outputs[-2] if order == 2 else None
-        _lib.call("uv_unipc_predictor", _lib.ptr(sample), _lib.ptr(self.model_outputs[-1]), _lib.ptr(m_prev), _lib.ptr(out),
-                  c["r"], c["c1"], c["c2"], c["rk"], order, out.numel(), _lib.stream_ptr())
-        return out
+        return _lib.unipc_predictor(sample, self.model_outputs[-1], m_prev, out, c["r"], c["c1"], c["c2"], c["rk"], order)
 
     def _advance(self, x0, timestep, sample):
         """Everything in step() after convert_model_output (:691-741)."""
@@ -184,8 +179,7 @@ class FlowUniPCMultistepScheduler:
         x0 = torch.empty_like(sample)
         sigma = self.sigmas[self._step_index].item()
         # gs = 0 makes the CFG stage the identity: x0 = sample - sigma * model_output (:323)
-        _lib.call("uv_cfg_convert", _lib.ptr(model_output), _lib.ptr(model_output), _lib.ptr(sample), 0.0, sigma, None,
-                  _lib.ptr(x0), x0.numel(), _lib.stream_ptr())
+        _lib.cfg_convert(model_output, model_output, sample, 0.0, sigma, None, x0)
         prev = self._advance(x0, timestep, sample)
         return SchedulerOutput(prev_sample=prev) if return_dict else (prev,)
 
@@ -197,7 +191,6 @@ class FlowUniPCMultistepScheduler:
         x0 = torch.empty_like(sample)
         npred = torch.empty_like(sample) if want_noise_pred else None
         sigma = self.sigmas[self._step_index].item()
-        _lib.call("uv_cfg_convert", _lib.ptr(cond), _lib.ptr(uncond), _lib.ptr(sample), float(guide_scale), sigma,
-                  _lib.ptr(npred), _lib.ptr(x0), x0.numel(), _lib.stream_ptr())
+        _lib.cfg_convert(cond, uncond, sample, guide_scale, sigma, npred, x0)
         prev = self._advance(x0, timestep, sample)
         return (prev, npred) if want_noise_pred else prev

@@ -447,8 +447,7 @@ class WanAttentionBlock(nn.Module):
         n_t = e0_rows.shape[0]
         Ls, L = L, batch * L          # Ls = tokens per sample; L = rows of every row-wise kernel below
         tab = torch.empty(n_t, 6 * C, dtype=torch.float32, device=dev)
-        _lib.call("uv_add_rows_f32", _lib.ptr(self.modulation), _lib.ptr(e0_rows), _lib.ptr(tab), n_t, 6 * C,
-                  _lib.stream_ptr())                                                               # model.py:239
+        _lib.add_rows(self.modulation, e0_rows, tab)                                               # model.py:239
         # (rows of the block's bf16 activations: L, or L rounded up to whole 256-row tiles for ffn.0 - see below; the pad rows are never
         # written and their products never read, so they need no zeroing and no scratch that outlives the forward)
         Lf = _ffn0_rows(L, self.ffn_dim, dev)
@@ -477,7 +476,7 @@ class WanAttentionBlock(nn.Module):
             # forward was re-assigned on the instance (UniVid hook): honour it, then add the residual un-fused
             y = self.cross_attn.forward(h[:, :C].view(batch, Ls, C), ctx.view(batch, Lc, C), None)
             y = y.reshape(L, C).contiguous()
-            _lib.call("uv_add_bf16_resid", _lib.ptr(x), x.stride(0), _lib.ptr(y), y.stride(0), L, C, _lib.stream_ptr())
+            _lib.add_bf16_resid(x, y, L, C)
         else:
             self.cross_attn._cross_fused(h, ctx, Ls, Lc, x, batch, kv_key)
         # FFN (model.py:252-255)
@@ -542,7 +541,7 @@ class Head(nn.Module):
         n_t = e_rows.shape[0]
         tab = torch.empty(n_t, 2 * C, dtype=torch.float32, device=dev)
         e2 = e_rows.repeat(1, 2).contiguous()       # e.unsqueeze(2) broadcast over the 2 modulation rows
-        _lib.call("uv_add_rows_f32", _lib.ptr(self.modulation), _lib.ptr(e2), _lib.ptr(tab), n_t, 2 * C, _lib.stream_ptr())
+        _lib.add_rows(self.modulation, e2, tab)
         hh = torch.empty(L, C, dtype=torch.float32, device=dev)
         _lib.layernorm_mod(x, hh, L, C, self.eps, mode=1, tab=tab, shift_off=0, scale_off=C, tid=tid)
         out = torch.empty(L, self.head.out_features, dtype=torch.float32, device=dev)
@@ -767,19 +766,15 @@ class WanModel(nn.Module):
         n_t = tvals.numel()
         dev = tvals.device
         C = self.dim
-        sp = _lib.stream_ptr()
         emb = torch.empty(n_t, self.freq_dim, dtype=torch.float32, device=dev)
-        _lib.call("uv_sinusoid_f32", _lib.ptr(tvals), _lib.ptr(emb), n_t, self.freq_dim, sp)
+        _lib.sinusoid(tvals, emb)
         te0, te2, tp = self.time_embedding[0], self.time_embedding[2], self.time_projection[1]
         h1 = torch.empty(n_t, C, dtype=torch.float32, device=dev)
         e = torch.empty(n_t, C, dtype=torch.float32, device=dev)
         e0 = torch.empty(n_t, 6 * C, dtype=torch.float32, device=dev)
-        _lib.call("uv_linear_rows_f32", _lib.ptr(emb), emb.stride(0), _lib.ptr(te0.weight), _lib.ptr(te0.bias), _lib.ptr(h1),
-                  h1.stride(0), n_t, C, self.freq_dim, 0, sp)
-        _lib.call("uv_linear_rows_f32", _lib.ptr(h1), h1.stride(0), _lib.ptr(te2.weight), _lib.ptr(te2.bias), _lib.ptr(e),
-                  e.stride(0), n_t, C, C, 1, sp)
-        _lib.call("uv_linear_rows_f32", _lib.ptr(e), e.stride(0), _lib.ptr(tp.weight), _lib.ptr(tp.bias), _lib.ptr(e0),
-                  e0.stride(0), n_t, 6 * C, C, 1, sp)
+        _lib.linear_rows(emb, te0.weight, te0.bias, h1)
+        _lib.linear_rows(h1, te2.weight, te2.bias, e, act_in=1)
+        _lib.linear_rows(e, tp.weight, tp.bias, e0, act_in=1)
         return e, e0
 
     def embed_context(self, context: List[torch.Tensor]):
@@ -883,7 +878,6 @@ class WanModel(nn.Module):
         fr = _freqs_device(self.freqs, dev)
         pt, ph, pw = self.patch_size
         C = self.dim
-        sp = _lib.stream_ptr
         # Samples of identical shape run as ONE stacked pass ([B*L, C] rows: every GEMM / norm kernel sees B*L rows, the
         # attention kernel gets a batch dimension). Row-wise kernels and per-(sample, head) attention do not mix samples,
         # so each sample's result is bit-identical to running it alone; the benefit is occupancy (e.g. CFG's cond + uncond
@@ -905,7 +899,7 @@ class WanModel(nn.Module):
             Kp = self._prep["patch"].w.shape[1]
             a = torch.empty(B * L, Kp, dtype=BF16, device=dev)
             for j, i in enumerate(idx):
-                _lib.call("uv_patchify_bf16", _lib.ptr(xs_in[i]), _lib.ptr(a[j * L:]), a.stride(0), cin, F, H, W, pt, ph, pw, Kp, sp())
+                _lib.patchify(xs_in[i], a[j * L:], self.patch_size)
             # timesteps: distinct values -> rows; token -> row map (padding tokens beyond L are never computed)
             if t_rows is not None:
                 if len(groups) != 1:
@@ -962,8 +956,7 @@ class WanModel(nn.Module):
                 yj = yh[j * n:(j + 1) * n]
                 if par is not None:
                     yj = par.gather_rows(yj, L).contiguous()     # gather_forward (sequence_parallel.py:139)
-                _lib.call("uv_unpatchify_f32", _lib.ptr(yj), yj.stride(0), _lib.ptr(out), self.out_dim, Fp, Hp, Wp, pt, ph, pw,
-                          sp())
+                _lib.unpatchify(yj, out, (Fp, Hp, Wp), self.patch_size)
                 outs[i] = out
         return outs
 
@@ -982,8 +975,7 @@ class WanModel(nn.Module):
         for u, v in zip(x, grid_sizes.tolist()):
             u = u[:math.prod(v)].float().contiguous()
             out = torch.empty(self.out_dim, v[0] * pt, v[1] * ph, v[2] * pw, dtype=torch.float32, device=u.device)
-            _lib.call("uv_unpatchify_f32", _lib.ptr(u), u.stride(0), _lib.ptr(out), self.out_dim, v[0], v[1], v[2], pt, ph,
-                      pw, _lib.stream_ptr())
+            _lib.unpatchify(u, out, v, self.patch_size)
             outs.append(out)
         return outs
 

@@ -135,19 +135,18 @@ class T5Encoder(nn.Module):
             _lib.gemm_bf16(y, blk.attn.k.weight.detach(), None, k, EPI_BF16)
             _lib.gemm_bf16(y, blk.attn.v.weight.detach(), None, v, EPI_BF16)
             att = torch.empty(n, self.dim_attn, dtype=BF16, device=dev)
-            _lib.call("uv_t5_attention_bf16", _lib.ptr(q), q.stride(0), _lib.ptr(k), k.stride(0), _lib.ptr(v), v.stride(0), _lib.ptr(att),
-                      att.stride(0), n, H, _lib.ptr(self._tabs[key]), span, _lib.stream_ptr())
+            _lib.t5_attention(q, k, v, att, H, self._tabs[key], span)
             o = torch.empty(n, d, dtype=BF16, device=dev)
             _lib.gemm_bf16(att, blk.attn.o.weight.detach(), None, o, EPI_BF16)
-            _lib.call("uv_add_bf16", _lib.ptr(x), _lib.ptr(o), _lib.ptr(x), x.numel(), _lib.stream_ptr())
+            _lib.add_bf16(x, o, x)
             y = self._rms(x, wf[li][1], blk.norm2.eps)
             g = torch.empty(n, self.dim_ffn, dtype=BF16, device=dev)
             f = torch.empty(n, self.dim_ffn, dtype=BF16, device=dev)
             _lib.gemm_bf16(y, blk.ffn.gate[0].weight.detach(), None, g, EPI_BF16)
             _lib.gemm_bf16(y, blk.ffn.fc1.weight.detach(), None, f, EPI_BF16)
-            _lib.call("uv_t5_gated_gelu_bf16", _lib.ptr(g), _lib.ptr(f), _lib.ptr(f), f.numel(), _lib.stream_ptr())
+            _lib.t5_gated_gelu(g, f, f)
             _lib.gemm_bf16(f, blk.ffn.fc2.weight.detach(), None, o, EPI_BF16)
-            _lib.call("uv_add_bf16", _lib.ptr(x), _lib.ptr(o), _lib.ptr(x), x.numel(), _lib.stream_ptr())
+            _lib.add_bf16(x, o, x)
         return self._rms(x, wf[-1], self.norm.eps)
 
     def forward(self, ids, mask=None):

@@ -14,6 +14,7 @@ per convolution that is prepended to each pass's input.
 Everything is fp32 like the reference (`dtype=torch.float`, vae2_2.py:897, 1028, 1042). No eager fallback.
 """
 import contextlib
+import gc
 import logging
 import math
 from typing import List
@@ -188,14 +189,14 @@ class _ConvOp:
         """bf16 hi/lo planes of the weights for the bf16x3 kernel ([Cout][K/32][32 hi | 32 lo])."""
         if self.w_split is None:
             self.w_split = torch.empty(self.w.numel() * 2, dtype=torch.bfloat16, device=self.w.device)
-            _lib.call("uv_split_weights_bf16x3", _lib.ptr(self.w), _lib.ptr(self.w_split), self.w.numel(), _lib.stream_ptr())
+            _lib.split_weights_bf16x3(self.w, self.w_split)
         return self.w_split
 
     def split6(self):
         """three bf16 planes of the weights for the bf16x6 kernel ([Cout][K/32][32 p0 | 32 p1 | 32 p2], w = p0 + p1 + p2 exactly)."""
         if self.w_split6 is None:
             self.w_split6 = torch.empty(self.w.numel() * 3, dtype=torch.bfloat16, device=self.w.device)
-            _lib.call("uv_split_weights_bf16x6", _lib.ptr(self.w), _lib.ptr(self.w_split6), self.w.numel(), _lib.stream_ptr())
+            _lib.split_weights_bf16x6(self.w, self.w_split6)
         return self.w_split6
 
     def split_f16(self):
@@ -205,9 +206,15 @@ class _ConvOp:
         if self.w_split_f16 is None:
             scale = f16_weight_scale(float(self.w.abs().max()))
             buf = torch.empty(self.w.numel() * 2, dtype=torch.float16, device=self.w.device)
-            _lib.call("uv_split_weights_f16x3", _lib.ptr(self.w), _lib.ptr(buf), self.w.numel(), float(scale), _lib.stream_ptr())
+            _lib.split_weights_f16x3(self.w, buf, scale)
             self.w_split_f16 = (buf, float(scale))
         return self.w_split_f16
+
+    def weights(self, kind):
+        """(weight operand, scale of the f16x3 split) of the convolution entry `kind` (_lib.conv3d)."""
+        if kind == "f16x3":
+            return self.split_f16()
+        return (self.split6() if kind == "bf16x6" else self.split() if kind == "bf16x3" else self.w), 1.0
 
     def phases(self):
         """The four 2x2 phase kernels of a 2x-nearest-upsampling 3x3 convolution (Resample upsample2d / upsample3d, vae2_2.py:86-96, 153-155)
@@ -320,50 +327,29 @@ class _Engine:
         return ring[:need], None
 
     # -- kernels --
-    def _conv(self, op, src, Tin, Hin, Win, Tout, Hout, Wout, st=1, sh=1, sw=1, t_off=0, ph=0, pw=0, up=0, interleave=0,
-              resid=None, out=None, ldo=None, in_split=0, act_scale=None):
-        cout = op.cout // 2 if interleave else op.cout
-        tt = Tout * 2 if interleave else Tout
+    def _conv(self, op, src, Tin, Hin, Win, Tout, Hout, Wout, out=None, **kw):
+        """kw: st, sh, sw, t_off, ph, pw, up, interleave, resid, in_split, act_scale of _lib.conv3d."""
         if out is None:
-            out = torch.empty(tt, Hout, Wout, cout, dtype=torch.float32, device=self.dev)
-            ldo = cout
-        flops = 2 * Tout * Hout * Wout * op.cout * op.kt * op.kh * op.kw * op.cin
-        geom = (ldo, Tout, Hout, Wout, op.cin_pad, op.cout, op.kt, op.kh, op.kw, st, sh, sw, t_off, ph, pw, up, interleave,
-                _lib.ptr(resid), 0 if resid is None else resid.stride(-2))
-        if self.precision == "bf16x3":
-            _lib.call("uv_conv3d_bf16x3", _lib.ptr(src), src.stride(-2), Tin, Hin, Win, _lib.ptr(op.split()), _lib.ptr(op.b),
-                      _lib.ptr(out), *geom, int(in_split == 1), _lib.stream_ptr(), flops=flops)
-        elif self.precision == "f16x3" and in_split == 2:
-            wsp, wscale = op.split_f16()
-            _lib.call("uv_conv3d_f16x3", _lib.ptr(src), src.stride(-2), Tin, Hin, Win, _lib.ptr(wsp), _lib.ptr(op.b), _lib.ptr(out),
-                      *geom, wscale, _lib.ptr(act_scale), _lib.stream_ptr(), flops=flops)
-        else:
-            x6 = self.precision in ("bf16x6", "f16x3")         # f16x3: convolutions whose input is not an RMS_norm output
-            _lib.call("uv_conv3d_bf16x6" if x6 else "uv_conv3d_f32", _lib.ptr(src), src.stride(-2), Tin, Hin, Win,
-                      _lib.ptr(op.split6() if x6 else op.w), _lib.ptr(op.b), _lib.ptr(out), *geom, _lib.stream_ptr(), flops=flops)
-        return out
+            il = 2 if kw.get("interleave") else 1
+            out = torch.empty(Tout * il, Hout, Wout, op.cout // il, dtype=torch.float32, device=self.dev)
+        return _lib.conv3d(self.precision, src, op.weights, op.b, out, Tin, Hin, Win, Tout, Hout, Wout, op.cin_pad, op.cout, op.kt, op.kh, op.kw,
+                           flops=2 * Tout * Hout * Wout * op.cout * op.kt * op.kh * op.kw * op.cin, **kw)
 
     def _rms_silu(self, x, gamma, out, silu=True, split=0):
-        P = x.numel() // x.shape[-1]
-        _lib.call("uv_vae_rms_silu", _lib.ptr(x), x.stride(-2), _lib.ptr(gamma), _lib.ptr(out), out.stride(-2), P, x.shape[-1],
-                  int(silu), int(split), _lib.stream_ptr())
+        _lib.vae_rms_silu(x, gamma, out, silu=silu, split=split)
 
     def _split16(self, x):
         """fp16 pieces of a RAW feature map (not an RMS_norm output) for uv_conv3d_f16x3, under the per-tensor power-of-two scale the
         device finds (uv_vae_split_f16: 1 unless max |x| >= 2^15). Returns (split tensor, [1 / s, work] device scalars)."""
-        P, C = x.numel() // x.shape[-1], x.shape[-1]
         xs = torch.empty_like(x)
         sc = torch.empty(2, dtype=torch.float32, device=self.dev)
-        _lib.call("uv_vae_split_f16", _lib.ptr(x), x.stride(-2), _lib.ptr(xs), xs.stride(-2), P, C, _lib.ptr(sc), _lib.stream_ptr())
+        _lib.vae_split_f16(x, xs, sc)
         return xs, sc
 
     def _pointwise(self, op, x, resid=None):
         """1x1(x1) convolution = fp32 GEMM over pixel rows."""
-        P = x.numel() // x.shape[-1]
         out = torch.empty(*x.shape[:-1], op.cout, dtype=torch.float32, device=self.dev)
-        _lib.call("uv_gemm_f32_nt", _lib.ptr(x), x.stride(-2), _lib.ptr(op.w2d), op.w2d.stride(0), _lib.ptr(op.b), P, op.cout,
-                  op.cin, _lib.ptr(out), op.cout, _lib.ptr(resid), 0 if resid is None else resid.stride(-2), _lib.stream_ptr())
-        return out
+        return _lib.gemm_f32(x, op.w2d, op.b, out, resid=resid)
 
     # -- blocks --
     def causal_conv(self, conv, fill, T, H, W, resid=None, in_split=0):
@@ -402,24 +388,21 @@ class _Engine:
         out = torch.empty_like(x)
         xn = torch.zeros(n4, C, dtype=torch.float32, device=self.dev)            # rows >= n stay zero (GEMM N/K padding)
         qkv_op, proj_op = self.ops[blk.to_qkv], self.ops[blk.proj]
-        sp = _lib.stream_ptr
         for t in range(T):
             xt = x[t].reshape(n, C)
             self._rms_silu(xt, blk.norm.gamma, xn[:n], silu=False)
             qkv = self._pointwise(qkv_op, xn)                                   # [n4, 3C]
             q, k, v = qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:]
             s = torch.empty(n, n4, dtype=torch.float32, device=self.dev)
-            _lib.call("uv_gemm_f32_nt", _lib.ptr(q), q.stride(0), _lib.ptr(k), k.stride(0), None, n, n4, C, _lib.ptr(s), n4, None, 0, sp())
-            _lib.call("uv_softmax_rows_f32", _lib.ptr(s), n4, n, n, 1.0 / math.sqrt(C), sp())
+            _lib.gemm_f32(q, k, None, s, M=n)
+            _lib.softmax_rows(s, n, n, 1.0 / math.sqrt(C))
             if n4 > n:
                 s[:, n:].zero_()
             vt = torch.zeros(C, n4, dtype=torch.float32, device=self.dev)
             vt[:, :n] = v[:n].t()
             o = torch.empty(n, C, dtype=torch.float32, device=self.dev)
-            _lib.call("uv_gemm_f32_nt", _lib.ptr(s), n4, _lib.ptr(vt), n4, None, n, C, n4, _lib.ptr(o), C, None, 0, sp())
-            ot = out[t].reshape(n, C)
-            _lib.call("uv_gemm_f32_nt", _lib.ptr(o), C, _lib.ptr(proj_op.w2d), C, _lib.ptr(proj_op.b), n, C, C, _lib.ptr(ot), C,
-                      _lib.ptr(xt), C, sp())
+            _lib.gemm_f32(s, vt, None, o)
+            _lib.gemm_f32(o, proj_op.w2d, proj_op.b, out[t].reshape(n, C), resid=xt)
         return out
 
     def upsample(self, rs, x, first_chunk):
@@ -451,7 +434,7 @@ class _Engine:
             fmt = 2
         for k, ph in enumerate(op.phases()):
             a, b = k >> 1, k & 1
-            self._conv(ph, x, T, H, W, T, H, W, ph=1 - a, pw=1 - b, up=2 + k, out=out, ldo=op.cout, in_split=fmt, act_scale=sc)
+            self._conv(ph, x, T, H, W, T, H, W, ph=1 - a, pw=1 - b, up=2 + k, out=out, in_split=fmt, act_scale=sc)
         return out
 
     def downsample(self, rs, x, first_chunk):
@@ -478,20 +461,18 @@ class _Engine:
     def encoder_chunk(self, vid, f0, T, first_chunk):
         """Frames [f0, f0 + T) of the clip through the encoder (T = 1 for the first chunk, a multiple of 4 afterwards)."""
         enc = self.m.encoder
-        F, Hv, Wv = vid.shape[1:]
+        Hv, Wv = vid.shape[2:]
         H, W = Hv // 2, Wv // 2
 
         def fill(dst):
-            _lib.call("uv_vae_video_in", _lib.ptr(vid), _lib.ptr(dst), dst.stride(-2), F, Hv, Wv, f0, T, _lib.stream_ptr())
+            _lib.vae_video_in(vid, dst, f0, T)
 
         x = self.causal_conv(enc.conv1, fill, T, H, W)
         for stage in enc.downsamples:
             x_copy = x
             for mod in stage.downsamples:
                 x = self.resblock(mod, x) if isinstance(mod, ResidualBlock) else self.downsample(mod, x, first_chunk)
-            Tc, Hc, Wc, Cc = x_copy.shape
-            _lib.call("uv_vae_avgdown_add", _lib.ptr(x_copy), _lib.ptr(x), Tc, Hc, Wc, Cc, stage.out_dim, stage.factor_t,
-                      stage.factor_s, _lib.stream_ptr())
+            _lib.vae_avgdown_add(x_copy, x, stage.factor_t, stage.factor_s)
         x = self.resblock(enc.middle[0], x)
         x = self.attention(enc.middle[1], x)
         x = self.resblock(enc.middle[2], x)
@@ -512,14 +493,24 @@ class _Engine:
             for mod in stage.upsamples:
                 xm = self.resblock(mod, xm) if isinstance(mod, ResidualBlock) else self.upsample(mod, xm, first_chunk)
             if stage.up_flag:
-                T, Hh, Ww, C = x.shape
-                ft = stage.factor_t
-                _lib.call("uv_vae_dupup_add", _lib.ptr(x), _lib.ptr(xm), T, Hh, Ww, C, stage.out_dim, ft,
-                          (ft - 1) if first_chunk else 0, _lib.stream_ptr())
+                _lib.vae_dupup_add(x, xm, stage.factor_t, (stage.factor_t - 1) if first_chunk else 0)
             x = xm
         T, Hh, Ww, _ = x.shape
         sp = self.split_fmt(dec.head[0], x.shape[-1], 32)
         return self.causal_conv(dec.head[2], lambda dst: self._rms_silu(x, dec.head[0].gamma, dst, split=sp), T, Hh, Ww, in_split=sp)
+
+
+@contextlib.contextmanager
+def _gc_paused(ctx):
+    """`ctx` with Python's cyclic garbage collector off inside it (WanVAE_._arena)."""
+    was = gc.isenabled()
+    gc.disable()
+    try:
+        with ctx:
+            yield
+    finally:
+        if was:
+            gc.enable()
 
 
 class WanVAE_(nn.Module):
@@ -556,12 +547,16 @@ class WanVAE_(nn.Module):
         fills the pool with device allocations; every later call finds its blocks there: no hipMalloc / hipFree inside a decode, whatever
         the rest of the process (the DiT's loop, an empty_cache() elsewhere) did to the shared pool in between - a decode's wall time is its
         kernel time (round-4 verdict: 1.73 -> 3.65 s by allocator state). Memory plumbing only; dropped by invalidate() and by the
-        out-of-memory retry."""
+        out-of-memory retry.
+        The cyclic garbage collector is paused for the length of the call: a dropped VAE is cyclic garbage (engine <-> model) that still owns
+        its pool, and the caching allocator refuses - by an assertion in a destructor, i.e. by aborting the process - to release a pool's
+        blocks while allocations are routed to another pool. Whether a collection falls inside a call depends on nothing but the number
+        of host allocations made so far."""
         if not self.use_arena or not hasattr(torch.cuda, "MemPool"):
             return contextlib.nullcontext()
         if self._pool is None:
             self._pool = torch.cuda.MemPool()
-        return torch.cuda.use_mem_pool(self._pool, device=next(self.parameters()).device)
+        return _gc_paused(torch.cuda.use_mem_pool(self._pool, device=next(self.parameters()).device))
 
     def prepare(self, precision=None):
         """precision: 'fp32' = exact f32 MFMA (the reference's dtype) | 'bf16x6' = the same f32 operands, products on the
@@ -625,11 +620,10 @@ class WanVAE_(nn.Module):
             out = torch.cat(outs, 0)                                              # [f, h, w, 2z]
             y = eng._pointwise(eng.ops[self.conv1], out)                          # 1x1x1, then chunk(2) -> mu
             f, h, w, _ = y.shape
-            if (f, h, w) != tuple(mu.shape[2:]):      # uv_vae_latent_out writes f*h*w*z_dim floats through a raw pointer
+            if (f, h, w) != tuple(mu.shape[2:]):
                 raise ValueError(f"encoder produced {(f, h, w)} latent positions for a result sized {tuple(mu.shape[2:])} "
                                  f"(input {tuple(vid.shape)}: H and W must be multiples of 16)")
-            _lib.call("uv_vae_latent_out", _lib.ptr(y), y.stride(-2), _lib.ptr(scale[0]), _lib.ptr(scale[1]), _lib.ptr(mu), self.z_dim,
-                      f * h * w, _lib.stream_ptr())
+            _lib.vae_latent_out(y, scale[0], scale[1], mu, self.z_dim)
             eng.reset()
             del outs, out, y
         return mu
@@ -647,14 +641,13 @@ class WanVAE_(nn.Module):
             eng = self._eng()
             eng.reset()
             rows = torch.empty(f, h, w, Z, dtype=torch.float32, device=zz.device)
-            _lib.call("uv_vae_latent_in", _lib.ptr(zz), _lib.ptr(scale[0]), _lib.ptr(scale[1]), _lib.ptr(rows), Z, Z, f * h * w,
-                      _lib.stream_ptr())
+            _lib.vae_latent_in(zz, scale[0], scale[1], rows)
             x = eng._pointwise(eng.ops[self.conv2], rows)                         # conv2 (1x1x1) on all frames
             f0 = 0
             for i0, i1 in [(0, 1)] + [(i, min(i + G, f)) for i in range(1, f, G)]:
                 y = eng.decoder_chunk(x[i0:i1], first_chunk=(i0 == 0))           # [T, 8h, 8w, 12]
                 T = y.shape[0]
-                _lib.call("uv_vae_video_out", _lib.ptr(y), y.stride(-2), _lib.ptr(vid), F, 8 * h, 8 * w, f0, T, _lib.stream_ptr())
+                _lib.vae_video_out(y, vid, f0, T)
                 f0 += T
             assert f0 == F
             eng.reset()
