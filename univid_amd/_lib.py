@@ -448,6 +448,8 @@ def flash_attn(q, k, vt, out, Lq, Lk, H, D, scale, batch=1, q_rs=None, q_weight=
     q_rs / q_weight: q is the RAW projection and the kernel's Q prologue applies norm_q (per-row scale f32 [batch*Lq], weight f32 [C])."""
     f16 = q.dtype == F16
     C, half = H * D, F16 if f16 else BF16
+    if f16 and q_rs is not None:      # uv_flash_attn_bf16_qnorm would read the fp16 bits as bf16
+        raise UnividHipError("flash_attn: the q-norm prologue (q_rs / q_weight) is built for bf16 only, q is fp16")
     _check("flash_attn", (q, "q", half, C, batch * Lq), (k, "k", half, C, batch * Lk),
            (vt, "vt", half, (batch - 1) * Lk + (Lk + 63) // 64 * 64, C), (out, "out", half, C, batch * Lq),
            (q_rs, "q_rs", F32, batch * Lq, None, True), (q_weight, "q_weight", F32, C, None, q_rs is None))
@@ -460,25 +462,29 @@ def flash_attn(q, k, vt, out, Lq, Lk, H, D, scale, batch=1, q_rs=None, q_weight=
     return out
 
 
-def attn_kernel_name(Lq, Lk, D, batch=1, H=None, f16=False):
-    """Name of the kernel `flash_attn` dispatches for this geometry (dense [tokens, H*D] rows as the DiT uses them)."""
+def attn_kernel_name(Lq, Lk, D, batch=1, H=None, f16=False, ldk=None, ldvt=None):
+    """Name of the kernel `flash_attn` dispatches for this geometry. ldk / ldvt: the leading dimensions of k and V^T, default the dense
+    ones ([tokens, H*D] rows as the DiT uses them, V^T just wide enough for the batch)."""
     H = H or 1
     buf = ctypes.create_string_buffer(96)
-    ldvt = (batch - 1) * Lk + (Lk + 63) // 64 * 64
-    rc = load().uv_flash_attn_kernel_name(Lk, D, H * D, ldvt, int(f16), buf, 96)
+    ldk = H * D if ldk is None else ldk
+    ldvt = (batch - 1) * Lk + (Lk + 63) // 64 * 64 if ldvt is None else ldvt
+    rc = load().uv_flash_attn_kernel_name(Lk, D, int(ldk), int(ldvt), int(f16), buf, 96)
     if rc != 0:
         raise UnividHipError(load().uv_last_error().decode())
     return buf.value.decode()
 
 
-def attn_plan(Lq, Lk, D, batch=1, H=1, f16=False):
-    """Launch plan of `flash_attn` for this geometry (dense [tokens, H*D] rows) on the current device - 256 CUs without one - under the
-    current OPT_ATTN_CUT: dict(kernel=name, q_blocks=blocks per (sample, head), n12=how many of them own 12 units, grid=workgroups)."""
+def attn_plan(Lq, Lk, D, batch=1, H=1, f16=False, ldk=None, ldvt=None):
+    """Launch plan of `flash_attn` for this geometry on the current device - 256 CUs without one - under the current OPT_ATTN_CUT:
+    dict(kernel=name, q_blocks=blocks per (sample, head), n12=how many of them own 12 units, grid=workgroups). ldk / ldvt: the leading
+    dimensions of k and V^T, default the dense ones ([tokens, H*D] rows, V^T just wide enough for the batch)."""
     buf = ctypes.create_string_buffer(96)
     qb, n12, grid = _I(0), _I(0), _I(0)
-    ldvt = (batch - 1) * Lk + (Lk + 63) // 64 * 64
+    ldk = H * D if ldk is None else ldk
+    ldvt = (batch - 1) * Lk + (Lk + 63) // 64 * 64 if ldvt is None else ldvt
     lib = load()
-    if lib.uv_flash_attn_plan(batch, Lq, Lk, H, D, H * D, ldvt, int(f16), buf, 96, ctypes.byref(qb), ctypes.byref(n12), ctypes.byref(grid)) != 0:
+    if lib.uv_flash_attn_plan(batch, Lq, Lk, H, D, int(ldk), int(ldvt), int(f16), buf, 96, ctypes.byref(qb), ctypes.byref(n12), ctypes.byref(grid)) != 0:
         raise UnividHipError(lib.uv_last_error().decode())
     return dict(kernel=buf.value.decode(), q_blocks=qb.value, n12=n12.value, grid=grid.value)
 
