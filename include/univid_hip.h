@@ -112,6 +112,16 @@ int uv_rms_scale_from_ssq(const float* ssq, long ld_ssq, int M, int groups, int 
  * fixed-order chain over k (no split-K, no atomics): a row's bits do not depend on the other rows of the launch. */
 int uv_lora_down_bf16(const void* x, long ldx, const void* A, long lda, const float* scale, int M, int K, int R, void* out, long ldo,
                       int Rpad, void* stream);
+/* The same down-projection with one scale ROW PER SEGMENT of seg_rows consecutive rows of x (per-sample adapter weights inside one
+ * stacked forward: a segment is a stacked sample): row m belongs to segment s = m / seg_rows, scale f32 [nseg, ld_scale], and
+ * out[m][j] = +0 if scale[s][j] == 0 (whatever the accumulator holds - an adapter that is off for a sample contributes exact +0, never
+ * -0 or NaN), else bf16(scale[s][j] * sum_k x[m][k] A[j][k]) in uv_lora_down_bf16's accumulation order: with one segment, or segment by
+ * segment, the bits are that entry point's. Columns [R, Rpad) are +0. A segment boundary may fall anywhere (the scale is looked up per
+ * output row); the last segment may be partial. A 32-row workgroup skips a 128-rank pass - no read of x, no MFMA, zero stores only -
+ * when the pass's scale entries are zero for every segment its rows touch. Every check of uv_lora_down_bf16 applies; seg_rows >= 1,
+ * nseg >= 1, nseg * seg_rows >= M, ld_scale >= R, scale 4-byte aligned. */
+int uv_lora_down_seg_bf16(const void* x, long ldx, const void* A, long lda, const float* scale, long ld_scale, int seg_rows, int nseg,
+                          int M, int K, int R, void* out, long ldo, int Rpad, void* stream);
 
 /* ---- DiT: MXFP8 GEMMs (opt-in fast mode of ffn.0 / ffn.2; WanModel.set_ffn_precision("mxfp8")) ---------------------------------
  * Format (OCP Microscaling, MXFP8): elements are e4m3fn (the OCP encoding: bias 7, largest finite 448, no infinity, NaN = 0x7F / 0xFF;

@@ -2,6 +2,8 @@
 
   kernel   uv_lora_down_bf16 alone at the headline rows (M = 2 x 11 440) against the time to stream x once at the HBM rates of
            MI355X_MICROARCH.md (6.29 TB/s measured float4 copy; 8 TB/s spec)
+  seg      per-sample adapter weights: uv_lora_down_bf16 against uv_lora_down_seg_bf16 with two segments (the CFG pair), all scales non-zero
+           and with the second segment off, at M = 2 x 11 440, K = 3072, R = 64, alternating rounds (`profiles/lora_per_sample_bench.md`)
   block    one TI2V-5B block at M = 2 x 11 440 with a rank-16 adapter on all ten projections: un-merged against the same block with the
            adapter merged, alternating, device events around each run
   swap     a multi-layer TI2V-width model: time to put an adapter in place (load + operand preparation) and the device memory it
@@ -99,6 +101,29 @@ def bench_kernel(out):
         res.append(row)
         del buf
     out["kernel"] = res
+
+
+def bench_seg(out):
+    g = torch.Generator(device=DEV).manual_seed(0)
+    M, K, R = B * L1, DIM, 64
+    buf = torch.empty(M, K + 128, dtype=BF16, device=DEV)
+    buf[:, :K] = torch.randn(M, K, device=DEV, generator=g).to(BF16)
+    A = (torch.randn(R, K, device=DEV, generator=g) / K ** 0.5).to(BF16)
+    s1 = torch.full((R,), 2.0, device=DEV)
+    s_on = torch.full((B, R), 2.0, device=DEV)
+    s_half = s_on.clone()
+    s_half[1] = 0.0
+    variants = {"vector": lambda: _lib.lora_down(buf, K, A, s1), "seg_all_on": lambda: _lib.lora_down_seg(buf, K, A, s_on, L1),
+                "seg_second_off": lambda: _lib.lora_down_seg(buf, K, A, s_half, L1)}
+    ts = {k: [] for k in variants}
+    for r in range(10):                     # alternating rounds; the first is warm-up
+        for k, fn in variants.items():
+            med, _, _ = events(fn, iters=20, rounds=1)
+            if r:
+                ts[k].append(med * 1e3)
+    out["seg"] = {k: dict(M=M, K=K, R=R, us=statistics.median(v), us_min=min(v), us_max=max(v)) for k, v in ts.items()}
+    for k, v in out["seg"].items():
+        print(f"lora_down {k} M={M} K={K} R={R}: {v['us']:.2f} us [{v['us_min']:.2f} .. {v['us_max']:.2f}]", flush=True)
 
 
 def bench_block(out, tmp):
@@ -205,13 +230,15 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join("profile_out", "lora_bench.json"))
     ap.add_argument("--layers", type=int, default=4)
-    ap.add_argument("--only", choices=["kernel", "block", "swap"], default=None)
+    ap.add_argument("--only", choices=["kernel", "seg", "block", "swap"], default=None)
     a = ap.parse_args()
     _lib.init()
     out = {}
     with tempfile.TemporaryDirectory() as tmp:
         if a.only in (None, "kernel"):
             bench_kernel(out)
+        if a.only in (None, "seg"):
+            bench_seg(out)
         if a.only in (None, "block"):
             bench_block(out, tmp)
         if a.only in (None, "swap"):

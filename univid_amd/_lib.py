@@ -40,6 +40,7 @@ SIGNATURES = {
     "uv_gemm_bf16_nt_ssq": [_P, _L, _P, _L, _P, _I, _I, _I, _P, _L, _P, _L, _I, _P],
     "uv_rms_scale_from_ssq": [_P, _L, _I, _I, _I, _F, _P, _P],
     "uv_lora_down_bf16": [_P, _L, _P, _L, _P, _I, _I, _I, _P, _L, _I, _P],
+    "uv_lora_down_seg_bf16": [_P, _L, _P, _L, _P, _L, _I, _I, _I, _I, _I, _P, _L, _I, _P],
     "uv_cast_f32_bf16_rows": [_P, _L, _P, _L, _I, _I, _P],
     "uv_flash_attn_bf16_qnorm": [_P, _L, _P, _L, _P, _L, _P, _L, _I, _I, _I, _I, _I, _F, _P, _P, _P],
     "uv_flash_attn_bf16": [_P, _L, _P, _L, _P, _L, _P, _L, _I, _I, _I, _I, _I, _F, _P],
@@ -417,6 +418,27 @@ def lora_down(buf, K, A, scale, M=None, Rpad=None):
     out = buf[:, K:]
     call("uv_lora_down_bf16", ptr(buf), buf.stride(-2), ptr(A), A.stride(-2), ptr(scale), M, K, R, ptr(out), buf.stride(-2), Rpad, stream_ptr(),
          flops=2 * M * R * K)
+    return buf
+
+
+def lora_down_seg(buf, K, A, scale, seg_rows, M=None, Rpad=None):
+    """lora_down with one scale row per segment of `seg_rows` consecutive rows of buf (a stacked sample): scale f32 [nseg, R], rows
+    stride(0) apart; row m of buf takes scale[m // seg_rows], and a zero entry gives exactly +0 (uv_lora_down_seg_bf16). The rows of
+    `scale` must cover the M rows; the last segment may be partial."""
+    R = A.shape[0]
+    M = buf.shape[0] if M is None else M
+    Rpad = (R + 127) // 128 * 128 if Rpad is None else Rpad
+    nseg = scale.shape[0] if scale is not None and scale.dim() == 2 else 0
+    _check("lora_down_seg", (buf, "buf", BF16, K + Rpad, M), (A, "A", BF16, K, R), (scale, "scale", F32, R, nseg))
+    if buf.dim() != 2 or A.dim() != 2 or A.shape[1] != K or scale.shape[1] != R or buf.shape[1] < K + Rpad or M > buf.shape[0]:
+        raise UnividHipError(f"lora_down_seg: buffer {tuple(buf.shape)} / A {tuple(A.shape)} / scale {tuple(scale.shape)} do not fit K = {K}, "
+                             f"slot = {Rpad}, M = {M}")
+    seg_rows = int(seg_rows)
+    if seg_rows < 1 or nseg < 1 or nseg * seg_rows < M:
+        raise UnividHipError(f"lora_down_seg: {nseg} scale row(s) for segments of {seg_rows} row(s) do not cover M = {M}")
+    out = buf[:, K:]
+    call("uv_lora_down_seg_bf16", ptr(buf), buf.stride(-2), ptr(A), A.stride(-2), ptr(scale), scale.stride(-2), seg_rows, nseg, M, K, R,
+         ptr(out), buf.stride(-2), Rpad, stream_ptr(), flops=2 * M * R * K)
     return buf
 
 

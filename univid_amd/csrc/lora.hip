@@ -22,9 +22,14 @@
 #define LD_ROWS (LD_WAVES * 16)
 #define LD_OPITCH (128 + 8)
 
-template <int NT, int KC>
+// SEG (uv_lora_down_seg_bf16): the scale is a matrix, one row per segment of seg_rows consecutive rows of x (a stacked sample). The row's
+// scale is looked up per output row in the epilogue (a segment boundary may fall anywhere in a 16-row tile), an entry that is == 0
+// stores +0 whatever the accumulator holds, and a workgroup whose scale entries of this pass are zero for every segment its 32 rows touch
+// skips the pass before the K loop: no read of x, no MFMA, zero stores only. !SEG is uv_lora_down_bf16: it never skips or selects.
+template <int NT, int KC, bool SEG>
 __global__ __launch_bounds__(LD_THREADS) void lora_down_kernel(const bf16_t* __restrict__ x, long ldx, const bf16_t* __restrict__ A, long lda,
-                                                               const float* __restrict__ scale, int M, int K, int R, bf16_t* out, long ldo) {
+                                                               const float* __restrict__ scale, long ld_scale, int seg_rows, int M, int K, int R,
+                                                               bf16_t* out, long ldo) {
     constexpr int PITCH = KC + 8, XS = KC / 32, CPR = KC / 8, AS = NT * 16 * CPR / LD_THREADS;      // x loads / chunks per A row / A loads per lane
     __shared__ __attribute__((aligned(16))) bf16_t sA[NT * 16 * PITCH];
     __shared__ __attribute__((aligned(16))) bf16_t sO[LD_WAVES][16 * LD_OPITCH];
@@ -34,7 +39,17 @@ __global__ __launch_bounds__(LD_THREADS) void lora_down_kernel(const bf16_t* __r
     const int j0 = blockIdx.y * 128;                    // first rank of this pass
     const u32x4 zero4 = {0u, 0u, 0u, 0u};
 
-    if (j0 < R) {                                        // (uniform per workgroup: a pass without ranks only stores zeros)
+    bool live = j0 < R;                                  // (uniform per workgroup: a pass without ranks only stores zeros)
+    if constexpr (SEG) {
+        if (live) {
+            const int m0 = blockIdx.x * LD_ROWS, m1 = min(m0 + LD_ROWS, M) - 1;         // m0 < M: the grid covers M rows
+            const int s0 = m0 / seg_rows, ns = m1 / seg_rows - s0 + 1, nr = min(R - j0, 128);
+            int on = 0;
+            for (int idx = tid; idx < ns * nr; idx += LD_THREADS) on |= scale[(long)(s0 + idx / nr) * ld_scale + j0 + idx % nr] != 0.f;
+            live = __syncthreads_or(on) != 0;
+        }
+    }
+    if (live) {
         const long m = row0 + r16;
         const bool row_ok = m < M;
         const bf16_t* xrow = x + (row_ok ? m : 0) * ldx + g * 8;
@@ -81,17 +96,30 @@ __global__ __launch_bounds__(LD_THREADS) void lora_down_kernel(const bf16_t* __r
             }
         }
         // C/D map: column (rank) = lane & 15, row = (lane >> 4) * 4 + i
+        int seg[4];                                      // SEG: the segment of each of the lane's four output rows (rows >= M: the last row's)
+        if constexpr (SEG) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) seg[i] = (int)min(row0 + g * 4 + i, (long)M - 1) / seg_rows;
+        }
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
             const int col = t * 16 + r16, j = j0 + col;
-            const float s = j < R ? scale[j] : 0.f;
+            if constexpr (SEG) {
 #pragma unroll
-            for (int i = 0; i < 4; ++i)
-                sO[wave][(g * 4 + i) * LD_OPITCH + col] = j < R ? f2bf(__fmul_rn(s, acc[t][i])) : (bf16_t)0;
+                for (int i = 0; i < 4; ++i) {
+                    const float s = j < R ? scale[(long)seg[i] * ld_scale + j] : 0.f;
+                    sO[wave][(g * 4 + i) * LD_OPITCH + col] = s != 0.f ? f2bf(__fmul_rn(s, acc[t][i])) : (bf16_t)0;
+                }
+            } else {
+                const float s = j < R ? scale[j] : 0.f;
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+                    sO[wave][(g * 4 + i) * LD_OPITCH + col] = j < R ? f2bf(__fmul_rn(s, acc[t][i])) : (bf16_t)0;
+            }
         }
         __syncthreads();
     }
-    const int ncol = j0 < R ? NT * 16 : 0;              // columns of this pass that came through sO
+    const int ncol = live ? NT * 16 : 0;                // columns of this pass that came through sO
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
         const int idx = q * 64 + lane, r = idx >> 4, c = (idx & 15) * 8;
@@ -100,27 +128,48 @@ __global__ __launch_bounds__(LD_THREADS) void lora_down_kernel(const bf16_t* __r
     }
 }
 
-extern "C" int uv_lora_down_bf16(const void* x, long ldx, const void* A, long lda, const float* scale, int M, int K, int R, void* out,
-                                 long ldo, int Rpad, void* stream) {
-    UV_CHECK_ARG(x && A && scale && out, "uv_lora_down_bf16: null pointer");
-    UV_CHECK_ARG(M > 0 && K > 0 && K % 64 == 0, "uv_lora_down_bf16: M = %d, K = %d (K must be a positive multiple of 64)", M, K);
-    UV_CHECK_ARG(R >= 1 && R <= Rpad && Rpad % 128 == 0, "uv_lora_down_bf16: R = %d, Rpad = %d (1 <= R <= Rpad, Rpad %% 128 == 0)", R, Rpad);
+// the argument checks and the launch shared by the two entry points (seg_rows == 0: uv_lora_down_bf16, the scale is one vector)
+static int lora_down_launch(const char* fn, const void* x, long ldx, const void* A, long lda, const float* scale, long ld_scale, int seg_rows,
+                            int M, int K, int R, void* out, long ldo, int Rpad, void* stream) {
+    UV_CHECK_ARG(x && A && scale && out, "%s: null pointer", fn);
+    UV_CHECK_ARG(M > 0 && K > 0 && K % 64 == 0, "%s: M = %d, K = %d (K must be a positive multiple of 64)", fn, M, K);
+    UV_CHECK_ARG(R >= 1 && R <= Rpad && Rpad % 128 == 0, "%s: R = %d, Rpad = %d (1 <= R <= Rpad, Rpad %% 128 == 0)", fn, R, Rpad);
     UV_CHECK_ARG(ldx >= K && lda >= K && ldo >= Rpad && ldx % 8 == 0 && lda % 8 == 0 && ldo % 8 == 0,
-                 "uv_lora_down_bf16: leading dimensions (%ld, %ld, %ld) must cover the rows and be multiples of 8", ldx, lda, ldo);
-    UV_CHECK_ARG((((uintptr_t)x | (uintptr_t)A | (uintptr_t)out) & 15) == 0 && ((uintptr_t)scale & 3) == 0, "uv_lora_down_bf16: misaligned pointers");
+                 "%s: leading dimensions (%ld, %ld, %ld) must cover the rows and be multiples of 8", fn, ldx, lda, ldo);
+    UV_CHECK_ARG((((uintptr_t)x | (uintptr_t)A | (uintptr_t)out) & 15) == 0 && ((uintptr_t)scale & 3) == 0, "%s: misaligned pointers", fn);
     const long gx = ((long)M + LD_ROWS - 1) / LD_ROWS;
-    UV_CHECK_ARG(gx <= 0x7fffffffL && Rpad / 128 <= 65535, "uv_lora_down_bf16: launch too large");
+    UV_CHECK_ARG(gx <= 0x7fffffffL &&Rpad / 128 <= 65535, "%s: launch too large", fn);
     const dim3 grid((unsigned)gx, (unsigned)(Rpad / 128)), block(LD_THREADS);
     const int nr = R < 128 ? R : 128;                    // ranks of the widest pass
     const bf16_t *xp = (const bf16_t*)x, *ap = (const bf16_t*)A;
     bf16_t* op = (bf16_t*)out;
     hipStream_t st = (hipStream_t)stream;
-    if (nr <= 16) hipLaunchKernelGGL((lora_down_kernel<1, 256>), grid, block, 0, st, xp, ldx, ap, lda, scale, M, K, R, op, ldo);
-    else if (nr <= 32) hipLaunchKernelGGL((lora_down_kernel<2, 256>), grid, block, 0, st, xp, ldx, ap, lda, scale, M, K, R, op, ldo);
-    else if (nr <= 64) hipLaunchKernelGGL((lora_down_kernel<4, 256>), grid, block, 0, st, xp, ldx, ap, lda, scale, M, K, R, op, ldo);
-    else hipLaunchKernelGGL((lora_down_kernel<8, 128>), grid, block, 0, st, xp, ldx, ap, lda, scale, M, K, R, op, ldo);
-    UV_CHECK_LAUNCH("uv_lora_down_bf16");
+#define LD_LAUNCH(NT, KC)                                                                                                                  \
+    do {                                                                                                                                   \
+        if (seg_rows) hipLaunchKernelGGL((lora_down_kernel<NT, KC, true>), grid, block, 0, st, xp, ldx, ap, lda, scale, ld_scale, seg_rows, \
+                                         M, K, R, op, ldo);                                                                                \
+        else hipLaunchKernelGGL((lora_down_kernel<NT, KC, false>), grid, block, 0, st, xp, ldx, ap, lda, scale, 0L, 0, M, K, R, op, ldo);   \
+    } while (0)
+    if (nr <= 16) LD_LAUNCH(1, 256);
+    else if (nr <= 32) LD_LAUNCH(2, 256);
+    else if (nr <= 64) LD_LAUNCH(4, 256);
+    else LD_LAUNCH(8, 128);
+#undef LD_LAUNCH
+    UV_CHECK_LAUNCH(fn);
     return 0;
+}
+
+extern "C" int uv_lora_down_bf16(const void* x, long ldx, const void* A, long lda, const float* scale, int M, int K, int R, void* out,
+                                 long ldo, int Rpad, void* stream) {
+    return lora_down_launch("uv_lora_down_bf16", x, ldx, A, lda, scale, 0, 0, M, K, R, out, ldo, Rpad, stream);
+}
+
+extern "C" int uv_lora_down_seg_bf16(const void* x, long ldx, const void* A, long lda, const float* scale, long ld_scale, int seg_rows, int nseg,
+                                     int M, int K, int R, void* out, long ldo, int Rpad, void* stream) {
+    UV_CHECK_ARG(seg_rows >= 1 && nseg >= 1 && (long)nseg * seg_rows >= M,
+                 "uv_lora_down_seg_bf16: seg_rows = %d, nseg = %d must be >= 1 and cover M = %d rows", seg_rows, nseg, M);
+    UV_CHECK_ARG(ld_scale >= R, "uv_lora_down_seg_bf16: ld_scale = %ld < R = %d", ld_scale, R);
+    return lora_down_launch("uv_lora_down_seg_bf16", x, ldx, A, lda, scale, ld_scale, seg_rows, M, K, R, out, ldo, Rpad, stream);
 }
 
 // out[r][c] = bf16(in[r][c]) for rows with their own leading dimensions (uv_cast_f32_bf16 for an output that carries a LoRA slot)

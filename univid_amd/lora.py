@@ -21,6 +21,12 @@ low-rank parts are summed in the fp32 accumulator. Several adapters can be attac
 slot), `set_adapter_weight` rewrites the scale vector only, `unload(name)` detaches; attaching / detaching re-prepares only the
 attention / FFN modules whose projections changed.
 
+Per-sample weights (`set_adapter_weights([{name: weight}, ...])`, `WanTI2V.denoise(..., adapter_weights=)`): one dict per sample of a
+stacked forward - the CFG pair's two branches, or requests that share a forward - instead of one strength for all of them. The scale is
+then a matrix [samples, R] and the down-projection is `uv_lora_down_seg_bf16`, which looks the scale up per output row; a weight of 0 gives
+exact +0 slot columns, so the sample's bits are those of a model without the adapter, and a workgroup whose rows only touch samples
+with the adapter off does not read x at all. Each sample is bit-identical to a single-sample forward at those weights set globally.
+
 On-disk format read here (what `lora_model.save_pretrained(dir)` writes, model_pipeline.py:608-616, and the manual fallback of
 :627-640): `adapter_config.json` (r, lora_alpha, use_rslora, use_dora, bias, fan_in_fan_out, target_modules) and
 `adapter_model.safetensors` | `adapter_model.bin` | `lora_weights.pt` with keys
@@ -153,7 +159,7 @@ def _adapters_changed(model: nn.Module, paths=(), rescale=False):
         if hasattr(m, "_kv_cache"):
             m._kv_cache = {}
     if hasattr(model, "_prep_gen"):
-        model._prep_gen += 1
+        model._new_generation()
         model._ctx_cache = None
 
 
@@ -334,6 +340,20 @@ class LoRAManager:
                 ad["weight"] = float(weight)
         _adapters_changed(self.lora_model, rescale=True)
 
+    def set_adapter_weights(self, per_sample=None):
+        """Per-sample strengths inside one stacked forward: a list with one {adapter name: weight} dict per sample of the coming forwards
+        (names left out keep their global weight), or None for the global weights again (WanModel.set_adapter_weights)."""
+        if self.lora_model is None or not self.attached:
+            if per_sample is None:
+                return
+            raise RuntimeError("no un-merged adapter is attached: load one with load_lora_weights(dir, model, merge=False)")
+        if per_sample is not None:
+            for d in per_sample:
+                for name in (d if isinstance(d, dict) else ()):
+                    if name not in self.attached:
+                        raise KeyError(f"no un-merged adapter named {name!r} (attached: {sorted(self.attached)})")
+        self.lora_model.set_adapter_weights(per_sample)
+
     def merge_and_unload(self):
         """model_pipeline.py:752-764: the adapter is already merged; the dense model is returned and the saved base weights dropped."""
         if self.lora_model is None:
@@ -351,6 +371,10 @@ class LoRAManager:
         if self.attached:
             if name is not None and name not in self.attached:
                 raise KeyError(f"no un-merged adapter named {name!r} (attached: {sorted(self.attached)})")
+            # per-sample weights that name an adapter which goes away go with it
+            ps = self.lora_model.adapter_weights() if hasattr(self.lora_model, "adapter_weights") else None
+            if ps is not None and (name is None or any(name in d for d in ps)):
+                self.lora_model.set_adapter_weights(None)
             detach_adapter_(self.lora_model, name)
             for n in ([name] if name is not None else list(self.attached)):
                 del self.attached[n]
@@ -377,6 +401,7 @@ class LoRAManager:
         return {
             "mode": "unmerged" if self.attached else "merged",
             "adapters": list(self.attached),
+            "per_sample": bool(self.attached) and getattr(self.lora_model, "adapter_weights", lambda: None)() is not None,
             "lora_modules": len(m),
             "module_breakdown": {"cross_attention": sum("cross_attn" in x for x in m), "self_attention": sum("self_attn" in x for x in m),
                                  "ffn": sum("ffn" in x for x in m), "total": len(m)},

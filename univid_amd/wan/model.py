@@ -109,8 +109,10 @@ LORA_MAX_SLOT = 512     # columns of one activation's slot = the stacked rank of
 
 
 class _LoraSlot:
-    """Stacked lora_A [R, K] bf16, the per-row scale f32 [R] (scaling x run-time weight) and the slot width S of one activation."""
-    __slots__ = ("A", "scale", "S", "rows")
+    """Stacked lora_A [R, K] bf16, the per-row scale f32 [R] (scaling x run-time weight) and the slot width S of one activation.
+    Under per-sample adapter weights (WanModel.set_adapter_weights) also the scale matrix f32 [samples, R], one row per sample of the
+    coming forwards: `seg` on the device, `seg_host` its host copy (None = global weights: the launch is the vector one)."""
+    __slots__ = ("A", "scale", "S", "rows", "seg", "seg_host")
 
     def __init__(self, entries, dev):
         self.rows = [(ad, ad["A"].shape[0]) for ad in entries]
@@ -121,12 +123,33 @@ class _LoraSlot:
                              f"(LORA_MAX_SLOT) an activation buffer carries")
         self.A = torch.cat([ad["A"].to(device=dev, dtype=BF16) for ad in entries]).contiguous()
         self.scale = torch.empty(R, dtype=torch.float32, device=dev)
+        self.seg = self.seg_host = None
         self.refresh_scale()
 
     def refresh_scale(self):
         """Re-reads scaling x weight of every adapter into the device vector, in place (graph-captured launches read the same memory)."""
         host = torch.cat([torch.full((r,), float(ad["scaling"]) * float(ad["weight"]), dtype=torch.float32) for ad, r in self.rows])
         self.scale.copy_(host)
+        # per-sample weights: `ad["per_sample"]` holds one weight per sample (None = the adapter's global weight). The device matrix is kept
+        # when the model goes back to global weights: a captured graph of that setting reads it again when the setting comes back
+        n = max((len(ad["per_sample"]) for ad, _ in self.rows if ad.get("per_sample") is not None), default=0)
+        if not n:
+            self.seg_host = None
+            return
+        def w(ad, i):
+            ps = ad.get("per_sample")
+            return float(ad["weight"] if ps is None or ps[i] is None else ps[i])
+        self.seg_host = torch.stack([torch.cat([torch.full((r,), float(ad["scaling"]) * w(ad, i), dtype=torch.float32) for ad, r in self.rows])
+                                     for i in range(n)])
+        if self.seg is None or self.seg.shape != self.seg_host.shape:
+            with torch.inference_mode(False):      # a normal tensor: written in place by later settings, inside or outside inference mode
+                self.seg = torch.empty(self.seg_host.shape, dtype=torch.float32, device=self.scale.device)
+        self.seg.copy_(self.seg_host)
+
+    def rows_equal(self, s0, n):
+        """True when the samples [s0, s0 + n) carry the same scale row (always, under global weights)."""
+        h = self.seg_host
+        return h is None or bool((h[s0:s0 + n] == h[s0:s0 + 1]).all())
 
 
 def _prepare_group(lins):
@@ -157,9 +180,11 @@ def _act_buf(rows, K, slots, dev):
     return torch.empty(rows, K + S, dtype=BF16, device=dev)
 
 
-def _slotted(t, K, slot, M=None):
+def _slotted(t, K, slot, M=None, seg_rows=None, s0=0):
     """The activation `t` (x in its first K columns) as the [W | B] GEMMs of `slot` read it: the slot's down-projection of the first M
-    rows written behind the K columns, in place when `t` was allocated with room for it (_act_buf), into a widened copy otherwise."""
+    rows written behind the K columns, in place when `t` was allocated with room for it (_act_buf), into a widened copy otherwise.
+    Under per-sample adapter weights the M rows are stacked samples of seg_rows rows each (None: one sample), the first of them sample
+    s0 of the forward: each takes its own scale row."""
     if slot is None:
         return t
     M = t.shape[0] if M is None else M
@@ -167,8 +192,10 @@ def _slotted(t, K, slot, M=None):
         e = torch.empty(t.shape[0], K + slot.S, dtype=BF16, device=t.device)
         e[:M, :K].copy_(t[:M, :K])
         t = e
-    if M:
+    if M and slot.seg_host is None:
         _lib.lora_down(t, K, slot.A, slot.scale, M=M, Rpad=slot.S)
+    elif M:
+        _lib.lora_down_seg(t, K, slot.A, slot.seg[s0:], M if seg_rows is None else seg_rows, M=M, Rpad=slot.S)
     return t
 
 
@@ -201,6 +228,8 @@ class WanSelfAttention(nn.Module):
         self._prep = None
         self._slots = {}
         self._kv_cache = {}
+        self._s0 = 0     # index of the first sample this module is running among the samples of per-sample adapter weights (set by the
+                         # block's _run for its duration: the launch methods below keep their signatures)
 
     _groups = {"qkv": ("q", "k", "v"), "o": ("o",)}      # projections by the activation they read (one LoRA slot each)
 
@@ -220,7 +249,7 @@ class WanSelfAttention(nn.Module):
         p = self._prep
         dev = h.device
         M = batch * L
-        h = _slotted(h, C, self._slots["qkv"], M)
+        h = _slotted(h, C, self._slots["qkv"], M, L, self._s0)
         ql = torch.empty(M, C, dtype=BF16, device=dev)
         kl = torch.empty(M, C, dtype=BF16, device=dev)
         vt = _vt_scratch("vt", C, batch, L, dev)
@@ -231,7 +260,7 @@ class WanSelfAttention(nn.Module):
         _lib.rmsnorm_rope_qk(ql, kl, self.norm_q.weight, self.norm_k.weight, M, L, C, D, self.eps, freqs, grid)
         att = _act_buf(M, C, (self._slots["o"],), dev)
         _lib.flash_attn(ql, kl, vt, att, L, L, H, D, 1.0 / math.sqrt(D), batch=batch)
-        att = _slotted(att, C, self._slots["o"], M)
+        att = _slotted(att, C, self._slots["o"], M, L, self._s0)
         _lib.gemm_bf16(att, p["o"].w, p["o"].b, x_resid, EPI_GATE_RESID_F32, M=M, gate=gate, gate_tid=gate_tid)
 
     def _self_attn_sp(self, h, n, grid, freqs, x_resid, gate, gate_tid, batch, sp):
@@ -254,7 +283,7 @@ class WanSelfAttention(nn.Module):
         kf = torch.empty(batch * Lt, Cp, dtype=BF16, device=dev)
         vtf = _vt_scratch("vt_sp", Cp, batch, Lt, dev)
         if M:
-            h = _slotted(h, C, self._slots["qkv"], M)
+            h = _slotted(h, C, self._slots["qkv"], M, n, self._s0)
             _lib.gemm_bf16(h, p["q"].w, p["q"].b, ql, EPI_BF16, M=M)
             _lib.gemm_bf16(h, p["k"].w, p["k"].b, kl, EPI_BF16, M=M)
             _lib.gemm_bf16(h, p["v"].w, p["v"].b, vt, EPI_BF16_T, M=M)
@@ -272,7 +301,7 @@ class WanSelfAttention(nn.Module):
         for b in range(batch):
             par.tokens_to_heads(attf[b * Lt:(b + 1) * Lt], Lt, att[b * n:(b + 1) * n])
         if M:
-            att = _slotted(att, C, self._slots["o"], M)
+            att = _slotted(att, C, self._slots["o"], M, n, self._s0)
             _lib.gemm_bf16(att, p["o"].w, p["o"].b, x_resid, EPI_GATE_RESID_F32, M=M, gate=gate, gate_tid=gate_tid)
 
     def forward(self, x, seq_lens, grid_sizes, freqs):
@@ -286,7 +315,7 @@ class WanSelfAttention(nn.Module):
             Lk = int(seq_lens[b])
             C, H, D = self.dim, self.num_heads, self.head_dim
             p = self._prep
-            h = _slotted(x[b].to(BF16).contiguous(), C, self._slots["qkv"])
+            h = _slotted(x[b].to(BF16).contiguous(), C, self._slots["qkv"], s0=self._s0 + b)      # (sample b of the batch: its own row)
             ql = torch.empty(L, C, dtype=BF16, device=x.device)
             kl = torch.empty(L, C, dtype=BF16, device=x.device)
             vt = torch.zeros(C, _round_up(L, 64), dtype=BF16, device=x.device)
@@ -298,7 +327,7 @@ class WanSelfAttention(nn.Module):
             _lib.rmsnorm_rope(kl, kl, self.norm_k.weight, L, C, D, self.eps, fr, grid)
             att = _act_buf(L, C, (self._slots["o"],), x.device)
             _lib.flash_attn(ql, kl, vt, att, L, Lk, H, D, 1.0 / math.sqrt(D))
-            att = _slotted(att, C, self._slots["o"])
+            att = _slotted(att, C, self._slots["o"], s0=self._s0 + b)
             y = torch.empty(L, C, dtype=BF16, device=x.device)
             _lib.gemm_bf16(att, p["o"].w, p["o"].b, y, EPI_BF16)
             outs.append(y)
@@ -325,7 +354,7 @@ class WanCrossAttention(WanSelfAttention):
         C, D = self.dim, self.head_dim
         p = self._prep
         dev = ctx.device
-        ctx = _slotted(ctx, C, self._slots["kv"], batch * Lc)
+        ctx = _slotted(ctx, C, self._slots["kv"], batch * Lc, Lc, self._s0)
         if out is not None:
             kl, vt = out
             _lib.gemm_bf16(ctx, p["k"].w, p["k"].b, kl, EPI_BF16, M=batch * Lc)
@@ -354,7 +383,7 @@ class WanCrossAttention(WanSelfAttention):
         p = self._prep
         dev = hq.device
         M = batch * L
-        hq = _slotted(hq, C, self._slots["q"], M)
+        hq = _slotted(hq, C, self._slots["q"], M, L, self._s0)
         ql = torch.empty(M, C, dtype=BF16, device=dev)
         kl, vt = self._context_kv(ctx, Lc, batch, kv_key)
         att = _act_buf(M, C, (self._slots["o"],), dev)
@@ -374,7 +403,7 @@ class WanCrossAttention(WanSelfAttention):
         return att
 
     def _cross_fused(self, hq, ctx, L, Lc, x_resid, batch=1, kv_key=None):
-        att = _slotted(self._attend(hq, ctx, L, Lc, batch, kv_key), self.dim, self._slots["o"], batch * L)
+        att = _slotted(self._attend(hq, ctx, L, Lc, batch, kv_key), self.dim, self._slots["o"], batch * L, L, self._s0)
         p = self._prep["o"]
         _lib.gemm_bf16(att, p.w, p.b, x_resid, EPI_RESID_F32, M=batch * L)
 
@@ -386,7 +415,12 @@ class WanCrossAttention(WanSelfAttention):
         outs = []
         for b in range(x.size(0)):
             L, Lc = x.size(1), context.size(1)
-            att = _slotted(self._attend(x[b].to(BF16).contiguous(), context[b].to(BF16).contiguous(), L, Lc), self.dim, self._slots["o"])
+            self._s0 += b           # (sample b of the batch takes its own row of per-sample adapter weights)
+            try:
+                att = _slotted(self._attend(x[b].to(BF16).contiguous(), context[b].to(BF16).contiguous(), L, Lc), self.dim, self._slots["o"],
+                               s0=self._s0)
+            finally:
+                self._s0 -= b
             y = torch.empty(L, self.dim, dtype=BF16, device=x.device)
             p = self._prep["o"]
             _lib.gemm_bf16(att, p.w, p.b, y, EPI_BF16)
@@ -431,12 +465,23 @@ class WanAttentionBlock(nn.Module):
         p2, s2 = _prepare_group({"ffn2": self.ffn[2]})
         self._prep, self._slots = {**p0, **p2}, {"ffn0": s0, "ffn2": s2}
 
-    def _run(self, x, L, e0_rows, tid, grid, freqs, ctx, first_block, batch=1, sp=None, kv_key=None, twin_rows=False):
+    def _run(self, x, L, e0_rows, tid, grid, freqs, ctx, first_block, batch=1, sp=None, kv_key=None, twin_rows=False, s0=0):
+        """One block on the stacked samples (_run_block); s0 = the first stacked sample's index among the samples of per-sample adapter
+        weights (WanModel.set_adapter_weights), which the attention modules' slot launches read for the length of the call."""
+        self.self_attn._s0 = self.cross_attn._s0 = s0
+        try:
+            self._run_block(x, L, e0_rows, tid, grid, freqs, ctx, first_block, batch, sp, kv_key, twin_rows, s0)
+        finally:
+            self.self_attn._s0 = self.cross_attn._s0 = 0
+
+    def _run_block(self, x, L, e0_rows, tid, grid, freqs, ctx, first_block, batch, sp, kv_key, twin_rows, s0):
         """x: fp32 [batch*L, C] residual stream (independent samples stacked along the token axis), updated IN PLACE.
         e0_rows: fp32 [n_t, 6C]; tid int32 [batch*L] | None; ctx: bf16 [batch*Lc, C] embedded context(s); kv_key: cache key of
         the context's cross-attention K / V^T (WanCrossAttention._context_kv), None = recompute.
         twin_rows: the stacked samples enter this block with IDENTICAL rows and timesteps (the CFG pair on one latent, before its
-        first cross-attention): the self-attention half runs on sample 0 only and its result is copied to the others."""
+        first cross-attention): the self-attention half runs on sample 0 only and its result is copied to the others - unless per-sample
+        adapter weights give the samples different scale rows in the self-attention's slots.
+        s0: the first stacked sample's index among the samples of per-sample adapter weights (WanModel.set_adapter_weights)."""
         C = self.dim
         dev = x.device
         # (an adapter attached or detached since the last forward left exactly its own module un-prepared: univid_amd/lora.py)
@@ -456,7 +501,7 @@ class WanAttentionBlock(nn.Module):
         # NOTE for consumers of `mid` (ffn.0's output, below): its rows >= L are the GELU of whatever the allocator left in h_full[L:]
         # - UNDEFINED, possibly NaN / Inf. Rows are independent in every kernel of the block and ffn.2 reads L rows only.
         # self-attention (model.py:243-247)
-        if twin_rows and batch > 1 and sp is None:
+        if twin_rows and batch > 1 and sp is None and all(s is None or s.rows_equal(s0, batch) for s in self.self_attn._slots.values()):
             t1 = None if tid is None else tid[:Ls]
             _lib.layernorm_mod(x[:Ls], h[:Ls], Ls, C, self.eps, mode=1, tab=tab, shift_off=0, scale_off=C, tid=t1, round_ln=first_block)
             self.self_attn._self_attn(h[:Ls], Ls, grid, freqs, x[:Ls], tab[:, 2 * C:], t1, 1, None)
@@ -496,12 +541,12 @@ class WanAttentionBlock(nn.Module):
             _lib.mx_quant(mid, mq, ms)
             _lib.gemm_mxfp8(mq, ms, p2.w, p2.s, p2.b, x, EPI_GATE_RESID_F32, M=L, gate=tab[:, 5 * C:], gate_tid=tid)
             return
-        h_full = _slotted(h_full, C, self._slots["ffn0"], L)
+        h_full = _slotted(h_full, C, self._slots["ffn0"], L, Ls, s0)
         mid = _act_buf(Lf, self.ffn_dim, (self._slots["ffn2"],), dev)
         _lib.gemm_bf16(h_full, self._prep["ffn0"].w, self._prep["ffn0"].b, mid, EPI_GELU_BF16, M=Lf)
         # ffn.2's leftover rows (1 120 of 22 880) as one round of 256 x 256 tiles x split-K 4 where the library has that strip for the
         # shape (K >= 8192): it needs scratch for the partial tiles (63 MB at this shape; the allocator hands every block the same one)
-        mid = _slotted(mid, self.ffn_dim, self._slots["ffn2"], L)
+        mid = _slotted(mid, self.ffn_dim, self._slots["ffn2"], L, Ls, s0)
         nws = _splitk_ws_bytes(L, C, self._prep["ffn2"].w.shape[1], dev)
         ws = torch.empty(nws, dtype=torch.uint8, device=dev) if nws else None
         _lib.gemm_bf16(mid, self._prep["ffn2"].w, self._prep["ffn2"].b, x, EPI_GATE_RESID_F32, M=L,
@@ -521,7 +566,7 @@ class WanAttentionBlock(nn.Module):
             xb = x[b].float().contiguous().clone()
             tid = torch.arange(L, dtype=torch.int32, device=x.device)
             self._run(xb, L, e[b].reshape(L, -1).contiguous(), tid, tuple(int(v) for v in grid_sizes[b]), fr,
-                      context[b].to(BF16).contiguous(), first_block=(x.dtype == BF16))
+                      context[b].to(BF16).contiguous(), first_block=(x.dtype == BF16), s0=b)
             outs.append(xb)
         return torch.stack(outs)
 
@@ -699,7 +744,14 @@ class WanModel(nn.Module):
         self._prep = None
         self._ctx_cache = None   # (key, input tensors kept alive, embedded contexts, generation): see _embedded_context
         self._ctx_gen = 0
-        self._prep_gen = 0       # bumped by prepare() and invalidate(): the identity of "the prepared weights" for cache / graph keys
+        # `_prep_gen`: the identity of "the prepared weights" for cache / graph keys, moved on by prepare(), invalidate(), the LoRA manager
+        # (and by anybody who assigns to it). Under per-sample adapter weights (set_adapter_weights) it identifies (prepared weights,
+        # setting): a setting that comes back under unchanged weights gets its generation - and its captured graph - back
+        self._adapter_weights = None
+        self._gen_top = 0        # the highest generation handed out
+        self._gen_global = 0     # the generation of the global weights (None: not handed out yet)
+        self._gen_settings = {}  # per-sample setting -> its generation
+        self._gen = 0
         # Step-constant context work (text_embedding, cross-attention K / V^T) computed once per context. OFF for the bare
         # reference-signature forward: the cache key is tensor identity + version counter, which cannot see writes that bypass the
         # counter (`.data` writes, raw-pointer kernels). A sampling loop that OWNS its context tensors for its duration switches it
@@ -712,10 +764,35 @@ class WanModel(nn.Module):
         self.register_load_state_dict_post_hook(lambda m, _k: m.invalidate())
 
     # ---- weight preparation -------------------------------------------------------------------------------
+    @property
+    def _prep_gen(self):
+        return self._gen
+
+    @_prep_gen.setter
+    def _prep_gen(self, value):
+        # an assignment says "the prepared weights changed": the value belongs to the present per-sample setting, every other generation
+        # (the other settings', the global weights') is forgotten
+        self._gen = int(value)
+        self._gen_top = max(self._gen_top, self._gen)
+        self._gen_global, self._gen_settings = None, {}
+        if self._adapter_weights is None:
+            self._gen_global = self._gen
+        else:
+            self._gen_settings[self._adapter_weights] = self._gen
+
+    def _new_generation(self):
+        """What was prepared, cached or captured so far can never be served again (weights, adapters or their global strengths changed):
+        a generation nobody has seen, for the present per-sample setting; every other setting's generation is forgotten."""
+        self._prep_gen = self._gen_top + 1
+
+    def generation_alive(self, gen):
+        """True while a per-sample setting (or the global weights) that was given generation `gen` can come back and get it again."""
+        return gen == self._gen_global or gen in self._gen_settings.values()
+
     def invalidate(self):
         """Forget the bf16 weight copies (call after changing parameters in place)."""
         self._prep = None
-        self._prep_gen += 1
+        self._new_generation()
         self._ctx_cache = None
         for b in self.blocks:
             b._prep = None
@@ -750,7 +827,7 @@ class WanModel(nn.Module):
         pe = nn.Linear(1, 1, bias=True)
         pe.weight = nn.Parameter(self.patch_embedding.weight.detach().flatten(1), requires_grad=False)
         pe.bias = nn.Parameter(self.patch_embedding.bias.detach(), requires_grad=False)
-        self._prep_gen += 1
+        self._new_generation()
         self._prep = {
             "patch": _Prepared(pe, pad_k=64),
             "text0": _Prepared(self.text_embedding[0], pad_k=64),
@@ -828,6 +905,92 @@ class WanModel(nn.Module):
                 weights = None
         self._text_weight = None if weights is None else (weights, int(text_len), None if layers is None else frozenset(int(i) for i in layers))
 
+    # ---- per-sample adapter weights -------------------------------------------------------------------------
+    def _attached_adapters(self):
+        """{adapter name: its nn.Linear entries} of the un-merged adapters attached to this model (univid_amd/lora.py)."""
+        ads = {}
+        for m in self.modules():
+            for name, ad in (getattr(m, "_uv_lora", None) or {}).items():
+                ads.setdefault(name, []).append(ad)
+        return ads
+
+    def set_adapter_weights(self, per_sample=None):
+        """Strengths of the un-merged adapters PER SAMPLE of the coming forwards, inside one stacked pass: `per_sample` is a list with one
+        `{adapter name: weight}` dict per sample of the forward's x / context lists (the CFG pair stacked as [cond, uncond]: a style adapter
+        on the conditional branch only is `[{"style": 1.0}, {"style": 0.0}]`; two requests with different adapters share one stacked
+        forward). A name absent from a dict takes the adapter's global weight (LoRAManager.set_adapter_weight); weight 0 switches the
+        adapter off for that sample: its slot columns are exactly +0 and the sample's bits are those of a model without it. None restores
+        the global weights: the launch is then exactly the global one. Everything is validated before any state changes.
+        Like set_adapter_weight, a change drops the cached cross-attention K / V^T and the embedded context and moves `_prep_gen` on, so
+        HIP-graph runners re-capture - but a setting that was used before (under unchanged adapters and global weights) gets the
+        generation it had, so its captured graph is replayed."""
+        key = None
+        if per_sample is not None:
+            ads = self._attached_adapters()
+            rows = []
+            for i, d in enumerate(per_sample):
+                if not isinstance(d, dict):
+                    raise TypeError(f"set_adapter_weights: sample {i}: a dict {{adapter name: weight}} is expected, got {type(d).__name__}")
+                row = []
+                for name, w in d.items():
+                    if name not in ads:
+                        raise KeyError(f"set_adapter_weights: sample {i}: no un-merged adapter named {name!r} is attached (attached: {sorted(ads)})")
+                    w = float(w)
+                    if not math.isfinite(w):
+                        raise ValueError(f"set_adapter_weights: sample {i}: weight {w} of adapter {name!r} is not finite")
+                    row.append((name, w))
+                rows.append(tuple(sorted(row)))
+            if not rows:
+                raise ValueError("set_adapter_weights: an empty list (pass None for the global weights)")
+            key = tuple(rows)
+        if key == self._adapter_weights:
+            return
+        self._install_adapter_weights(key)
+
+    def _install_adapter_weights(self, key):
+        # the slots' device matrices are re-allocated when the sample count changes: graphs captured on the old ones must not come back
+        n_old = max((len(k) for k in self._gen_settings), default=None)
+        if key is not None and n_old is not None and len(key) != n_old:
+            self._gen_settings = {}
+        for name, entries in self._attached_adapters().items():
+            for ad in entries:
+                ad["per_sample"] = None if key is None else [dict(row).get(name) for row in key]
+        self._adapter_weights = key
+        for m in self.modules():
+            for slot in (getattr(m, "_slots", None) or {}).values():
+                if slot is not None:
+                    slot.refresh_scale()
+            if hasattr(m, "_kv_cache"):
+                m._kv_cache = {}
+        self._ctx_cache = None
+        if key is None:
+            if self._gen_global is None:
+                self._gen_top += 1
+                self._gen_global = self._gen_top
+            self._gen = self._gen_global
+            return
+        if key not in self._gen_settings:
+            while len(self._gen_settings) >= 16:      # (the oldest setting's graph is re-captured if it ever comes back)
+                del self._gen_settings[next(iter(self._gen_settings))]
+            self._gen_top += 1
+            self._gen_settings[key] = self._gen_top
+        self._gen = self._gen_settings[key]
+
+    def adapter_weights(self):
+        """The present per-sample setting as set_adapter_weights takes it (None: global weights)."""
+        return None if self._adapter_weights is None else [dict(row) for row in self._adapter_weights]
+
+    def _adapter_rows_differ(self):
+        """True when the per-sample setting gives two samples different strengths of some attached adapter."""
+        key = self._adapter_weights
+        if key is None:
+            return False
+        for name, entries in self._attached_adapters().items():
+            ws = [dict(row).get(name, entries[0]["weight"]) for row in key]
+            if any(w != ws[0] for w in ws):
+                return True
+        return False
+
     def weighted_context(self, ctx_all, idx, tw):
         """Embedded contexts of the samples `idx` stacked [len(idx) * text_len, C] with sample i's first tw[1] rows scaled by bf16(tw[0][i])."""
         weights, n_scaled, _ = tw
@@ -868,6 +1031,13 @@ class WanModel(nn.Module):
         """
         if self.model_type == "i2v":
             assert y is not None
+        aw = self._adapter_weights
+        if aw is not None:
+            if len(aw) != len(x):
+                raise ValueError(f"set_adapter_weights was given {len(aw)} sample(s); this forward has {len(x)} sample(s)")
+            if self.sp is not None and self.sp.size > 1 and self._adapter_rows_differ():
+                raise NotImplementedError("set_adapter_weights: per-sample adapter weights that differ between the samples are not built for "
+                                          "sequence-parallel forwards (equal rows, or the global weights, are)")
         _ensure_prepared(self)
         dev = self.patch_embedding.weight.device
         if y is not None:
@@ -947,7 +1117,7 @@ class WanModel(nn.Module):
                 hooked = ctx_w is not None and (tw[2] is None or li in tw[2])
                 if par is None or n:
                     blk._run(xs, n, e0_rows, tid, (Fp, Hp, Wp), fr, ctx_w if hooked else ctx, first_block=(li == 0), batch=B, sp=sp_arg,
-                             kv_key=None if hooked else kv_key, twin_rows=(twin and li == 0))
+                             kv_key=None if hooked else kv_key, twin_rows=(twin and li == 0), s0=idx[0])
                 else:   # a rank without tokens still takes part in the self-attention exchanges
                     blk.self_attn._self_attn_sp(xs.new_empty(0, C).to(BF16), 0, (Fp, Hp, Wp), fr, xs, None, None, B, sp_arg)
             yh = self.head._run(xs, B * n, e_rows, tid) if B * n else xs.new_empty(0, self.head.head.out_features)

@@ -300,12 +300,13 @@ class WanTI2V:
     def _runner_for(self, key, make):
         """The cached runner of `key` = (latent shape, i2v, prepared-weights generation, text_len), moved to the most-recently-used end, or
         `make()` stored under it. Returns (runner, fresh). Before a capture: runners of other prepared weights / another text_len are
-        dropped (they can never be asked for again) and the least recently used ones go until there is room - their graphs' pools are
+        dropped (they can never be asked for again; the generation of a per-sample adapter setting that can come back is kept) and the least recently used ones go until there is room - their graphs' pools are
         freed BEFORE the new capture allocates its own. A `make()` that raises leaves nothing behind under `key`."""
         runner = self._runners.pop(key, None)
         fresh = runner is None
         if fresh:
-            for stale in [k for k in self._runners if k[2:] != key[2:]]:
+            alive = getattr(getattr(self, "model", None), "generation_alive", lambda g: False)    # (a per-sample adapter setting that can come back)
+            for stale in [k for k in self._runners if k[2:] != key[2:] and not (k[3:] == key[3:] and alive(k[2]))]:
                 del self._runners[stale]
             while len(self._runners) >= max(1, self.max_graph_runners):
                 self._runners.popitem(last=False)
@@ -343,7 +344,7 @@ class WanTI2V:
     def generate(self, input_prompt, img=None, size=(1280, 704), max_area=704 * 1280, frame_num=81, shift=5.0,
                  sample_solver="unipc", sampling_steps=50, guide_scale=5.0, n_prompt="", seed=-1, offload_model=True,
                  **kw):
-        """textimage2video.py:162-237."""
+        """textimage2video.py:162-237. Keyword extensions of t2v / i2v (prompt_embeds=, noise=, decode=, adapter_weights=) pass through."""
         if img is not None:
             return self.i2v(input_prompt=input_prompt, img=img, max_area=max_area, frame_num=frame_num, shift=shift,
                             sample_solver=sample_solver, sampling_steps=sampling_steps, guide_scale=guide_scale,
@@ -354,11 +355,48 @@ class WanTI2V:
 
     # ---- the hot loop ----------------------------------------------------------------------------------------
     def denoise(self, noise, context, context_null, sampling_steps, shift, guide_scale, z=None, record=None, graph=None,
-                sample_solver="unipc"):
+                sample_solver="unipc", adapter_weights=None):
+        """adapter_weights: strengths of the un-merged adapters for THIS call - one {adapter name: weight} dict for both branches of the
+        CFG pair, or a (cond, uncond) pair of dicts (a style adapter on the conditional branch only: ({"style": 1.0}, {"style": 0.0})).
+        Installed with WanModel.set_adapter_weights for the length of the call - on the stacked pair eager or replayed from a HIP graph
+        (a repeated request with the same weights replays its capture), one branch per rank under CFG parallelism - and the previous
+        setting is restored afterwards. None: the model's setting as it is. See _denoise for the other arguments."""
         # the loop owns its context tensors for its duration: step-constant context work is computed once (WanModel.context_cached)
         cached = self.model.context_cached() if hasattr(self.model, "context_cached") else contextlib.nullcontext()
-        with cached:
-            return self._denoise(noise, context, context_null, sampling_steps, shift, guide_scale, z, record, graph, sample_solver)
+        if adapter_weights is None:
+            with cached:
+                return self._denoise(noise, context, context_null, sampling_steps, shift, guide_scale, z, record, graph, sample_solver)
+        per_sample = self._adapter_rows(adapter_weights)
+        previous = self.model.adapter_weights()
+        self.model.set_adapter_weights(per_sample)          # validates before anything changes
+        try:
+            with cached:
+                return self._denoise(noise, context, context_null, sampling_steps, shift, guide_scale, z, record, graph, sample_solver)
+        finally:
+            self.model.set_adapter_weights(previous)
+
+    def _adapter_rows(self, adapter_weights):
+        """denoise's adapter_weights= as the per-sample list of the forwards this pipeline runs: [cond, uncond] for the stacked pair, this
+        rank's branch under CFG parallelism, the one dict where the pair runs as two separate forwards."""
+        if isinstance(adapter_weights, dict):
+            cond = uncond = adapter_weights
+        else:
+            try:
+                cond, uncond = adapter_weights
+            except (TypeError, ValueError):
+                raise TypeError("adapter_weights: one {adapter name: weight} dict or a (cond, uncond) pair of them") from None
+            if not (isinstance(cond, dict) and isinstance(uncond, dict)):
+                raise TypeError("adapter_weights: one {adapter name: weight} dict or a (cond, uncond) pair of them")
+        if not hasattr(self.model, "set_adapter_weights"):
+            raise NotImplementedError("adapter_weights= needs a WanModel (set_adapter_weights)")
+        if self.cfgp is not None:
+            return [cond if self.cfgp.rank == 0 else uncond]
+        if "forward" in self.model.__dict__:
+            if dict(cond) != dict(uncond):
+                raise NotImplementedError("adapter_weights: a re-assigned model.forward runs the CFG pair as two separate forwards; different "
+                                          "weights for the two branches need the stacked pair (or CFG parallelism)")
+            return [cond]
+        return [cond, uncond]
 
     def _denoise(self, noise, context, context_null, sampling_steps, shift, guide_scale, z=None, record=None, graph=None,
                  sample_solver="unipc"):
@@ -526,7 +564,7 @@ class WanTI2V:
 
     def t2v(self, input_prompt, size=(1280, 704), frame_num=121, shift=5.0, sample_solver="unipc", sampling_steps=50,
             guide_scale=5.0, n_prompt="", seed=-1, offload_model=True, *, prompt_embeds=None, negative_prompt_embeds=None,
-            noise=None, decode=True):
+            noise=None, decode=True, adapter_weights=None):
         """textimage2video.py:239-411. Returns the video [3, N, H, W] in [-1, 1] (or the latent if decode=False)."""
         F = frame_num
         z_dim = self.model.in_dim
@@ -539,7 +577,8 @@ class WanTI2V:
         if noise is None:
             noise = self._noise(target_shape, seed)
         with torch.no_grad():
-            x0 = self.denoise(noise, context, context_null, sampling_steps, shift, guide_scale, sample_solver=sample_solver)
+            x0 = self.denoise(noise, context, context_null, sampling_steps, shift, guide_scale, sample_solver=sample_solver,
+                              adapter_weights=adapter_weights)
             if not decode:
                 return x0
             if self.vae is None:
@@ -548,7 +587,7 @@ class WanTI2V:
 
     def i2v(self, input_prompt, img, max_area=704 * 1280, frame_num=121, shift=5.0, sample_solver="unipc",
             sampling_steps=40, guide_scale=5.0, n_prompt="", seed=-1, offload_model=True, *, prompt_embeds=None,
-            negative_prompt_embeds=None, noise=None, decode=True):
+            negative_prompt_embeds=None, noise=None, decode=True, adapter_weights=None):
         """textimage2video.py:413-619. `img` is a PIL image, or a float tensor [3, H, W] in [-1, 1] that already has
         the output size (the PIL resize/crop of :462-477 is host-side image I/O)."""
         if self.vae is None:
@@ -581,5 +620,6 @@ class WanTI2V:
         context_null = self._encode(n_prompt, negative_prompt_embeds)
         with torch.no_grad():
             z = self.vae.encode([img_t])[0]
-            x0 = self.denoise(noise, context, context_null, sampling_steps, shift, guide_scale, z=z, sample_solver=sample_solver)
+            x0 = self.denoise(noise, context, context_null, sampling_steps, shift, guide_scale, z=z, sample_solver=sample_solver,
+                              adapter_weights=adapter_weights)
             return self.vae.decode([x0])[0] if decode else x0
