@@ -440,6 +440,69 @@ def test_context_cache_is_scoped_and_survives_inference_tensors():
     assert m._prep_gen == g0 + 1
 
 
+def test_vt_cols_is_the_attention_kernels_layout():
+    """_lib.vt_cols(batch, L): every sample but the last takes L columns, the last runs up to its 64-key tile bound."""
+    want = {(1, 1): 64, (1, 64): 64, (1, 65): 128, (2, 512): 1024, (3, 8): 80}
+    assert {k: _lib.vt_cols(*k) for k in want} == want
+
+
+def test_context_kv_is_refused_before_any_device_work():
+    """WanModel.forward(context_kv=): a wrong number of (k, V^T) pairs, mixed shapes and a re-assigned cross-attention forward raise
+    their own errors on a model that has no device (preparing its weights would raise UnividHipError)."""
+    from oracle import wan_dit
+    cfg = wan_dit.TINY_CFG
+    m = WanModel.from_config(dict(cfg, model_type="ti2v"))
+    x, small = torch.zeros(cfg["in_dim"], 4, 16, 16), torch.zeros(cfg["in_dim"], 2, 8, 8)
+    kv = [(None, None)] * len(m.blocks)
+    with pytest.raises(ValueError, match=r"1 \(k, V\^T\) pair\(s\) for 2 block"):
+        m([x, x], None, None, 256, context_kv=kv[:1])
+    with pytest.raises(ValueError, match="one shape"):
+        m([x, small], None, None, 256, context_kv=kv)
+    m.blocks[1].cross_attn.forward = lambda *a, **k: None
+    with pytest.raises(NotImplementedError, match="re-assigned"):
+        m([x, x], None, None, 256, context_kv=kv)
+    del m.blocks[1].cross_attn.forward
+    with pytest.raises(_lib.UnividHipError):
+        m([x, x], None, None, 256, context_kv=kv)
+
+
+def test_sample_offset_lives_on_a_module_for_the_hooked_call_only(monkeypatch):
+    """The sample offset of per-sample adapter weights is an argument everywhere but in a re-assigned cross_attn.forward, which the block
+    serves through WanCrossAttention._s0 for the length of that call: a closure sees it, and after a forward that raises midway - inside
+    the closure, or before any block ran - no attention module carries a non-zero offset."""
+    from oracle import wan_dit
+    from univid_amd.wan import model as M
+
+    class NoLaunch:                  # every entry point a no-op: the host path of a block runs without a device
+        vt_cols = staticmethod(_lib.vt_cols)
+
+        def __getattr__(self, name):
+            return lambda *a, **k: None
+    cfg = wan_dit.TINY_CFG
+    m = WanModel.from_config(dict(cfg, model_type="ti2v"))
+
+    def offsets():
+        return [mod._s0 for mod in m.modules() if hasattr(mod, "_s0")]
+    assert offsets() == [0] * len(m.blocks) and not hasattr(m.blocks[0].self_attn, "_s0")
+    with pytest.raises(_lib.UnividHipError):
+        m([torch.zeros(cfg["in_dim"], 4, 16, 16)], torch.zeros(1), [torch.zeros(4, cfg["text_dim"])], 256)
+    assert offsets() == [0] * len(m.blocks)
+    monkeypatch.setattr(M, "_lib", NoLaunch())
+    blk, seen, attn_kw = m.blocks[0], [], []
+    blk.self_attn._self_attn = lambda *a, **k: attn_kw.append(k)
+
+    def closure(x, context, context_lens=None):
+        seen.append(blk.cross_attn._s0)
+        raise RuntimeError("boom")
+    blk.cross_attn.forward = closure
+    C, Ls = cfg["dim"], 256
+    with pytest.raises(RuntimeError, match="boom"):
+        blk._run(torch.zeros(2 * Ls, C), Ls, torch.zeros(1, 6 * C), None, (4, 8, 8), None, torch.zeros(2 * 8, C, dtype=torch.bfloat16), False,
+                 batch=2, s0=1)
+    assert seen == [1] and attn_kw == [{"s0": 1}]
+    assert offsets() == [0] * len(m.blocks)
+
+
 def test_vae_pass_length_falls_back_when_memory_runs_out():
     """WanVAE_._with_pass_length: an out-of-memory error at `frames_per_pass` frames retries with half the pass length down to the
     reference's 1 (the result does not depend on it), with the engine and its workspace arena released first; at 1 the error propagates."""

@@ -204,13 +204,22 @@ def _attach_ab(tmp_path, cfg, m, names=NAMES18):
 @gpu
 def test_stacked_samples_take_their_own_adapter_weights(tmp_path):
     """M1: three stacked samples with their own mixes, each bit-identical to a single-sample forward with those values set globally (the
-    forwards test_unmerged_adapter_tiny_model_vs_unmerged_oracle gates against the oracle); the all-off sample is the base model."""
+    forwards test_unmerged_adapter_tiny_model_vs_unmerged_oracle gates against the oracle); the all-off sample is the base model.
+    The same for the ways a sample's offset into the weights reaches the launches: stacked (an argument of one pass), a mixed-shape batch
+    (one pass per sample), block 0's cross_attn.forward re-assigned to a closure (the one call that cannot carry an argument), and both."""
     g = load_golden("dit_tiny")
     cfg, sd, m = _tiny_model(g["seed"])
     x0, t, c0 = g["x"].to(DEV), g["t_one"].to(DEV), g["ctx"].to(DEV)
     xs = [x0, (x0 * 0.5).contiguous(), (x0 + 0.1).contiguous()]
     cs = [c0, (c0 * 0.5).contiguous(), (c0 * 0.8).contiguous()]
     mixes = [{"a": 1.0, "b": 0.0}, {"a": 0.0, "b": 0.5}, {"a": 0.0, "b": 0.0}]
+    small = torch.randn(48, 2, 8, 8, generator=torch.Generator().manual_seed(5)).to(DEV)
+    mixed = [xs[0], small, xs[2]]            # not one shape: the samples run one by one, each at its own offset into the per-sample weights
+    ca = m.blocks[0].cross_attn
+    original = ca.forward
+
+    def closure(x, context, context_lens=None):      # UniVid's hook reduced to its call of the original bound forward
+        return original(x, context, context_lens)
     with torch.no_grad():
         base = [m([xs[i]], t, [cs[i]], LT)[0] for i in range(3)]
         mgr = _attach_ab(tmp_path, cfg, m)
@@ -219,15 +228,28 @@ def test_stacked_samples_take_their_own_adapter_weights(tmp_path):
             for name, w in mix.items():
                 mgr.set_adapter_weight(name, w)
             singles.append(m([xs[i]], t, [cs[i]], LT)[0])
+            if i == 1:
+                small_single = m([small], t, [cs[1]], LT)[0]
         mgr.set_adapter_weight("a", 1.0)
         mgr.set_adapter_weight("b", 1.0)
         mgr.set_adapter_weights(mixes)
         assert mgr.get_statistics()["per_sample"] is True
         got = m(xs, torch.cat([t, t, t]), cs, LT)
         again = m(xs, torch.cat([t, t, t]), cs, LT)
+        got_mixed = m(mixed, torch.cat([t, t, t]), cs, LT)
+        ca.forward = closure
+        try:
+            got_hooked = m(xs, torch.cat([t, t, t]), cs, LT)
+            got_mixed_hooked = m(mixed, torch.cat([t, t, t]), cs, LT)
+        finally:
+            del ca.forward
     for i in range(3):
         assert torch.equal(got[i], singles[i]), f"sample {i} differs from the single-sample forward at its weights"
         assert torch.equal(again[i], got[i])
+        want_mixed = small_single if i == 1 else singles[i]
+        assert torch.equal(got_mixed[i], want_mixed), f"mixed shapes: sample {i} differs from the single-sample forward at its weights"
+        assert torch.equal(got_hooked[i], got[i]), f"re-assigned cross_attn.forward: sample {i} differs from the un-hooked forward"
+        assert torch.equal(got_mixed_hooked[i], want_mixed), f"mixed shapes + re-assigned cross_attn.forward: sample {i}"
     assert torch.equal(got[2], base[2]), "a sample with every adapter off must be the base model bit for bit"
     assert not torch.equal(got[0], base[0]) and not torch.equal(got[1], base[1])
     # names left out take the adapter's global weight (a = b = 1 here)

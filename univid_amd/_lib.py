@@ -465,15 +465,22 @@ def gemm_f32(a, w, bias, out, resid=None, M=None):
 
 
 # -- DiT: attention and its operator seam --
+def vt_cols(batch, L):
+    """Columns of the V^T operand of `flash_attn` for `batch` stacked samples of L keys: sample b's keys are columns [b*L, (b+1)*L), and
+    the last sample's run up to its 64-key tile bound. The columns past batch*L are masked by the kernels (P = 0 exactly), so they only
+    have to be FINITE."""
+    return (batch - 1) * L + (L + 63) // 64 * 64
+
+
 def flash_attn(q, k, vt, out, Lq, Lk, H, D, scale, batch=1, q_rs=None, q_weight=None):
-    """q [batch*Lq, C], k [batch*Lk, C], vt [C, >= (batch-1)*Lk + roundup(Lk, 64)] (sample b = columns b*Lk..), out [batch*Lq, C].
+    """q [batch*Lq, C], k [batch*Lk, C], vt [C, >= vt_cols(batch, Lk)] (sample b = columns b*Lk..), out [batch*Lq, C].
     q_rs / q_weight: q is the RAW projection and the kernel's Q prologue applies norm_q (per-row scale f32 [batch*Lq], weight f32 [C])."""
     f16 = q.dtype == F16
     C, half = H * D, F16 if f16 else BF16
     if f16 and q_rs is not None:      # uv_flash_attn_bf16_qnorm would read the fp16 bits as bf16
         raise UnividHipError("flash_attn: the q-norm prologue (q_rs / q_weight) is built for bf16 only, q is fp16")
     _check("flash_attn", (q, "q", half, C, batch * Lq), (k, "k", half, C, batch * Lk),
-           (vt, "vt", half, (batch - 1) * Lk + (Lk + 63) // 64 * 64, C), (out, "out", half, C, batch * Lq),
+           (vt, "vt", half, vt_cols(batch, Lk), C), (out, "out", half, C, batch * Lq),
            (q_rs, "q_rs", F32, batch * Lq, None, True), (q_weight, "q_weight", F32, C, None, q_rs is None))
     if q_rs is not None:
         call("uv_flash_attn_bf16_qnorm", ptr(q), q.stride(-2), ptr(k), k.stride(-2), ptr(vt), vt.stride(-2), ptr(out), out.stride(-2),
@@ -490,7 +497,7 @@ def attn_kernel_name(Lq, Lk, D, batch=1, H=None, f16=False, ldk=None, ldvt=None)
     H = H or 1
     buf = ctypes.create_string_buffer(96)
     ldk = H * D if ldk is None else ldk
-    ldvt = (batch - 1) * Lk + (Lk + 63) // 64 * 64 if ldvt is None else ldvt
+    ldvt = vt_cols(batch, Lk) if ldvt is None else ldvt
     rc = load().uv_flash_attn_kernel_name(Lk, D, int(ldk), int(ldvt), int(f16), buf, 96)
     if rc != 0:
         raise UnividHipError(load().uv_last_error().decode())
@@ -504,7 +511,7 @@ def attn_plan(Lq, Lk, D, batch=1, H=1, f16=False, ldk=None, ldvt=None):
     buf = ctypes.create_string_buffer(96)
     qb, n12, grid = _I(0), _I(0), _I(0)
     ldk = H * D if ldk is None else ldk
-    ldvt = (batch - 1) * Lk + (Lk + 63) // 64 * 64 if ldvt is None else ldvt
+    ldvt = vt_cols(batch, Lk) if ldvt is None else ldvt
     lib = load()
     if lib.uv_flash_attn_plan(batch, Lq, Lk, H, D, int(ldk), int(ldvt), int(f16), buf, 96, ctypes.byref(qb), ctypes.byref(n12), ctypes.byref(grid)) != 0:
         raise UnividHipError(lib.uv_last_error().decode())

@@ -26,6 +26,9 @@ stacked forward - the CFG pair's two branches, or requests that share a forward 
 then a matrix [samples, R] and the down-projection is `uv_lora_down_seg_bf16`, which looks the scale up per output row; a weight of 0 gives
 exact +0 slot columns, so the sample's bits are those of a model without the adapter, and a workgroup whose rows only touch samples
 with the adapter off does not read x at all. Each sample is bit-identical to a single-sample forward at those weights set globally.
+Which row of the matrix a launch starts at - the index of its first sample among the forward's samples - travels as the `s0` argument of
+the block's `_run` and the attention launch methods (a re-assigned `cross_attn.forward` reads it from `WanCrossAttention._s0`, set for
+that call only).
 
 On-disk format read here (what `lora_model.save_pretrained(dir)` writes, model_pipeline.py:608-616, and the manual fallback of
 :627-640): `adapter_config.json` (r, lora_alpha, use_rslora, use_dora, bias, fan_in_fan_out, target_modules) and
@@ -151,16 +154,14 @@ def _adapters_changed(model: nn.Module, paths=(), rescale=False):
         own = _owner(model, path)
         if own is not None:
             own._prep = None
-    for m in model.modules():
-        if rescale:
+    if rescale:
+        for m in model.modules():
             for slot in (getattr(m, "_slots", None) or {}).values():
                 if slot is not None:
                     slot.refresh_scale()
-        if hasattr(m, "_kv_cache"):
-            m._kv_cache = {}
-    if hasattr(model, "_prep_gen"):
+    if hasattr(model, "_prep_gen"):       # (a WanModel: only its forward fills those caches)
         model._new_generation()
-        model._ctx_cache = None
+        model._drop_context()
 
 
 def _check_slots(model: nn.Module):

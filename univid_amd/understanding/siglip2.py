@@ -25,10 +25,6 @@ from .._lib import EPI_BF16, EPI_BF16_T, EPI_F32_FROM_BF16, EPI_GELU_BF16, EPI_R
 BF16 = torch.bfloat16
 
 
-def _round_up(a, b):
-    return (a + b - 1) // b * b
-
-
 class _W:
     """16-bit operand copies of one Linear (weight [N, K] with K padded to the GEMM's 64 granularity, bias)."""
     __slots__ = ("w", "b")
@@ -91,7 +87,7 @@ class Siglip2EncoderLayer(nn.Module):
         if stacked or batch == 1:
             yk = y if Lq == Lk else y[:Lk]
             k = torch.empty(batch * Lk, h, dtype=BF16, device=dev)
-            vt = torch.zeros(h, (batch - 1) * Lk + _round_up(Lk, 64), dtype=BF16, device=dev)
+            vt = torch.zeros(h, _lib.vt_cols(batch, Lk), dtype=BF16, device=dev)
             _lib.gemm_bf16(yk, p["k_proj"].w, p["k_proj"].b, k, EPI_BF16, M=batch * Lk)
             _lib.gemm_bf16(yk, p["v_proj"].w, p["v_proj"].b, vt, EPI_BF16_T, M=batch * Lk)
             _lib.flash_attn(q, k, vt, att, Lq, Lk, H, D, D ** -0.5, batch=batch)
@@ -99,7 +95,7 @@ class Siglip2EncoderLayer(nn.Module):
             for b_ in range(batch):
                 yb = y[b_ * Lq:b_ * Lq + Lk]
                 k = torch.empty(Lk, h, dtype=BF16, device=dev)
-                vt = torch.zeros(h, _round_up(Lk, 64), dtype=BF16, device=dev)
+                vt = torch.zeros(h, _lib.vt_cols(1, Lk), dtype=BF16, device=dev)
                 _lib.gemm_bf16(yb, p["k_proj"].w, p["k_proj"].b, k, EPI_BF16)
                 _lib.gemm_bf16(yb, p["v_proj"].w, p["v_proj"].b, vt, EPI_BF16_T)
                 _lib.flash_attn(q[b_ * Lq:(b_ + 1) * Lq], k, vt, att[b_ * Lq:(b_ + 1) * Lq], Lq, Lk, H, D, D ** -0.5)
@@ -249,7 +245,7 @@ class Siglip2VisionModel(nn.Module):
         att = torch.empty(G, h, dtype=BF16, device=dev)
         if G == 1 or n % 8 == 0:
             k = torch.empty(G * n, h, dtype=BF16, device=dev)
-            vt = torch.zeros(h, (G - 1) * n + _round_up(n, 64), dtype=BF16, device=dev)
+            vt = torch.zeros(h, _lib.vt_cols(G, n), dtype=BF16, device=dev)
             _lib.gemm_bf16(y, p["hk"].w, p["hk"].b, k, EPI_BF16)
             _lib.gemm_bf16(y, p["hv"].w, p["hv"].b, vt, EPI_BF16_T)
             _lib.flash_attn(q, k, vt, att, 1, n, H, D, D ** -0.5, batch=G)
@@ -257,7 +253,7 @@ class Siglip2VisionModel(nn.Module):
             for g in range(G):
                 yb = y[g * n:(g + 1) * n]
                 k = torch.empty(n, h, dtype=BF16, device=dev)
-                vt = torch.zeros(h, _round_up(n, 64), dtype=BF16, device=dev)
+                vt = torch.zeros(h, _lib.vt_cols(1, n), dtype=BF16, device=dev)
                 _lib.gemm_bf16(yb, p["hk"].w, p["hk"].b, k, EPI_BF16)
                 _lib.gemm_bf16(yb, p["hv"].w, p["hv"].b, vt, EPI_BF16_T)
                 _lib.flash_attn(q[g:g + 1], k, vt, att[g:g + 1], 1, n, H, D, D ** -0.5)

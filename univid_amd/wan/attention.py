@@ -87,19 +87,18 @@ def flash_attention(q, k, v, q_lens=None, k_lens=None, dropout_p=0., softmax_sca
 
     def vt_of(rows, L, vt, col0):
         """vt[:, col0 : col0 + roundup(L, 64)] = rows[:L]^T, zero beyond L."""
-        _lib.transpose_16(rows, vt[:, col0:], L, C, (L + 63) // 64 * 64)
+        _lib.transpose_16(rows, vt[:, col0:], L, C, _lib.vt_cols(1, L))
 
     if len(set(kls)) == 1 and kls[0] == lk and (b == 1 or lk % 8 == 0):
         # every sample attends all Lk keys: ONE launch over the stacked samples (sample s = V^T columns [s*Lk, (s+1)*Lk))
-        cols = (b - 1) * lk + (lk + 63) // 64 * 64
-        vt = torch.empty(C, cols, dtype=vh.dtype, device=dev)
+        vt = torch.empty(C, _lib.vt_cols(b, lk), dtype=vh.dtype, device=dev)
         for s in range(b):      # later samples overwrite the previous sample's zero padding, the last one keeps it
             vt_of(v2[s * lk:(s + 1) * lk], lk, vt, s * lk)
         _lib.flash_attn(q2, k2, vt, out.view(b * lq, C), lq, lk, n, c, scale, batch=b)
     else:
         for s in range(b):      # ragged key lengths: one launch per sample on its first k_lens[s] keys
             L = kls[s]
-            vt = torch.empty(C, (L + 63) // 64 * 64, dtype=vh.dtype, device=dev)
+            vt = torch.empty(C, _lib.vt_cols(1, L), dtype=vh.dtype, device=dev)
             vt_of(v2[s * lk:s * lk + L], L, vt, 0)
             _lib.flash_attn(q2[s * lq:(s + 1) * lq], k2[s * lk:s * lk + L], vt, out[s], lq, L, n, c, scale)
     out = out.view(b, lq, n, c)

@@ -228,8 +228,6 @@ class WanSelfAttention(nn.Module):
         self._prep = None
         self._slots = {}
         self._kv_cache = {}
-        self._s0 = 0     # index of the first sample this module is running among the samples of per-sample adapter weights (set by the
-                         # block's _run for its duration: the launch methods below keep their signatures)
 
     _groups = {"qkv": ("q", "k", "v"), "o": ("o",)}      # projections by the activation they read (one LoRA slot each)
 
@@ -240,30 +238,43 @@ class WanSelfAttention(nn.Module):
             self._prep.update(preps)
         self._kv_cache = {}
 
-    def _self_attn(self, h, L, grid, freqs, x_resid, gate, gate_tid, batch=1, sp=None):
-        """h: bf16 [batch*L, C] modulated input (samples stacked along the token axis). Adds o(attn) * gate into x_resid
-        (fp32) in the GEMM epilogue. sp = (SeqParallel, L_total, r0): h holds this rank's token range of every sample."""
-        if sp is not None:
-            return self._self_attn_sp(h, L, grid, freqs, x_resid, gate, gate_tid, batch, sp)
-        C, H, D = self.dim, self.num_heads, self.head_dim
-        p = self._prep
-        dev = h.device
-        M = batch * L
-        h = _slotted(h, C, self._slots["qkv"], M, L, self._s0)
-        ql = torch.empty(M, C, dtype=BF16, device=dev)
-        kl = torch.empty(M, C, dtype=BF16, device=dev)
-        vt = _vt_scratch("vt", C, batch, L, dev)
+    def _qkv(self, h, M, seg_rows, s0, vt):
+        """The q / k / v projections of h's first M rows (stacked samples of seg_rows rows, the first of them sample s0 of the forward's
+        per-sample adapter weights): the slot's down-projection, then q and k as bf16 [M, C] (returned) and V^T into vt's first M columns
+        (sample b = columns b*seg_rows..)."""
+        C, p = self.dim, self._prep
+        h = _slotted(h, C, self._slots["qkv"], M, seg_rows, s0)
+        ql = torch.empty(M, C, dtype=BF16, device=h.device)
+        kl = torch.empty(M, C, dtype=BF16, device=h.device)
         _lib.gemm_bf16(h, p["q"].w, p["q"].b, ql, EPI_BF16, M=M)
         _lib.gemm_bf16(h, p["k"].w, p["k"].b, kl, EPI_BF16, M=M)
-        _lib.gemm_bf16(h, p["v"].w, p["v"].b, vt, EPI_BF16_T, M=M)   # V^T [C, tokens]: sample b = columns b*L..
+        _lib.gemm_bf16(h, p["v"].w, p["v"].b, vt, EPI_BF16_T, M=M)
+        return ql, kl
+
+    def _attn(self, h, L, Lk, grid, freqs, batch, s0):
+        """Self-attention of h (bf16 [batch*L, C], samples stacked along the token axis) over each sample's first Lk keys (Lk < L: the
+        rest of L is padding; one sample only) -> the attention output as the o projection reads it."""
+        C, H, D = self.dim, self.num_heads, self.head_dim
+        M = batch * L
+        vt = _vt_scratch("vt", C, batch, L, h.device)
+        ql, kl = self._qkv(h, M, L, s0, vt)
         # q and k of every stacked sample in one launch (RoPE positions restart with every sample)
         _lib.rmsnorm_rope_qk(ql, kl, self.norm_q.weight, self.norm_k.weight, M, L, C, D, self.eps, freqs, grid)
-        att = _act_buf(M, C, (self._slots["o"],), dev)
-        _lib.flash_attn(ql, kl, vt, att, L, L, H, D, 1.0 / math.sqrt(D), batch=batch)
-        att = _slotted(att, C, self._slots["o"], M, L, self._s0)
-        _lib.gemm_bf16(att, p["o"].w, p["o"].b, x_resid, EPI_GATE_RESID_F32, M=M, gate=gate, gate_tid=gate_tid)
+        att = _act_buf(M, C, (self._slots["o"],), h.device)
+        _lib.flash_attn(ql, kl, vt, att, L, Lk, H, D, 1.0 / math.sqrt(D), batch=batch)
+        return _slotted(att, C, self._slots["o"], M, L, s0)
 
-    def _self_attn_sp(self, h, n, grid, freqs, x_resid, gate, gate_tid, batch, sp):
+    def _self_attn(self, h, L, grid, freqs, x_resid, gate, gate_tid, batch=1, sp=None, s0=0):
+        """h: bf16 [batch*L, C] modulated input (samples stacked along the token axis). Adds o(attn) * gate into x_resid
+        (fp32) in the GEMM epilogue. sp = (SeqParallel, L_total, r0): h holds this rank's token range of every sample.
+        s0: the first stacked sample's index among the samples of per-sample adapter weights (WanModel.set_adapter_weights)."""
+        if sp is not None:
+            return self._self_attn_sp(h, L, grid, freqs, x_resid, gate, gate_tid, batch, sp, s0=s0)
+        p = self._prep["o"]
+        _lib.gemm_bf16(self._attn(h, L, L, grid, freqs, batch, s0), p.w, p.b, x_resid, EPI_GATE_RESID_F32, M=batch * L, gate=gate,
+                       gate_tid=gate_tid)
+
+    def _self_attn_sp(self, h, n, grid, freqs, x_resid, gate, gate_tid, batch, sp, s0=0):
         """Ulysses form (distributed/sequence_parallel.py:147-176, ulysses.py:9-47): projections, RMSNorm and RoPE on the
         rank's n tokens of each sample; q/k/V^T exchanged to [all tokens, heads/p]; attention over the whole sequence for
         the rank's heads; output exchanged back; o-projection + gated residual on the rank's tokens."""
@@ -276,17 +287,11 @@ class WanSelfAttention(nn.Module):
         dev = h.device
         M = batch * n
         Cp, Hp = C // P, H // P
-        ql = torch.empty(M, C, dtype=BF16, device=dev)
-        kl = torch.empty(M, C, dtype=BF16, device=dev)
-        vt = torch.zeros(C, _round_up(max(M, 1), 64), dtype=BF16, device=dev)
+        vt = torch.zeros(C, _lib.vt_cols(1, max(M, 1)), dtype=BF16, device=dev)      # (the rank's tokens of all samples side by side)
         qf = torch.empty(batch * Lt, Cp, dtype=BF16, device=dev)
         kf = torch.empty(batch * Lt, Cp, dtype=BF16, device=dev)
         vtf = _vt_scratch("vt_sp", Cp, batch, Lt, dev)
-        if M:
-            h = _slotted(h, C, self._slots["qkv"], M, n, self._s0)
-            _lib.gemm_bf16(h, p["q"].w, p["q"].b, ql, EPI_BF16, M=M)
-            _lib.gemm_bf16(h, p["k"].w, p["k"].b, kl, EPI_BF16, M=M)
-            _lib.gemm_bf16(h, p["v"].w, p["v"].b, vt, EPI_BF16_T, M=M)
+        ql, kl = self._qkv(h, M, n, s0, vt) if M else (h.new_empty(0, C), h.new_empty(0, C))
         for b in range(batch):
             rows = slice(b * n, (b + 1) * n)
             if n:
@@ -301,7 +306,7 @@ class WanSelfAttention(nn.Module):
         for b in range(batch):
             par.tokens_to_heads(attf[b * Lt:(b + 1) * Lt], Lt, att[b * n:(b + 1) * n])
         if M:
-            att = _slotted(att, C, self._slots["o"], M, n, self._s0)
+            att = _slotted(att, C, self._slots["o"], M, n, s0)
             _lib.gemm_bf16(att, p["o"].w, p["o"].b, x_resid, EPI_GATE_RESID_F32, M=M, gate=gate, gate_tid=gate_tid)
 
     def forward(self, x, seq_lens, grid_sizes, freqs):
@@ -310,26 +315,11 @@ class WanSelfAttention(nn.Module):
         _ensure_prepared(self)
         outs = []
         fr = _freqs_device(freqs, x.device)
-        for b in range(x.size(0)):
-            L = x.size(1)
-            Lk = int(seq_lens[b])
-            C, H, D = self.dim, self.num_heads, self.head_dim
-            p = self._prep
-            h = _slotted(x[b].to(BF16).contiguous(), C, self._slots["qkv"], s0=self._s0 + b)      # (sample b of the batch: its own row)
-            ql = torch.empty(L, C, dtype=BF16, device=x.device)
-            kl = torch.empty(L, C, dtype=BF16, device=x.device)
-            vt = torch.zeros(C, _round_up(L, 64), dtype=BF16, device=x.device)
-            _lib.gemm_bf16(h, p["q"].w, p["q"].b, ql, EPI_BF16)
-            _lib.gemm_bf16(h, p["k"].w, p["k"].b, kl, EPI_BF16)
-            _lib.gemm_bf16(h, p["v"].w, p["v"].b, vt, EPI_BF16_T)
-            grid = tuple(int(v) for v in grid_sizes[b])
-            _lib.rmsnorm_rope(ql, ql, self.norm_q.weight, L, C, D, self.eps, fr, grid)
-            _lib.rmsnorm_rope(kl, kl, self.norm_k.weight, L, C, D, self.eps, fr, grid)
-            att = _act_buf(L, C, (self._slots["o"],), x.device)
-            _lib.flash_attn(ql, kl, vt, att, L, Lk, H, D, 1.0 / math.sqrt(D))
-            att = _slotted(att, C, self._slots["o"], s0=self._s0 + b)
-            y = torch.empty(L, C, dtype=BF16, device=x.device)
-            _lib.gemm_bf16(att, p["o"].w, p["o"].b, y, EPI_BF16)
+        L, p = x.size(1), self._prep["o"]
+        for b in range(x.size(0)):      # (sample b of the batch takes its own row of per-sample adapter weights)
+            att = self._attn(x[b].to(BF16).contiguous(), L, int(seq_lens[b]), tuple(int(v) for v in grid_sizes[b]), fr, 1, b)
+            y = torch.empty(L, self.dim, dtype=BF16, device=x.device)
+            _lib.gemm_bf16(att, p.w, p.b, y, EPI_BF16, M=L)
             outs.append(y)
         return torch.stack(outs)
 
@@ -339,10 +329,10 @@ class WanCrossAttention(WanSelfAttention):
     part of UniVid's contract: Wan22ContextWrapper finds modules by `__class__.__name__ == 'WanCrossAttention'`
     and replaces `module.forward` with a closure that rescales `context` (model_pipeline.py:1745-1807)."""
     _groups = {"q": ("q",), "kv": ("k", "v"), "o": ("o",)}
-    fuse_q_norm = True      # norm_q inside the attention kernel's Q prologue instead of a pass over q (A/B switch; same arithmetic but for
-                            # the summation order of the row's mean square)
+    _s0 = 0     # a re-assigned `forward` (UniVid's closure) calls the original with (x, context, None) and cannot carry the sample offset:
+                # the block sets this around THAT call only (WanAttentionBlock._run); every other path takes s0 as an argument
 
-    def _context_kv(self, ctx, Lc, batch, kv_key, out=None):
+    def _context_kv(self, ctx, Lc, batch, kv_key, out=None, s0=0):
         """k = norm_k(Wk ctx) [batch*Lc, C] and V^T = (Wv ctx)^T of the embedded context (model.py:170-172). They depend on the
         context and this block's weights only, not on the latent or the timestep, so across the steps of a sampling loop they are
         computed ONCE: `kv_key` identifies the (context generation, sample group) WanModel.forward is running; None = no caching
@@ -354,40 +344,38 @@ class WanCrossAttention(WanSelfAttention):
         C, D = self.dim, self.head_dim
         p = self._prep
         dev = ctx.device
-        ctx = _slotted(ctx, C, self._slots["kv"], batch * Lc, Lc, self._s0)
         if out is not None:
             kl, vt = out
-            _lib.gemm_bf16(ctx, p["k"].w, p["k"].b, kl, EPI_BF16, M=batch * Lc)
-            _lib.gemm_bf16(ctx, p["v"].w, p["v"].b, vt, EPI_BF16_T, M=batch * Lc)
-            _lib.rmsnorm_rope(kl, kl, self.norm_k.weight, batch * Lc, C, D, self.eps)
-            return kl, vt
-        kl = torch.empty(batch * Lc, C, dtype=BF16, device=dev)
-        if kv_key is None:
-            vt = _vt_scratch("cvt", C, batch, Lc, dev)
         else:
-            if batch > 1 and Lc % 8:
-                raise NotImplementedError(f"stacked samples need a context length divisible by 8 (got {Lc})")
-            vt = torch.zeros(C, (batch - 1) * Lc + _round_up(Lc, 64), dtype=BF16, device=dev)
+            kl = torch.empty(batch * Lc, C, dtype=BF16, device=dev)
+            if kv_key is None:
+                vt = _vt_scratch("cvt", C, batch, Lc, dev)
+            else:       # kept in the cache: a tensor of its own
+                if batch > 1 and Lc % 8:
+                    raise NotImplementedError(f"stacked samples need a context length divisible by 8 (got {Lc})")
+                vt = torch.zeros(C, _lib.vt_cols(batch, Lc), dtype=BF16, device=dev)
+        ctx = _slotted(ctx, C, self._slots["kv"], batch * Lc, Lc, s0)
         _lib.gemm_bf16(ctx, p["k"].w, p["k"].b, kl, EPI_BF16, M=batch * Lc)
         _lib.gemm_bf16(ctx, p["v"].w, p["v"].b, vt, EPI_BF16_T, M=batch * Lc)
         _lib.rmsnorm_rope(kl, kl, self.norm_k.weight, batch * Lc, C, D, self.eps)
-        if kv_key is not None:
+        if kv_key is not None and out is None:
             if self._kv_cache and next(iter(self._kv_cache))[0] != kv_key[0]:
                 self._kv_cache.clear()          # a new context generation: the old entries can never hit again
             self._kv_cache[kv_key] = (kl, vt)
         return kl, vt
 
-    def _attend(self, hq, ctx, L, Lc, batch=1, kv_key=None):
-        """hq bf16 [batch*L, C] (normed queries' input), ctx bf16 [batch*Lc, C] -> attention output bf16 [batch*L, C]."""
+    def _attend(self, hq, ctx, L, Lc, batch=1, kv_key=None, kv=None, s0=0):
+        """hq bf16 [batch*L, C] (normed queries' input), ctx bf16 [batch*Lc, C] -> attention output bf16 [batch*L, C].
+        kv = (k, V^T) of the stacked contexts in the caller's own buffers (WanModel.forward's context_kv=): ctx is then not read."""
         C, H, D = self.dim, self.num_heads, self.head_dim
         p = self._prep
         dev = hq.device
         M = batch * L
-        hq = _slotted(hq, C, self._slots["q"], M, L, self._s0)
+        hq = _slotted(hq, C, self._slots["q"], M, L, s0)
         ql = torch.empty(M, C, dtype=BF16, device=dev)
-        kl, vt = self._context_kv(ctx, Lc, batch, kv_key)
+        kl, vt = kv if kv is not None else self._context_kv(ctx, Lc, batch, kv_key, s0=s0)
         att = _act_buf(M, C, (self._slots["o"],), dev)
-        if self.fuse_q_norm and C % 32 == 0:
+        if C % 32 == 0:
             # norm_q without a pass of its own over q (round 5): the q GEMM's epilogue leaves each output row's sums of squares per 32-column
             # group, a tiny kernel turns them into the row scale 1 / sqrt(mean + eps), and the attention kernel's Q prologue applies scale and
             # weight with WanRMSNorm's rounding points (model.py:82-85) while it loads the raw projection
@@ -402,8 +390,8 @@ class WanCrossAttention(WanSelfAttention):
         _lib.flash_attn(ql, kl, vt, att, L, Lc, H, D, 1.0 / math.sqrt(D), batch=batch)
         return att
 
-    def _cross_fused(self, hq, ctx, L, Lc, x_resid, batch=1, kv_key=None):
-        att = _slotted(self._attend(hq, ctx, L, Lc, batch, kv_key), self.dim, self._slots["o"], batch * L, L, self._s0)
+    def _cross_fused(self, hq, ctx, L, Lc, x_resid, batch=1, kv_key=None, kv=None, s0=0):
+        att = _slotted(self._attend(hq, ctx, L, Lc, batch, kv_key, kv, s0), self.dim, self._slots["o"], batch * L, L, s0)
         p = self._prep["o"]
         _lib.gemm_bf16(att, p.w, p.b, x_resid, EPI_RESID_F32, M=batch * L)
 
@@ -413,16 +401,12 @@ class WanCrossAttention(WanSelfAttention):
             raise NotImplementedError("context_lens is always None on UniVid's path (model.py:472)")
         _ensure_prepared(self)
         outs = []
+        L, Lc, p = x.size(1), context.size(1), self._prep["o"]
         for b in range(x.size(0)):
-            L, Lc = x.size(1), context.size(1)
-            self._s0 += b           # (sample b of the batch takes its own row of per-sample adapter weights)
-            try:
-                att = _slotted(self._attend(x[b].to(BF16).contiguous(), context[b].to(BF16).contiguous(), L, Lc), self.dim, self._slots["o"],
-                               s0=self._s0)
-            finally:
-                self._s0 -= b
+            s0 = self._s0 + b       # (sample b of the batch takes its own row of per-sample adapter weights)
+            att = _slotted(self._attend(x[b].to(BF16).contiguous(), context[b].to(BF16).contiguous(), L, Lc, s0=s0), self.dim,
+                           self._slots["o"], s0=s0)
             y = torch.empty(L, self.dim, dtype=BF16, device=x.device)
-            p = self._prep["o"]
             _lib.gemm_bf16(att, p.w, p.b, y, EPI_BF16)
             outs.append(y)
         return torch.stack(outs)
@@ -465,23 +449,15 @@ class WanAttentionBlock(nn.Module):
         p2, s2 = _prepare_group({"ffn2": self.ffn[2]})
         self._prep, self._slots = {**p0, **p2}, {"ffn0": s0, "ffn2": s2}
 
-    def _run(self, x, L, e0_rows, tid, grid, freqs, ctx, first_block, batch=1, sp=None, kv_key=None, twin_rows=False, s0=0):
-        """One block on the stacked samples (_run_block); s0 = the first stacked sample's index among the samples of per-sample adapter
-        weights (WanModel.set_adapter_weights), which the attention modules' slot launches read for the length of the call."""
-        self.self_attn._s0 = self.cross_attn._s0 = s0
-        try:
-            self._run_block(x, L, e0_rows, tid, grid, freqs, ctx, first_block, batch, sp, kv_key, twin_rows, s0)
-        finally:
-            self.self_attn._s0 = self.cross_attn._s0 = 0
-
-    def _run_block(self, x, L, e0_rows, tid, grid, freqs, ctx, first_block, batch, sp, kv_key, twin_rows, s0):
+    def _run(self, x, L, e0_rows, tid, grid, freqs, ctx, first_block, batch=1, sp=None, kv_key=None, twin_rows=False, s0=0, kv=None):
         """x: fp32 [batch*L, C] residual stream (independent samples stacked along the token axis), updated IN PLACE.
         e0_rows: fp32 [n_t, 6C]; tid int32 [batch*L] | None; ctx: bf16 [batch*Lc, C] embedded context(s); kv_key: cache key of
         the context's cross-attention K / V^T (WanCrossAttention._context_kv), None = recompute.
         twin_rows: the stacked samples enter this block with IDENTICAL rows and timesteps (the CFG pair on one latent, before its
         first cross-attention): the self-attention half runs on sample 0 only and its result is copied to the others - unless per-sample
         adapter weights give the samples different scale rows in the self-attention's slots.
-        s0: the first stacked sample's index among the samples of per-sample adapter weights (WanModel.set_adapter_weights)."""
+        s0: the first stacked sample's index among the samples of per-sample adapter weights (WanModel.set_adapter_weights).
+        kv: the caller's own (k, V^T) of the stacked contexts (WanModel.forward's context_kv=): ctx is not read and may be None."""
         C = self.dim
         dev = x.device
         # (an adapter attached or detached since the last forward left exactly its own module un-prepared: univid_amd/lora.py)
@@ -501,29 +477,32 @@ class WanAttentionBlock(nn.Module):
         # NOTE for consumers of `mid` (ffn.0's output, below): its rows >= L are the GELU of whatever the allocator left in h_full[L:]
         # - UNDEFINED, possibly NaN / Inf. Rows are independent in every kernel of the block and ffn.2 reads L rows only.
         # self-attention (model.py:243-247)
-        if twin_rows and batch > 1 and sp is None and all(s is None or s.rows_equal(s0, batch) for s in self.self_attn._slots.values()):
-            t1 = None if tid is None else tid[:Ls]
-            _lib.layernorm_mod(x[:Ls], h[:Ls], Ls, C, self.eps, mode=1, tab=tab, shift_off=0, scale_off=C, tid=t1, round_ln=first_block)
-            self.self_attn._self_attn(h[:Ls], Ls, grid, freqs, x[:Ls], tab[:, 2 * C:], t1, 1, None)
-            for b in range(1, batch):
-                x[b * Ls:(b + 1) * Ls].copy_(x[:Ls])
-        else:
-            _lib.layernorm_mod(x, h, L, C, self.eps, mode=1, tab=tab, shift_off=0, scale_off=C, tid=tid,
-                               round_ln=first_block)
-            self.self_attn._self_attn(h, Ls, grid, freqs, x, tab[:, 2 * C:], tid, batch, sp)
+        twin = twin_rows and batch > 1 and sp is None and all(s is None or s.rows_equal(s0, batch) for s in self.self_attn._slots.values())
+        # the rows and samples the self-attention half runs on: sample 0's for twins (no views on the common path: a slice costs the host
+        # as much as a launch)
+        xa, ha, ta, nb = (x[:Ls], h[:Ls], None if tid is None else tid[:Ls], 1) if twin else (x, h, tid, batch)
+        _lib.layernorm_mod(xa, ha, nb * Ls, C, self.eps, mode=1, tab=tab, shift_off=0, scale_off=C, tid=ta, round_ln=first_block)
+        self.self_attn._self_attn(ha, Ls, grid, freqs, xa, tab[:, 2 * C:], ta, nb, sp, s0=s0)
+        for b in range(nb, batch):
+            x[b * Ls:(b + 1) * Ls].copy_(x[:Ls])
         # cross-attention (model.py:251)
         if self.cross_attn_norm:
             _lib.layernorm_mod(x, h, L, C, self.eps, mode=2, w=self.norm3.weight, b=self.norm3.bias)
         else:
             _lib.cast_f32_bf16(x, h, L, C)
-        Lc = ctx.shape[0] // batch
+        Lc = (ctx if kv is None else kv[0]).shape[0] // batch
         if "forward" in self.cross_attn.__dict__:
-            # forward was re-assigned on the instance (UniVid hook): honour it, then add the residual un-fused
-            y = self.cross_attn.forward(h[:, :C].view(batch, Ls, C), ctx.view(batch, Lc, C), None)
+            # forward was re-assigned on the instance (UniVid hook): honour it, then add the residual un-fused. The closure calls the original
+            # forward(x, context, None), which reads the sample offset from the module: set for this call only
+            self.cross_attn._s0 = s0
+            try:
+                y = self.cross_attn.forward(h[:, :C].view(batch, Ls, C), ctx.view(batch, Lc, C), None)
+            finally:
+                self.cross_attn._s0 = 0
             y = y.reshape(L, C).contiguous()
             _lib.add_bf16_resid(x, y, L, C)
         else:
-            self.cross_attn._cross_fused(h, ctx, Ls, Lc, x, batch, kv_key)
+            self.cross_attn._cross_fused(h, ctx, Ls, Lc, x, batch, kv_key, kv, s0)
         # FFN (model.py:252-255)
         # ffn.0 on rows rounded up to whole 256-row tiles where the extra tiles ride in the last, partial round of the persistent GEMM
         # (22 880 rows x 14 336 columns: 19.47 -> 19.69 rounds, both 20) instead of a leftover-row launch behind it: the pad rows of the
@@ -594,7 +573,7 @@ class Head(nn.Module):
         return out
 
 
-_zero_cache = {}
+_zero_cache = {}     # (tag, device, stream) -> (V^T scratch, its last user (batch, L, data pointer)): _vt_scratch
 
 
 _ncu = {}
@@ -629,41 +608,32 @@ def _ffn0_rows(L, n_cols, dev):
     return Lp if full >= 2 * ncu and -(-padded // ncu) == -(-full // ncu) else L
 
 
-def _zeros_cached(key, shape, dtype, device):
-    """Zero-initialised scratch whose padding region is never written (V^T column padding). One tensor per key: a new shape
-    replaces the old one (the caching allocator frees it in stream order), so the cache does not grow with the resolutions served."""
-    t = _zero_cache.get(key)
-    # (a scratch created under torch.inference_mode() cannot be re-zeroed in place outside it - e.g. by a HIP-graph capture, which runs
-    # outside inference mode -: such a tensor is replaced)
-    if t is None or tuple(t.shape) != tuple(shape) or (t.is_inference() and not torch.is_inference_mode_enabled()):
-        t = torch.zeros(shape, dtype=dtype, device=device)
-        _zero_cache[key] = t
-    return t
-
-
-_vt_user = {}
-
-
 def _vt_scratch(tag, C, batch, L, device):
-    """V^T [C, columns]: sample b's keys are columns [b*L, (b+1)*L); the tail [batch*L, columns) up to the 64-key tile bound is
-    zero. The attention kernels mask the scores of those columns to -inf (P = 0 exactly), so the contract they need is only
+    """V^T [C, _lib.vt_cols(batch, L)]: sample b's keys are columns [b*L, (b+1)*L); the tail [batch*L, columns) up to the 64-key tile
+    bound is zero. The attention kernels mask the scores of those columns to -inf (P = 0 exactly), so the contract they need is only
     that the tail is FINITE (0 * NaN would poison the row); it is kept zero here: different (batch, L) pairs can give the same
-    column count, and then the previous user's V values would sit in the new user's tail - it is re-zeroed on such a change."""
+    column count, and then the previous user's V values would sit in the new user's tail - it is re-zeroed on such a change.
+    One tensor per key: a new shape replaces the old one (the caching allocator frees it in stream order), so the cache does not grow
+    with the resolutions served."""
     if batch > 1 and L % 8:
         raise NotImplementedError(f"stacked samples need a token count divisible by 8 (got {L}); run them one by one")
-    cols = (batch - 1) * L + _round_up(L, 64)
+    cols = _lib.vt_cols(batch, L)
     # one scratch per stream: forwards running concurrently on different streams must not share it
     key = (tag, device, torch.cuda.current_stream(device).cuda_stream)
-    t = _zeros_cached(key, (C, cols), BF16, device)
-    if _vt_user.get(key, (batch, L, t.data_ptr())) != (batch, L, t.data_ptr()) and cols > batch * L:
+    t, user = _zero_cache.get(key, (None, None))
+    # (a scratch created under torch.inference_mode() cannot be re-zeroed in place outside it - e.g. by a HIP-graph capture, which runs
+    # outside inference mode -: such a tensor is replaced)
+    if t is None or tuple(t.shape) != (C, cols) or (t.is_inference() and not torch.is_inference_mode_enabled()):
+        t = torch.zeros(C, cols, dtype=BF16, device=device)
+    if user not in (None, (batch, L, t.data_ptr())) and cols > batch * L:
         t[:, batch * L:].zero_()
-    _vt_user[key] = (batch, L, t.data_ptr())
+    _zero_cache[key] = (t, (batch, L, t.data_ptr()))
     return t
 
 
 def scratch_snapshot():
     """Identity of every per-stream scratch tensor (before a HIP-graph capture)."""
-    return {k: id(t) for k, t in _zero_cache.items()}
+    return {k: id(t) for k, (t, _) in _zero_cache.items()}
 
 
 def scratch_take_new(snapshot):
@@ -671,9 +641,8 @@ def scratch_take_new(snapshot):
     live in that graph's private memory pool, and torch's capture stream (part of their cache key) is shared by all captures."""
     taken = []
     for k in list(_zero_cache):
-        if snapshot.get(k) != id(_zero_cache[k]):
-            taken.append(_zero_cache.pop(k))
-            _vt_user.pop(k, None)
+        if snapshot.get(k) != id(_zero_cache[k][0]):
+            taken.append(_zero_cache.pop(k)[0])
     return taken
 
 
@@ -793,11 +762,16 @@ class WanModel(nn.Module):
         """Forget the bf16 weight copies (call after changing parameters in place)."""
         self._prep = None
         self._new_generation()
-        self._ctx_cache = None
+        self._drop_context()
         for b in self.blocks:
             b._prep = None
             b.self_attn._prep = None
             b.cross_attn._prep = None
+
+    def _drop_context(self):
+        """Forgets the embedded context and every block's cross-attention K / V^T of it."""
+        self._ctx_cache = None
+        for b in self.blocks:
             b.cross_attn._kv_cache = {}
 
     def set_ffn_precision(self, mode):
@@ -884,9 +858,7 @@ class WanModel(nn.Module):
         finally:
             self.cache_context = prev
             if not prev:
-                self._ctx_cache = None
-                for b in self.blocks:
-                    b.cross_attn._kv_cache = {}
+                self._drop_context()
 
     # ---- UniVid's dynamic text weight, native (models/model_pipeline.py:1699-1810) -----------------------------
     def set_text_weight(self, weights=None, text_len=0, layers=None):
@@ -960,9 +932,7 @@ class WanModel(nn.Module):
             for slot in (getattr(m, "_slots", None) or {}).values():
                 if slot is not None:
                     slot.refresh_scale()
-            if hasattr(m, "_kv_cache"):
-                m._kv_cache = {}
-        self._ctx_cache = None
+        self._drop_context()
         if key is None:
             if self._gen_global is None:
                 self._gen_top += 1
@@ -1016,7 +986,14 @@ class WanModel(nn.Module):
             c = self._ctx_cache = (key, list(context), self.embed_context(context), self._ctx_gen)
         return c[2], c[3]
 
-    def forward(self, x, t, context, seq_len, y=None, *, t_rows=None):
+    def _stacks(self, x):
+        """True when the samples x run as ONE stacked pass: one shape, and 16-byte aligned per-sample columns in V^T (token count and
+        context length % 8 == 0)."""
+        pt, ph, pw = self.patch_size
+        _, F0, H0, W0 = x[0].shape
+        return len({tuple(u.shape) for u in x}) == 1 and ((F0 // pt) * (H0 // ph) * (W0 // pw)) % 8 == 0 and self.text_len % 8 == 0
+
+    def forward(self, x, t, context, seq_len, y=None, *, t_rows=None, context_kv=None):
         r"""Same contract as the reference (model.py:410-497).
 
         x: List[Tensor[C_in, F, H, W]] fp32; t: Tensor[B] or Tensor[B, seq_len]; context: List[Tensor[L<=text_len,
@@ -1028,9 +1005,22 @@ class WanModel(nn.Module):
         forward contains no device -> host round trip (finding the distinct values of a [B, seq_len] tensor needs one), which
         is what makes it capturable in a HIP graph (WanTI2V.denoise builds the table from the sampler's scalar timestep and
         the i2v mask). Only for equal-shape samples (one stacked group).
+
+        context_kv (extension, keyword-only): one `(k bf16 [B*text_len, C], V^T bf16 [C, _lib.vt_cols(B, text_len)])` pair per block - the
+        cross-attention K / V^T of the stacked samples' embedded contexts in the CALLER's buffers (WanCrossAttention._context_kv(out=)
+        fills them), which this forward's cross-attention launches read. `context` is then not read (None will do), nothing is embedded
+        or cached, and set_text_weight is not consulted: the weights are whatever the caller put into the buffers. One stacked group
+        only, and no re-assigned cross-attention forward (a closure takes the context, not its K / V^T).
         """
         if self.model_type == "i2v":
             assert y is not None
+        if context_kv is not None:
+            if len(context_kv) != len(self.blocks):
+                raise ValueError(f"context_kv: {len(context_kv)} (k, V^T) pair(s) for {len(self.blocks)} block(s)")
+            if not self._stacks(x):
+                raise ValueError("context_kv= needs samples of one shape (a single stacked group)")
+            if any("forward" in b.cross_attn.__dict__ for b in self.blocks):
+                raise NotImplementedError("context_kv= with a re-assigned cross_attn.forward: the closure takes the context, not its K / V^T")
         aw = self._adapter_weights
         if aw is not None:
             if len(aw) != len(x):
@@ -1044,7 +1034,7 @@ class WanModel(nn.Module):
             x = [torch.cat([u, v], dim=0) for u, v in zip(x, y)]
         if t_rows is None and t.dim() == 1:  # one timestep per sample (model.py:460-461)
             t = t.view(-1, 1).expand(-1, seq_len)
-        ctx_all, ctx_gen = self._embedded_context(context)
+        ctx_all, ctx_gen = self._embedded_context(context) if context_kv is None else (None, None)
         fr = _freqs_device(self.freqs, dev)
         pt, ph, pw = self.patch_size
         C = self.dim
@@ -1053,11 +1043,7 @@ class WanModel(nn.Module):
         # so each sample's result is bit-identical to running it alone; the benefit is occupancy (e.g. CFG's cond + uncond
         # pair: 4320 attention workgroups instead of 2 x 2160 on 512 slots) and weight reuse. Mixed shapes run one by one.
         xs_in = [u.to(device=dev, dtype=torch.float32).contiguous() for u in x]
-        same = len({tuple(u.shape) for u in xs_in}) == 1
-        if same:   # stacking needs 16-byte aligned per-sample columns in V^T: token count and context length % 8 == 0
-            _, F0, H0, W0 = xs_in[0].shape
-            same = ((F0 // pt) * (H0 // ph) * (W0 // pw)) % 8 == 0 and self.text_len % 8 == 0
-        groups = [list(range(len(xs_in)))] if same else [[i] for i in range(len(xs_in))]
+        groups = [list(range(len(xs_in)))] if self._stacks(xs_in) else [[i] for i in range(len(xs_in))]
         outs = [None] * len(xs_in)
         for idx in groups:
             B = len(idx)
@@ -1085,7 +1071,7 @@ class WanModel(nn.Module):
                 # (i2v: two timesteps per sample - the samples of a twin pair must also agree token by token)
                 twin_t = tid is None or (B > 1 and bool(torch.equal(inv.view(B, L), inv[:L].expand(B, L))))
             e_rows, e0_rows = self._time_rows(tvals.contiguous())
-            ctx = ctx_all[idx[0]] if B == 1 else torch.cat([ctx_all[i] for i in idx], 0)
+            ctx = None if context_kv is not None else ctx_all[idx[0]] if B == 1 else torch.cat([ctx_all[i] for i in idx], 0)
             kv_key = None if ctx_gen is None else (ctx_gen, tuple(idx))
             par = self.sp if (self.sp is not None and self.sp.size > 1) else None
             if par is None:
@@ -1109,7 +1095,7 @@ class WanModel(nn.Module):
                     (tid is None or twin_t))
             # UniVid's dynamic text weight (set_text_weight): the hooked blocks read the row-scaled context, and compute their K / V^T
             # of it in this forward (it changes from forward to forward while the schedule runs; the cache holds the plain one)
-            tw = self._text_weight
+            tw = self._text_weight if context_kv is None else None
             if tw is not None and len(tw[0]) != len(xs_in):
                 raise ValueError(f"set_text_weight was given {len(tw[0])} weight(s); this forward has {len(xs_in)} sample(s)")
             ctx_w = self.weighted_context(ctx_all, idx, tw) if (tw is not None and any(tw[0][i] != 1.0 for i in idx)) else None
@@ -1117,7 +1103,8 @@ class WanModel(nn.Module):
                 hooked = ctx_w is not None and (tw[2] is None or li in tw[2])
                 if par is None or n:
                     blk._run(xs, n, e0_rows, tid, (Fp, Hp, Wp), fr, ctx_w if hooked else ctx, first_block=(li == 0), batch=B, sp=sp_arg,
-                             kv_key=None if hooked else kv_key, twin_rows=(twin and li == 0), s0=idx[0])
+                             kv_key=None if hooked else kv_key, twin_rows=(twin and li == 0), s0=idx[0],
+                             kv=None if context_kv is None else context_kv[li])
                 else:   # a rank without tokens still takes part in the self-attention exchanges
                     blk.self_attn._self_attn_sp(xs.new_empty(0, C).to(BF16), 0, (Fp, Hp, Wp), fr, xs, None, None, B, sp_arg)
             yh = self.head._run(xs, B * n, e_rows, tid) if B * n else xs.new_empty(0, self.head.head.out_features)

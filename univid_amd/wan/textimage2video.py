@@ -128,52 +128,39 @@ class _GraphedPair:
         # here is allowed; the static buffers below are normal tensors, which inference-mode code may write in place.
         # Capture and replay run with the latent's device current: torch's capture stream belongs to the current device, and the
         # kernels follow the device of their tensors (a model on cuda:1 in a process whose current device is cuda:0).
-        tw, model._text_weight = model._text_weight, None      # the capture is the PLAIN forward; weights arrive through apply()
-        try:
-            with torch.inference_mode(False), torch.no_grad(), torch.cuda.device(dev), model.context_cached():
-                self.lat = torch.empty(latent.shape, dtype=latent.dtype, device=dev)
-                n_t = 1 if i2v_mask is None else 2
-                self.tvals = torch.zeros(n_t, dtype=torch.float32, device=dev)
-                if i2v_mask is None:
-                    tid = None
-                else:   # mask 0 (first latent frame) -> row 0 (timestep 0), mask 1 -> row 1 (timestep t); padding tokens never exist here
-                    one = i2v_mask.to(torch.int32)
-                    tid = torch.cat([one, one]).contiguous()
-                self.tid = tid          # the captured kernels read it on every replay: it has to live as long as the graph (until round 5 it was a
-                                        # local - freed after the capture, its memory handed to the next allocation; found as a GPU memory fault)
-                ctx = [context[0], context_null[0]]
-                self.lat.copy_(latent)
-                # eager warm-up on the capture inputs: weight preparation, context cache, scratch buffers, function attributes
-                model([self.lat, self.lat], None, ctx, L, t_rows=(self.tvals, tid, True))
-                torch.cuda.synchronize(dev)
-                # runner-owned copies of the context's cross-attention K / V^T, visible to the model's cache lookups during the capture only
-                kvk = (model._ctx_gen, (0, 1))
-                self.kv, theirs = [], []
-                for b in model.blocks:
-                    kl, vt = b.cross_attn._kv_cache[kvk]
-                    self.kv.append((kl.clone(), vt.clone()))
-                    theirs.append((kl, vt))
-                    b.cross_attn._kv_cache[kvk] = self.kv[-1]
-                emb = model._ctx_cache[2]
-                self.emb = torch.cat([emb[0], emb[1]], 0)   # [2 * text_len, C] bf16: what the K / V projections read (own copy)
-                self.keep = (model._ctx_cache, ctx)       # (the embedded contexts the captured `cat` reads; its result is unused on a cache hit)
-                self.graph = torch.cuda.CUDAGraph()
-                # scratch the forward caches per stream (V^T tiles): tensors born during the capture live in THIS graph's memory pool and
-                # torch's capture stream is shared by all captures, so they must neither be found by a later capture (which would bake an
-                # address of this pool into another graph) nor outlive this runner in a global cache (round-4 advisor finding)
-                snap = _m.scratch_snapshot()
-                try:
-                    with torch.cuda.graph(self.graph):
-                        self.out = model([self.lat, self.lat], None, ctx, L, t_rows=(self.tvals, tid, True))
-                finally:
-                    self.scratch = _m.scratch_take_new(snap)
-                    for b, own in zip(model.blocks, theirs):
-                        if kvk in b.cross_attn._kv_cache:
-                            b.cross_attn._kv_cache[kvk] = own
-        finally:
-            model._text_weight = tw
-        self.state = [(1.0, 1.0)] * len(self.kv)     # per block: the (cond, uncond) text weights its K / V^T buffers were computed with
-        self._scaled = None                          # ((w_cond, w_uncond), rows) -> the row-scaled embedded context of the current prompt
+        with torch.inference_mode(False), torch.no_grad(), torch.cuda.device(dev):
+            self.lat = torch.empty(latent.shape, dtype=latent.dtype, device=dev)
+            n_t = 1 if i2v_mask is None else 2
+            self.tvals = torch.zeros(n_t, dtype=torch.float32, device=dev)
+            if i2v_mask is None:
+                tid = None
+            else:   # mask 0 (first latent frame) -> row 0 (timestep 0), mask 1 -> row 1 (timestep t); padding tokens never exist here
+                one = i2v_mask.to(torch.int32)
+                tid = torch.cat([one, one]).contiguous()
+            self.tid = tid          # the captured kernels read it on every replay: it has to live as long as the graph (until round 5 it was a
+                                    # local - freed after the capture, its memory handed to the next allocation; found as a GPU memory fault)
+            # the context's cross-attention K / V^T of every block, in buffers the runner owns and hands to the forward (context_kv=): the
+            # capture is the PLAIN forward over them; prompts and text weights arrive through refresh() / apply(), from the first fill on
+            Lc, C = model.text_len, model.dim
+            self.kv = [(torch.empty(2 * Lc, C, dtype=torch.bfloat16, device=dev),
+                        torch.zeros(C, _lib.vt_cols(2, Lc), dtype=torch.bfloat16, device=dev)) for _ in model.blocks]
+            self.refresh(context, context_null)     # self.emb, self.state (per block: the (cond, uncond) text weights its buffers hold), self._scaled
+            self.apply()
+            self.lat.copy_(latent)
+            pair = [self.lat, self.lat]
+            # eager warm-up on the capture inputs: weight preparation, scratch buffers, function attributes
+            model(pair, None, None, L, t_rows=(self.tvals, tid, True), context_kv=self.kv)
+            torch.cuda.synchronize(dev)
+            self.graph = torch.cuda.CUDAGraph()
+            # scratch the forward caches per stream (V^T tiles): tensors born during the capture live in THIS graph's memory pool and
+            # torch's capture stream is shared by all captures, so they must neither be found by a later capture (which would bake an
+            # address of this pool into another graph) nor outlive this runner in a global cache (round-4 advisor finding)
+            snap = _m.scratch_snapshot()
+            try:
+                with torch.cuda.graph(self.graph):
+                    self.out = model(pair, None, None, L, t_rows=(self.tvals, tid, True), context_kv=self.kv)
+            finally:
+                self.scratch = _m.scratch_take_new(snap)
 
     def __del__(self):
         # the graph (and its memory pool) must not be destroyed under a replay that is still running: a generation returns without
@@ -190,9 +177,9 @@ class _GraphedPair:
         m = self.model
         with torch.inference_mode(False), torch.no_grad(), torch.cuda.device(self.dev):
             emb = m.embed_context([context[0], context_null[0]])          # [2, text_len, C] bf16
-            self.emb = torch.cat([emb[0], emb[1]], 0)
-        self.state = [None] * len(self.kv)
-        self._scaled = None
+            self.emb = torch.cat([emb[0], emb[1]], 0)                     # [2 * text_len, C] bf16: what the K / V projections read (own copy)
+        self.state = [None] * len(self.kv)           # per block: the (cond, uncond) text weights its K / V^T buffers were computed with
+        self._scaled = None                          # ((w_cond, w_uncond), rows) -> the row-scaled embedded context of the current prompt
 
     def apply(self, text_weight=None):
         """Brings every block's K / V^T buffers to the text weight of the coming forward pair: text_weight = None (plain) or
@@ -222,6 +209,7 @@ class _GraphedPair:
                             _lib.text_weight_rows(self.emb[j * Lc:(j + 1) * Lc], sc[j * Lc:(j + 1) * Lc], min(rows, Lc) if w[j] != 1.0 else 0, w[j])
                         self._scaled = ((w, rows), sc)
                     src = self._scaled[1]
+                _ensure_prepared(m.blocks[li].cross_attn)     # (an adapter attached since the last forward left its module un-prepared)
                 m.blocks[li].cross_attn._context_kv(src, Lc, 2, None, out=self.kv[li])
                 self.state[li] = w if hooked else plain
         return len(stale)
