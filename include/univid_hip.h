@@ -190,6 +190,26 @@ int uv_flash_attn_kernel_name(int Lk, int head_dim, long ldk, long ldvt, int f16
 int uv_flash_attn_plan(int batch, int Lq, int Lk, int H, int head_dim, long ldk, long ldvt, int f16, char* kernel, int len,
                        int* q_blocks, int* n12, int* grid);
 
+/* ---- DiT: self-attention with MXFP8 q / k (opt-in mode; WanModel.set_attn_precision("mxfp8_qk")) ------------------------------
+ * uv_flash_attn_bf16 with q and k in the MXFP8 format stated above (e4m3fn codes, one e8m0 byte per 32 consecutive elements of a row, e =
+ * clamp(exp(amax) - 8, 0, 254), clamp to +-448 then RNE, never a NaN code): replaces attention.py:24-130 as called at model.py:145-150 with
+ * q and k NARROWER than the reference's bf16. The 32-element blocks run along the head dimension: each (row, head) has four scale bytes.
+ * q_codes uint8 [batch*Lq, ldq] with head h at bytes [128 h, 128 h + 128), q_scales uint8 [batch*Lq, ld_qs] with head h at bytes
+ * [4 h, 4 h + 4); k likewise over batch*Lk rows. ldq, ldk >= H*128 and % 16 == 0; ld_qs, ld_ks >= H*4 and % 4 == 0; code pointers 16-byte,
+ * scale pointers 4-byte aligned (codes may be column slices of a wider buffer). vt, out, batch, Lq, Lk, H, softmax_scale: exactly
+ * uv_flash_attn_bf16's meaning and checks (ldvt, the finite pad, Lk % 8 == 0 when batch > 1). head_dim 128 only; anything else is
+ * rejected and nothing is written. S^T = K Q^T runs on v_mfma_scale_f32_32x32x64_f8f6f4 (the scales applied in hardware, products exact,
+ * f32 accumulate); P.V and everything behind S is the bf16 kernels' arithmetic. Every S element is ONE chain: the instruction over
+ * head-dim elements 0..63, then the one over 64..127, into the same accumulator - a query's bits do not depend on the kernel, the
+ * query-block cut, the batch or its neighbours. Code and scale rows at Lk and beyond are never read (the ragged tile clamps both). */
+int uv_flash_attn_mxqk(const void* q_codes, long ldq, const void* q_scales, long ld_qs, const void* k_codes, long ldk, const void* k_scales,
+                       long ld_ks, const void* vt, long ldvt, void* out, long ldo, int batch, int Lq, int Lk, int H, int head_dim,
+                       float softmax_scale, void* stream);
+
+/* The launch plan of uv_flash_attn_mxqk, as uv_flash_attn_plan reports uv_flash_attn_bf16's: flash_attn_mxqk12_kernel (Lk >= 2048; *n12 of the
+ * *q_blocks own 12 units of 32 queries, the others 8) or flash_attn_mxqk4_kernel (blocks of 128 queries, *n12 = 0). Host-only. */
+int uv_flash_attn_mxqk_plan(int batch, int Lq, int Lk, int H, int head_dim, char* kernel, int len, int* q_blocks, int* n12, int* grid);
+
 /* Operator-seam helpers: what flash_attention(q, k, v, ...) (attention.py:24-130) does around the core when it is handed
  * [B, L, N, C] tensors of any float dtype: `half(x)` casts (:59-83), and `.type(out_dtype)` of the result (:130); the
  * transpose produces the V^T operand of uv_flash_attn_* from token-major V rows.
@@ -225,6 +245,15 @@ int uv_rmsnorm_rope(const void* x, long ldx, void* out, long ldo, const float* w
 int uv_rmsnorm_rope_qk(const void* q, void* q_out, const float* q_weight, const void* k, void* k_out, const float* k_weight,
                        long ldx, long ldo, int L, int Ls, int C, int head_dim, float eps, const double* freqs, int F, int Hh,
                        int Ww, int row0, void* stream);
+
+/* uv_rmsnorm_rope_qk with an MXFP8 output (the producer of uv_flash_attn_mxqk; same reference lines plus the quantisation the mode adds):
+ * for q and for k, codes uint8 [L, ldc] (ldc >= C, % 16 == 0) and scales uint8 [L, ld_s] (ld_s >= C / 32, % 4 == 0). The bytes are, bit for
+ * bit, uv_mx_quant_bf16 applied to what uv_rmsnorm_rope_qk writes for the same inputs (stacked samples and row0 included) - that equality
+ * is the definition. head_dim 128 only, C % 128 == 0, C <= 4096. q and k are only read (no in-place form); columns >= C of the codes and
+ * >= C / 32 of the scales are not written. */
+int uv_rmsnorm_rope_qk_mx(const void* q, const float* q_weight, void* q_codes, void* q_scales, const void* k, const float* k_weight,
+                          void* k_codes, void* k_scales, long ldx, long ldc, long ld_s, int L, int Ls, int C, int head_dim, float eps,
+                          const double* freqs, int F, int Hh, int Ww, int row0, void* stream);
 
 /* latent [Cin,F,H,W] f32 -> im2col rows [L, Kpad] bf16, column order (c,kt,kh,kw) = Conv3d.weight.flatten(1)
  * (model.py:378-379, 448-451). */

@@ -25,3 +25,49 @@ ms = s.elapsed_time(e) / n
 import hashlib
 print(f"attention B{B} Lq{L} Lk{Lk}: {ms:.3f} ms {4*B*L*Lk*C/ms/1e9:.1f} TFLOP/s  kernel={_lib.attn_kernel_name(L, Lk, D, B)}  out sha={hashlib.sha1(out.view(torch.int16).cpu().numpy().tobytes()).hexdigest()[:12]}")
 
+
+if "--qk" in sys.argv and sys.argv[sys.argv.index("--qk") + 1] == "mxfp8":
+    # bf16 against the MXFP8 q / k mode (WanModel.set_attn_precision("mxfp8_qk")) on the same random operands, in ONE process: the launches
+    # and their producers (rmsnorm_rope_qk / rmsnorm_rope_qk_mx on the raw projections) alternate round by round, the first round of each is
+    # dropped, medians and the spread (min .. max) of the ROUNDS rounds are printed. The figure that counts is launch + producer.
+    import statistics
+    rounds = int(os.environ.get("ROUNDS", 7))
+    U8 = torch.uint8
+    F, Hh, Ww = 1, 1, 1                                         # RoPE grid: the kernels' cost does not depend on the positions
+    freqs = torch.view_as_real(torch.polar(torch.ones(1024, D // 2, dtype=torch.float64), torch.rand(1024, D // 2, dtype=torch.float64))).contiguous().to(dev)
+    wq, wk = torch.rand(C, device=dev) + 0.5, torch.rand(C, device=dev) + 0.5
+    q_raw, k_raw = torch.randn(B * L, C, device=dev).to(BF16), torch.randn(B * Lk, C, device=dev).to(BF16)
+    qc, kc = torch.empty(B * L, C, dtype=U8, device=dev), torch.empty(B * Lk, C, dtype=U8, device=dev)
+    qs, ks = torch.empty(B * L, C // 32, dtype=U8, device=dev), torch.empty(B * Lk, C // 32, dtype=U8, device=dev)
+    _lib.mx_quant(q, qc, qs); _lib.mx_quant(k, kc, ks)
+    out_mx = torch.empty_like(out)
+    qn, kn = q_raw.clone(), k_raw.clone()
+    assert L == Lk, "the producers run on q and k of one geometry (self-attention)"
+    work = {
+        "attn bf16": lambda: _lib.flash_attn(q, k, vt, out, L, Lk, H, D, 1 / math.sqrt(D), batch=B),
+        "attn mxqk": lambda: _lib.flash_attn_mxqk(qc, qs, kc, ks, vt, out_mx, L, Lk, H, D, 1 / math.sqrt(D), batch=B),
+        "prod bf16": lambda: _lib.rmsnorm_rope_qk(qn, kn, wq, wk, B * L, L, C, D, 1e-6, freqs, (F, Hh, Ww)),      # (in place: re-normalises its own output, same cost)
+        "prod mxqk": lambda: _lib.rmsnorm_rope_qk_mx(q_raw, k_raw, wq, wk, qc, qs, kc, ks, B * L, L, C, D, 1e-6, freqs, (F, Hh, Ww)),
+    }
+    times = {name: [] for name in work}
+    for rnd in range(rounds + 1):
+        for name, fn in work.items():
+            fn(); torch.cuda.synchronize()
+            s.record()
+            for _ in range(n):
+                fn()
+            e.record(); torch.cuda.synchronize()
+            if rnd:
+                times[name].append(s.elapsed_time(e) / n * 1e3)
+    _lib.mx_quant(q, qc, qs); _lib.mx_quant(k, kc, ks)          # (the producer rounds overwrote the codes)
+    work["attn mxqk"](); torch.cuda.synchronize()
+    med = {name: statistics.median(t) for name, t in times.items()}
+    flop = 4 * B * L * Lk * C
+    for name, t in times.items():
+        extra = f"  {flop / med[name] / 1e9:.3f} PFLOP/s" if name.startswith("attn") else ""
+        print(f"{name} B{B} L{L}: median {med[name]:.1f} us  (min {min(t):.1f} max {max(t):.1f}, {len(t)} rounds of {n}){extra}")
+    tot_b, tot_m = med["attn bf16"] + med["prod bf16"], med["attn mxqk"] + med["prod mxqk"]
+    spread = max(times["attn bf16"]) - min(times["attn bf16"]) + max(times["prod bf16"]) - min(times["prod bf16"])
+    print(f"launch + producer: bf16 {tot_b:.1f} us, mxfp8_qk {tot_m:.1f} us, ratio {tot_m / tot_b:.3f} (bf16 spread between rounds {spread:.1f} us); "
+          f"kernel={_lib.attn_mxqk_plan(L, Lk, D, B, H)['kernel']}; rel rms of the mxqk output against bf16 on the same operands "
+          f"{float((out_mx.float() - out.float()).pow(2).mean().sqrt() / out.float().pow(2).mean().sqrt()):.3e}")

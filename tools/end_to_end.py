@@ -2,7 +2,9 @@
 random-init weights, synthetic prompt embeddings): 50 UniPC steps with CFG + VAE decode, per stage, for the exact-f32 VAE and the
 f32-grade bf16x6 / f16x3 modes - at the bench size (49 frames of 704 x 1280) and at UniVid's own default workload (121 frames of
 704 x 1280, inference.py:48-50).   env: STEPS (50), FRAMES ("49,121"), PRECS ("fp32,bf16x6,f16x3")
-    --ffn-precision bf16|mxfp8   the DiT's FFN projections in the opt-in MXFP8 mode (WanModel.set_ffn_precision)"""
+    --ffn-precision bf16|mxfp8   the DiT's FFN projections in the opt-in MXFP8 mode (WanModel.set_ffn_precision)
+    --attn-precision bf16|mxfp8_qk   the DiT's self-attention q / k in the opt-in MXFP8 mode (WanModel.set_attn_precision)
+    --attn-ab ROUNDS   instead of the table: ms per denoise step with the self-attention in bf16 against mxfp8_qk, alternating in one process"""
 import os, sys, time, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from univid_amd import _lib
@@ -18,7 +20,9 @@ m = m.eval().requires_grad_(False)
 m.init_weights(0)
 ffn_precision = sys.argv[sys.argv.index("--ffn-precision") + 1] if "--ffn-precision" in sys.argv else "bf16"
 m.set_ffn_precision(ffn_precision)
-print(f"ffn_precision {ffn_precision}", flush=True)
+attn_precision = sys.argv[sys.argv.index("--attn-precision") + 1] if "--attn-precision" in sys.argv else "bf16"
+m.set_attn_precision(attn_precision)
+print(f"ffn_precision {ffn_precision} attn_precision {attn_precision}", flush=True)
 m.prepare()
 g = torch.Generator(device=dev).manual_seed(1)
 pe = [torch.randn(40, 4096, device=dev, generator=g) * 0.1]
@@ -32,10 +36,32 @@ def clock(fn):
 
 frames = [int(f) for f in os.environ.get("FRAMES", "49,121").split(",")]
 precs = os.environ.get("PRECS", "fp32,bf16x6,f16x3").split(",")
+if "--attn-ab" in sys.argv:
+    # --attn-ab ROUNDS: the denoise loop alone (t2v, decode=False) at the first FRAMES entry with the self-attention in "bf16" and in "mxfp8_qk",
+    # alternating round by round in THIS process (each switch re-prepares and re-captures: its warm-up generation is not timed), the first
+    # round dropped; medians and the spread of the rounds. --ffn-precision applies to both sides.
+    import statistics
+    rounds, F = int(sys.argv[sys.argv.index("--attn-ab") + 1]), frames[0]
+    pipe = WanTI2V(model=m, vae=Wan2_2_VAE(device=dev, seed=0, precision="f16x3"), device=dev)
+    ms = {"bf16": [], "mxfp8_qk": []}
+    for rnd in range(rounds + 1):
+        for mode in ms:
+            m.set_attn_precision(mode)
+            with torch.no_grad():
+                pipe.t2v("", size=(1280, 704), frame_num=F, sampling_steps=2, seed=7, prompt_embeds=pe, negative_prompt_embeds=ne, decode=False)
+                _, t = clock(lambda: pipe.t2v("", size=(1280, 704), frame_num=F, sampling_steps=steps, seed=7, prompt_embeds=pe,
+                                              negative_prompt_embeds=ne, decode=False))
+            if rnd:
+                ms[mode].append(t / steps * 1e3)
+    med = {k: statistics.median(v) for k, v in ms.items()}
+    for k, v in ms.items():
+        print(f"{F} frames, ffn {ffn_precision}, attn {k:8s}: median {med[k]:.2f} ms/step (min {min(v):.2f} max {max(v):.2f}, {len(v)} rounds of {steps} steps)", flush=True)
+    print(f"mxfp8_qk / bf16 = {med['mxfp8_qk'] / med['bf16']:.4f} (bf16 spread {max(ms['bf16']) - min(ms['bf16']):.2f} ms)", flush=True)
+    sys.exit(0)
 for F in frames:
     for prec in precs:
         vae = Wan2_2_VAE(device=dev, seed=0, precision=prec)
-        pipe = WanTI2V(model=m, vae=vae, device=dev, ffn_precision=ffn_precision)
+        pipe = WanTI2V(model=m, vae=vae, device=dev, ffn_precision=ffn_precision, attn_precision=attn_precision)
         with torch.no_grad():
             # warm-up of both loops (2 steps each): one-time costs - the VAE's weight preparation, the HIP-graph captures of the t2v and i2v
             # forward pairs (one per latent shape and mode; a NEW PROMPT does not recapture) - stay out of the timed generations

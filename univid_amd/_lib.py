@@ -45,6 +45,8 @@ SIGNATURES = {
     "uv_flash_attn_bf16_qnorm": [_P, _L, _P, _L, _P, _L, _P, _L, _I, _I, _I, _I, _I, _F, _P, _P, _P],
     "uv_flash_attn_bf16": [_P, _L, _P, _L, _P, _L, _P, _L, _I, _I, _I, _I, _I, _F, _P],
     "uv_flash_attn_f16": [_P, _L, _P, _L, _P, _L, _P, _L, _I, _I, _I, _I, _I, _F, _P],
+    "uv_flash_attn_mxqk": [_P, _L, _P, _L, _P, _L, _P, _L, _P, _L, _P, _L, _I, _I, _I, _I, _I, _F, _P],
+    "uv_flash_attn_mxqk_plan": [_I, _I, _I, _I, _I, _c.c_char_p, _I, _c.POINTER(_I), _c.POINTER(_I), _c.POINTER(_I)],
     "uv_flash_attn_kernel_name": [_I, _I, _L, _L, _I, _c.c_char_p, _I],
     "uv_flash_attn_plan": [_I, _I, _I, _I, _I, _L, _L, _I, _c.c_char_p, _I, _c.POINTER(_I), _c.POINTER(_I), _c.POINTER(_I)],
     "uv_transpose_16": [_P, _L, _P, _L, _I, _I, _I, _P],
@@ -58,6 +60,7 @@ SIGNATURES = {
     "uv_interp_linear_rows_bf16": [_P, _L, _P, _L, _I, _I, _I, _P],
     "uv_l2_normalize_rows_f32": [_P, _L, _P, _L, _I, _I, _F, _P],
     "uv_rmsnorm_rope": [_P, _L, _P, _L, _P, _I, _I, _I, _F, _P, _I, _I, _I, _I, _P],
+    "uv_rmsnorm_rope_qk_mx": [_P, _P, _P, _P, _P, _P, _P, _P, _L, _L, _L, _I, _I, _I, _I, _F, _P, _I, _I, _I, _I, _P],
     "uv_rmsnorm_rope_qk": [_P, _P, _P, _P, _P, _P, _L, _L, _I, _I, _I, _I, _F, _P, _I, _I, _I, _I, _P],
     "uv_patchify_bf16": [_P, _P, _L, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     "uv_unpatchify_f32": [_P, _L, _P, _I, _I, _I, _I, _I, _I, _I, _P],
@@ -518,6 +521,30 @@ def attn_plan(Lq, Lk, D, batch=1, H=1, f16=False, ldk=None, ldvt=None):
     return dict(kernel=buf.value.decode(), q_blocks=qb.value, n12=n12.value, grid=grid.value)
 
 
+def flash_attn_mxqk(q_codes, q_scales, k_codes, k_scales, vt, out, Lq, Lk, H, D, scale, batch=1):
+    """`flash_attn` with MXFP8 q / k (include/univid_hip.h): q_codes uint8 [batch*Lq, >= H*128] / q_scales uint8 [batch*Lq, >= H*4] (head h
+    at bytes 128 h / 4 h), k likewise over batch*Lk rows (`rmsnorm_rope_qk_mx` or `mx_quant` write them); vt / out bf16 as for `flash_attn`.
+    head_dim 128 only."""
+    C = H * D
+    _check("flash_attn_mxqk", (q_codes, "q_codes", U8, C, batch * Lq), (q_scales, "q_scales", U8, C // 32, batch * Lq),
+           (k_codes, "k_codes", U8, C, batch * Lk), (k_scales, "k_scales", U8, C // 32, batch * Lk),
+           (vt, "vt", BF16, vt_cols(batch, Lk), C), (out, "out", BF16, C, batch * Lq))
+    call("uv_flash_attn_mxqk", ptr(q_codes), q_codes.stride(-2), ptr(q_scales), q_scales.stride(-2), ptr(k_codes), k_codes.stride(-2),
+         ptr(k_scales), k_scales.stride(-2), ptr(vt), vt.stride(-2), ptr(out), out.stride(-2), batch, Lq, Lk, H, D, float(scale), stream_ptr(),
+         flops=4 * batch * Lq * Lk * H * D)
+    return out
+
+
+def attn_mxqk_plan(Lq, Lk, D=128, batch=1, H=1):
+    """Launch plan of `flash_attn_mxqk` for this geometry, as `attn_plan` reports `flash_attn`'s."""
+    buf = ctypes.create_string_buffer(96)
+    qb, n12, grid = _I(0), _I(0), _I(0)
+    lib = load()
+    if lib.uv_flash_attn_mxqk_plan(batch, Lq, Lk, H, D, buf, 96, ctypes.byref(qb), ctypes.byref(n12), ctypes.byref(grid)) != 0:
+        raise UnividHipError(lib.uv_last_error().decode())
+    return dict(kernel=buf.value.decode(), q_blocks=qb.value, n12=n12.value, grid=grid.value)
+
+
 def conv_plan(prec, Tout, Hout, Wout, Hin, Win, Cin, Cout, kt, kh, kw, st=1, sh=1, sw=1, ph=0, pw=0, up=0, interleave=0):
     """Launch plan of a uv_conv3d_* call of this geometry on the current device - 256 CUs without one - under the current OPT_CONV_HALO:
     dict(kernel=name, tiles_m=row tiles or pixel patches, tiles_n=output-channel tiles). prec: 0 f32, 1 / 2 bf16x3 without / with
@@ -581,6 +608,20 @@ def rmsnorm_rope_qk(q, k, q_weight, k_weight, L, Ls, C, D, eps, freqs, grid, row
         raise UnividHipError("rmsnorm_rope_qk: q and k must have the same row stride")
     call("uv_rmsnorm_rope_qk", ptr(q), ptr(q), ptr(q_weight), ptr(k), ptr(k), ptr(k_weight), q.stride(-2), q.stride(-2), L, Ls, C, D,
          float(eps), ptr(freqs), int(grid[0]), int(grid[1]), int(grid[2]), int(row0), stream_ptr())
+
+
+def rmsnorm_rope_qk_mx(q, k, q_weight, k_weight, q_codes, q_scales, k_codes, k_scales, L, Ls, C, D, eps, freqs, grid, row0=0):
+    """`rmsnorm_rope_qk` with an MXFP8 store: q / k bf16 [L, C] are only READ; codes uint8 [L, >= C] and scales uint8 [L, >= C / 32] receive,
+    bit for bit, `mx_quant` of what `rmsnorm_rope_qk` would write. head_dim 128 only."""
+    _check("rmsnorm_rope_qk_mx", (q, "q", BF16, C, L), (k, "k", BF16, C, L), (q_weight, "q_weight", F32, C), (k_weight, "k_weight", F32, C),
+           (q_codes, "q_codes", U8, C, L), (q_scales, "q_scales", U8, C // 32, L), (k_codes, "k_codes", U8, C, L),
+           (k_scales, "k_scales", U8, C // 32, L), (freqs, "freqs", torch.float64, 1024 * D, None, True))
+    if q.stride(-2) != k.stride(-2) or q_codes.stride(-2) != k_codes.stride(-2) or q_scales.stride(-2) != k_scales.stride(-2):
+        raise UnividHipError("rmsnorm_rope_qk_mx: q / k, their codes and their scales must each share one row stride")
+    call("uv_rmsnorm_rope_qk_mx", ptr(q), ptr(q_weight), ptr(q_codes), ptr(q_scales), ptr(k), ptr(k_weight), ptr(k_codes), ptr(k_scales),
+         q.stride(-2), q_codes.stride(-2), q_scales.stride(-2), L, Ls, C, D, float(eps), ptr(freqs), int(grid[0]), int(grid[1]), int(grid[2]),
+         int(row0), stream_ptr())
+    return q_codes, q_scales, k_codes, k_scales
 
 
 def text_weight_rows(x, out, n_scaled, w):

@@ -1,4 +1,4 @@
-// The flash-attention kernels' shared host and device pieces (attention.hip; tools/diag/attn_pw4.hip): the argument block and constants,
+// The flash-attention kernels' shared host and device pieces (attention.hip; attention_mx.hip; tools/diag/attn_pw4.hip): the argument block and constants,
 // plan_attn - the ONE place that decides which kernel serves a call, on what query-block cut and on what grid -, and the device code the
 // kernels have in common.
 #pragma once
@@ -23,9 +23,9 @@ struct AttnArgs {
     const float* q_w;
 };
 
-enum AttnKernel { ATT_FWD12 = 0, ATT_FWD3 = 1, ATT_FWD_D128 = 2, ATT_FWD_D64 = 3 };
+enum AttnKernel { ATT_FWD12 = 0, ATT_FWD3 = 1, ATT_FWD_D128 = 2, ATT_FWD_D64 = 3, ATT_MXQK12 = 4, ATT_MXQK4 = 5 };
 static const char* const kAttnKernelName[] = {"flash_attn_fwd12_kernel", "flash_attn_fwd3_kernel", "flash_attn_fwd_kernel<128>",
-                                              "flash_attn_fwd_kernel<64>"};
+                                              "flash_attn_fwd_kernel<64>", "flash_attn_mxqk12_kernel", "flash_attn_mxqk4_kernel"};
 struct AttnPlan {
     int kernel;            // AttnKernel
     int q_blocks, n12;     // query blocks per (sample, head); of them the 12-unit ones (flash_attn_fwd12_kernel only, else 0)
@@ -92,6 +92,15 @@ static inline AttnPlan plan_attn(int batch, int Lq, int Lk, int H, int head_dim,
     memo[memo_next] = Memo{nwu, nbh, ncus, best12, best8};
     memo_next = (memo_next + 1) & 7;
     return cut(best12, best8);
+}
+
+// The MXFP8-q/k kernels (attention_mx.hip; head_dim 128, 64-bit piece addresses: no leading-dimension limit): plan_attn's decision for the bf16
+// problem of the same shape - the same Lk threshold, query-block cut and grid - with the kernel of the same size. plan_attn stays the one place
+// that chooses.
+static inline AttnPlan plan_attn_mxqk(int batch, int Lq, int Lk, int H, int ncus, int force_cut) {
+    AttnPlan plan = plan_attn(batch, Lq, Lk, H, 128, 8, 8, false, ncus, force_cut);
+    plan.kernel = plan.kernel == ATT_FWD12 ? ATT_MXQK12 : ATT_MXQK4;
+    return plan;
 }
 
 // ---- device code the kernels share

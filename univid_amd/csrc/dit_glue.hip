@@ -199,6 +199,8 @@ struct RmsRopeArgs {
     int nf, nh, nw;       // complex columns per axis
     int row0;             // global token index of row 0 (sequence-parallel shards), RoPE positions only
     float eps;
+    // MX instantiations (uv_rmsnorm_rope_qk_mx): out / out2 are e4m3fn CODE rows (ldo in bytes) and these the e8m0 scale rows beside them
+    uint8_t* sc; uint8_t* sc2; long ld_s;
 };
 
 // One wave walks RPW consecutive token rows; the norm weight of its columns stays in registers. A lane's 8-element
@@ -206,14 +208,18 @@ struct RmsRopeArgs {
 // the factors are fetched once per row instead of once per chunk.
 // EXACT: C == MAXV * 512, every lane owns MAXV full chunks: no per-chunk predicates, so a row's loads are ONE burst behind ONE wait
 // (with the predicates hipcc branches around every chunk's load and waits vmcnt(0) chunk by chunk).
-template <int MAXV, int RPW, bool EXACT = false>
+// MX: the store is uv_mx_quant_bf16's (gemm_mx.hip, the rule of include/univid_hip.h) applied to the bf16 values the plain form would write - the
+// same operations on the same numbers, so the bytes equal the two-pass form's. A lane's 8 columns are a quarter of an MX block: amax across
+// the 4 lanes that hold the block, the scale byte, the explicit clamp, cvt_pk_fp8; the four scale bytes of a head (16 lanes) leave as one dword.
+// C % 128 == 0 there, so whole 16-lane groups are live or idle.
+template <int MAXV, int RPW, bool EXACT = false, bool MX = false>
 __global__ __launch_bounds__(256) void rmsnorm_rope_kernel(RmsRopeArgs p) {
     const int lane = threadIdx.x & 63;
     // the wave index as a provably uniform value: the row, its RoPE position (three integer divisions) and the rope / no-rope branch
     // then live on the scalar unit instead of costing vector instructions and registers in every lane
     const int row0 = (blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6)) * RPW;
     if (row0 >= p.L) return;
-    if (blockIdx.y == 1) { p.x = p.x2; p.out = p.out2; p.weight = p.weight2; }
+    if (blockIdx.y == 1) { p.x = p.x2; p.out = p.out2; p.weight = p.weight2; p.sc = p.sc2; }
     const int nv = EXACT ? MAXV : p.C >> 9;      // 8-element chunks per lane (64 lanes * 8 = 512)
     const int rem = EXACT ? 0 : (p.C & 511) >> 3;   // leftover chunks (C % 512 != 0, e.g. C = 256)
     const int half = p.D >> 1;
@@ -282,8 +288,9 @@ __global__ __launch_bounds__(256) void rmsnorm_rope_kernel(RmsRopeArgs p) {
 #pragma unroll
         for (int i = 0; i < MAXV; ++i) {
             const bool on = EXACT || (i < nv) || (i == nv && lane < rem);
+            const int c0 = (i * 64 + lane) * 8;
+            u32x4 o = {0u, 0u, 0u, 0u};
             if (on) {
-                const int c0 = (i * 64 + lane) * 8;
                 float y[8];
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
@@ -318,8 +325,39 @@ __global__ __launch_bounds__(256) void rmsnorm_rope_kernel(RmsRopeArgs p) {
                         y[2 * e + 1] = __builtin_fmaf(a, ih, __builtin_fmaf(b, rh, __builtin_fmaf(a, il, __fmul_rn(b, rl))));
                     }
                 }
-                u32x4 o = {pack_bf2(y[0], y[1]), pack_bf2(y[2], y[3]), pack_bf2(y[4], y[5]), pack_bf2(y[6], y[7])};
-                *(u32x4*)(p.out + (long)row * p.ldo + c0) = o;
+                o = (u32x4){pack_bf2(y[0], y[1]), pack_bf2(y[2], y[3]), pack_bf2(y[4], y[5]), pack_bf2(y[6], y[7])};
+                if constexpr (!MX) *(u32x4*)(p.out + (long)row * p.ldo + c0) = o;
+            }
+            if constexpr (MX) {      // (the shuffles run on every lane; an idle lane carries zeros)
+                float v[8];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    v[2 * e] = __builtin_bit_cast(float, o[e] << 16);
+                    v[2 * e + 1] = __builtin_bit_cast(float, o[e] & 0xffff0000u);
+                }
+                uint32_t amax = 0;
+#pragma unroll
+                for (int e = 0; e < 8; ++e) amax = max(amax, __builtin_bit_cast(uint32_t, v[e]) & 0x7fffffffu);
+                amax = max(amax, (uint32_t)__shfl_xor((int)amax, 1, 64));
+                amax = max(amax, (uint32_t)__shfl_xor((int)amax, 2, 64));
+                const int eb = max((int)(amax >> 23) - 8, 0);
+                const float inv = __builtin_bit_cast(float, (uint32_t)(254 - eb) << 23);
+                uint32_t w[2];
+#pragma unroll
+                for (int e = 0; e < 2; ++e) {
+                    float s[4];
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) s[j] = fminf(fmaxf(__fmul_rn(v[4 * e + j], inv), -448.f), 448.f);
+                    int pk = __builtin_amdgcn_cvt_pk_fp8_f32(s[0], s[1], 0, false);
+                    pk = __builtin_amdgcn_cvt_pk_fp8_f32(s[2], s[3], pk, true);
+                    w[e] = (uint32_t)pk;
+                }
+                const int g0 = lane & ~15;
+                const uint32_t e1 = (uint32_t)__shfl(eb, g0 + 4, 64), e2 = (uint32_t)__shfl(eb, g0 + 8, 64), e3 = (uint32_t)__shfl(eb, g0 + 12, 64);
+                if (on) {
+                    *(u32x2*)((uint8_t*)p.out + (long)row * p.ldo + c0) = (u32x2){w[0], w[1]};
+                    if ((lane & 15) == 0) *(uint32_t*)(p.sc + (long)row * p.ld_s + (c0 >> 5)) = (uint32_t)eb | e1 << 8 | e2 << 16 | e3 << 24;
+                }
             }
         }
     }
@@ -327,7 +365,8 @@ __global__ __launch_bounds__(256) void rmsnorm_rope_kernel(RmsRopeArgs p) {
 
 static int rmsnorm_rope_launch(const char* name, const void* x, void* out, const float* weight, const void* x2, void* out2,
                                const float* weight2, long ldx, long ldo, int L, int Ls, int C, int head_dim, float eps,
-                               const double* freqs, int F, int Hh, int Ww, int row0, void* stream) {
+                               const double* freqs, int F, int Hh, int Ww, int row0, void* stream, void* q_sc = nullptr, void* k_sc = nullptr,
+                               long ld_s = 0) {
     UV_CHECK_ARG(x && out && weight && L > 0, "%s: null pointer / empty", name);
     UV_CHECK_ARG(C % 8 == 0 && C <= 8192, "%s: C=%d must be a multiple of 8 and <= 8192", name, C);
     UV_CHECK_ARG(head_dim % 8 == 0 && C % head_dim == 0, "%s: bad head_dim %d", name, head_dim);
@@ -339,6 +378,7 @@ static int rmsnorm_rope_launch(const char* name, const void* x, void* out, const
     a.x = (const bf16_t*)x; a.ldx = ldx; a.out = (bf16_t*)out; a.ldo = ldo; a.weight = weight; a.freqs = freqs;
     a.x2 = (const bf16_t*)x2; a.out2 = (bf16_t*)out2; a.weight2 = weight2;
     a.L = L; a.Ls = Ls; a.C = C; a.D = head_dim; a.F = F; a.Hh = Hh; a.Ww = Ww; a.eps = eps; a.row0 = row0;
+    a.sc = (uint8_t*)q_sc; a.sc2 = (uint8_t*)k_sc; a.ld_s = ld_s;
     const int c = head_dim / 2;  // model.py:43  split [c - 2*(c//3), c//3, c//3]
     a.nh = c / 3; a.nw = c / 3; a.nf = c - 2 * (c / 3);
     const int rpw = L >= 4096 ? 4 : 1;
@@ -347,6 +387,19 @@ static int rmsnorm_rope_launch(const char* name, const void* x, void* out, const
     hipStream_t st = (hipStream_t)stream;
     // whole 512-column chunks and RoPE factors shared by a lane's chunks (or no RoPE): the predicate-free instantiations
     const bool exact = C % 512 == 0 && (!freqs || 512 % head_dim == 0);
+    if (q_sc) {       // the MXFP8 store (head_dim 128, C <= 4096: checked by the entry point)
+        if (rpw == 4) {
+            if (exact && chunks == 6) hipLaunchKernelGGL((rmsnorm_rope_kernel<6, 4, true, true>), grid, block, 0, st, a);
+            else if (chunks <= 2) hipLaunchKernelGGL((rmsnorm_rope_kernel<2, 4, false, true>), grid, block, 0, st, a);
+            else hipLaunchKernelGGL((rmsnorm_rope_kernel<8, 4, false, true>), grid, block, 0, st, a);
+        } else {
+            if (exact && chunks == 6) hipLaunchKernelGGL((rmsnorm_rope_kernel<6, 1, true, true>), grid, block, 0, st, a);
+            else if (chunks <= 2) hipLaunchKernelGGL((rmsnorm_rope_kernel<2, 1, false, true>), grid, block, 0, st, a);
+            else hipLaunchKernelGGL((rmsnorm_rope_kernel<8, 1, false, true>), grid, block, 0, st, a);
+        }
+        UV_CHECK_LAUNCH(name);
+        return 0;
+    }
     if (rpw == 4) {
         if (exact && chunks == 2) hipLaunchKernelGGL((rmsnorm_rope_kernel<2, 4, true>), grid, block, 0, st, a);
         else if (exact && chunks == 6) hipLaunchKernelGGL((rmsnorm_rope_kernel<6, 4, true>), grid, block, 0, st, a);   // the DiT's 3072
@@ -382,6 +435,26 @@ extern "C" int uv_rmsnorm_rope_qk(const void* q, void* q_out, const float* q_wei
     UV_CHECK_ARG(Ls > 0 && L % Ls == 0, "uv_rmsnorm_rope_qk: L=%d must be a whole number of samples of Ls=%d rows", L, Ls);
     return rmsnorm_rope_launch("uv_rmsnorm_rope_qk", q, q_out, q_weight, k, k_out, k_weight, ldx, ldo, L, Ls, C, head_dim, eps,
                                freqs, F, Hh, Ww, row0, stream);
+}
+
+// uv_rmsnorm_rope_qk with an MXFP8 store: the producer of uv_flash_attn_mxqk's q and k (WanModel.set_attn_precision("mxfp8_qk")). No in-place
+// form (the codes are half as wide as the input): q and k are only read.
+extern "C" int uv_rmsnorm_rope_qk_mx(const void* q, const float* q_weight, void* q_codes, void* q_scales, const void* k, const float* k_weight,
+                                     void* k_codes, void* k_scales, long ldx, long ldc, long ld_s, int L, int Ls, int C, int head_dim,
+                                     float eps, const double* freqs, int F, int Hh, int Ww, int row0, void* stream) {
+    const char* name = "uv_rmsnorm_rope_qk_mx";
+    UV_CHECK_ARG(q && k && q_codes && k_codes && q_weight && k_weight, "%s: null pointer", name);
+    UV_CHECK_ARG(q_scales && k_scales, "%s: null scale pointer", name);
+    UV_CHECK_ARG(head_dim == 128, "%s: head_dim %d unsupported (128 only)", name, head_dim);
+    UV_CHECK_ARG(C > 0 && C % 128 == 0 && C <= 4096, "%s: C=%d must be a multiple of 128 and <= 4096", name, C);
+    UV_CHECK_ARG(Ls > 0 && L > 0 && L % Ls == 0, "%s: L=%d must be a whole number of samples of Ls=%d rows", name, L, Ls);
+    UV_CHECK_ARG(ldx >= C && ldc >= C && ldc % 16 == 0, "%s: ldx / ldc must be >= C, ldc a multiple of 16 bytes", name);
+    UV_CHECK_ARG(ld_s >= C / 32 && ld_s % 4 == 0, "%s: ld_s must be >= C / 32 = %d and a multiple of 4 (ld_s=%ld)", name, C / 32, ld_s);
+    UV_CHECK_ARG((((uintptr_t)q | (uintptr_t)k | (uintptr_t)q_codes | (uintptr_t)k_codes | (uintptr_t)q_weight | (uintptr_t)k_weight) & 15) == 0,
+                 "%s: q / k / codes / weights must be 16-byte aligned", name);
+    UV_CHECK_ARG((((uintptr_t)q_scales | (uintptr_t)k_scales) & 3) == 0, "%s: scale pointers must be 4-byte aligned", name);
+    return rmsnorm_rope_launch(name, q, q_codes, q_weight, k, k_codes, k_weight, ldx, ldc, L, Ls, C, head_dim, eps, freqs, F, Hh, Ww, row0,
+                               stream, q_scales, k_scales, ld_s);
 }
 
 // ------------------------------------------------------------------------------------------------

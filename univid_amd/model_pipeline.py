@@ -54,6 +54,7 @@ class CrossAttentionConfig:
     lora_target_strategy: str = "your_method_here"
     lora_merge: bool = True       # CrossAttentionFusionPipeline.load_lora: fold the adapter into the dense weights (False: attach it un-merged)
     ffn_precision: str = "bf16"   # "mxfp8": the DiT's ffn.0 / ffn.2 on MXFP8 operands (WanModel.set_ffn_precision), an opt-in fast mode
+    attn_precision: str = "bf16"  # "mxfp8_qk": the DiT's self-attention q / k as MXFP8 (WanModel.set_attn_precision), an opt-in experimental mode
     guidance_strength: float = 1.0
     bagel_cross_attn_layers: List[int] = None
     freeze_bagel: bool = True
@@ -380,6 +381,9 @@ class CrossAttentionFusionPipeline:
         ffn_precision = getattr(config, "ffn_precision", "bf16")
         if ffn_precision != "bf16" and hasattr(self.dit_model, "set_ffn_precision") and ffn_precision != self.dit_model.ffn_precision:
             self.dit_model.set_ffn_precision(ffn_precision)
+        attn_precision = getattr(config, "attn_precision", "bf16")
+        if attn_precision != "bf16" and hasattr(self.dit_model, "set_attn_precision") and attn_precision != self.dit_model.attn_precision:
+            self.dit_model.set_attn_precision(attn_precision)
         self.vae_model = wan_pipeline.vae
         self.text_encoder = wan_pipeline.text_encoder
         # native_text_weight=False: the reference's closures on the model's generic path (kept as the comparison the tests and bench use)
@@ -407,7 +411,8 @@ class CrossAttentionFusionPipeline:
         self._check_gpu("wan_gpu")
         try:
             return WanTI2V(config=wan_config, checkpoint_dir=path, device_id=self.config.wan_gpu, rank=0, t5_fsdp=False, dit_fsdp=False,
-                           use_sp=False, ffn_precision=getattr(self.config, "ffn_precision", "bf16"))
+                           use_sp=False, ffn_precision=getattr(self.config, "ffn_precision", "bf16"),
+                           attn_precision=getattr(self.config, "attn_precision", "bf16"))
         except Exception as e:
             raise RuntimeError(f"Wan2.2 initialization failed: {e}") from e
 

@@ -84,6 +84,18 @@ class _PreparedMx:
         self.b = p.b
 
 
+ATTN_PRECISIONS = ("bf16", "mxfp8_qk")
+
+
+def _check_attn_precision(mode, head_dim):
+    """set_attn_precision's guards, on one self-attention's geometry: raises before any state changes."""
+    if mode not in ATTN_PRECISIONS:
+        raise ValueError(f"attn_precision {mode!r}: one of {ATTN_PRECISIONS}")
+    if mode == "mxfp8_qk" and head_dim != 128:
+        raise ValueError(f"attn_precision 'mxfp8_qk' needs head_dim 128 (one MX scale dword per head and row, two 64-element steps of the "
+                         f"block-scaled matrix instruction); this model has head_dim {head_dim}")
+
+
 def _check_ffn_precision(mode, dim, ffn_dim, ffn):
     """Everything that can refuse a mode, before any state changes."""
     if mode not in FFN_PRECISIONS:
@@ -228,6 +240,7 @@ class WanSelfAttention(nn.Module):
         self._prep = None
         self._slots = {}
         self._kv_cache = {}
+        self.attn_precision = "bf16"     # WanModel.set_attn_precision: instance state, never a module global
 
     _groups = {"qkv": ("q", "k", "v"), "o": ("o",)}      # projections by the activation they read (one LoRA slot each)
 
@@ -258,9 +271,17 @@ class WanSelfAttention(nn.Module):
         M = batch * L
         vt = _vt_scratch("vt", C, batch, L, h.device)
         ql, kl = self._qkv(h, M, L, s0, vt)
+        att = _act_buf(M, C, (self._slots["o"],), h.device)
+        if self.attn_precision == "mxfp8_qk":
+            # q and k leave the norm + RoPE pass as MXFP8 codes + scales (fresh buffers: no in-place form), S = K Q^T on the block-scaled
+            # matrix instruction; V^T, P.V and the output stay bf16
+            qc, kc = (torch.empty(M, C, dtype=torch.uint8, device=h.device) for _ in range(2))
+            qs, ks = (torch.empty(M, C // 32, dtype=torch.uint8, device=h.device) for _ in range(2))
+            _lib.rmsnorm_rope_qk_mx(ql, kl, self.norm_q.weight, self.norm_k.weight, qc, qs, kc, ks, M, L, C, D, self.eps, freqs, grid)
+            _lib.flash_attn_mxqk(qc, qs, kc, ks, vt, att, L, Lk, H, D, 1.0 / math.sqrt(D), batch=batch)
+            return _slotted(att, C, self._slots["o"], M, L, s0)
         # q and k of every stacked sample in one launch (RoPE positions restart with every sample)
         _lib.rmsnorm_rope_qk(ql, kl, self.norm_q.weight, self.norm_k.weight, M, L, C, D, self.eps, freqs, grid)
-        att = _act_buf(M, C, (self._slots["o"],), h.device)
         _lib.flash_attn(ql, kl, vt, att, L, Lk, H, D, 1.0 / math.sqrt(D), batch=batch)
         return _slotted(att, C, self._slots["o"], M, L, s0)
 
@@ -278,6 +299,9 @@ class WanSelfAttention(nn.Module):
         """Ulysses form (distributed/sequence_parallel.py:147-176, ulysses.py:9-47): projections, RMSNorm and RoPE on the
         rank's n tokens of each sample; q/k/V^T exchanged to [all tokens, heads/p]; attention over the whole sequence for
         the rank's heads; output exchanged back; o-projection + gated residual on the rank's tokens."""
+        if self.attn_precision != "bf16":
+            raise NotImplementedError(f"attn_precision {self.attn_precision!r} is not built for the sequence-parallel forward (the Ulysses "
+                                      f"exchange carries bf16 q / k): set_attn_precision('bf16') or run without sequence parallelism")
         par, Lt, r0 = sp
         C, H, D = self.dim, self.num_heads, self.head_dim
         P = par.size
@@ -439,6 +463,12 @@ class WanAttentionBlock(nn.Module):
         _check_ffn_precision(mode, self.dim, self.ffn_dim, self.ffn)
         self.ffn_precision = mode
         self._prep = None
+
+    def set_attn_precision(self, mode):
+        """"bf16" (default) or "mxfp8_qk": this block's self-attention with MXFP8 q / k (WanModel.set_attn_precision states the mode). No
+        prepared weight depends on it."""
+        _check_attn_precision(mode, self.self_attn.head_dim)
+        self.self_attn.attn_precision = mode
 
     def _prepare_ffn(self):
         if self.ffn_precision == "mxfp8":
@@ -729,6 +759,7 @@ class WanModel(nn.Module):
         self.sp = None   # SeqParallel when Ulysses sequence parallelism is enabled (enable_sequence_parallel)
         self._text_weight = None  # (per-sample weights, rows, layers | None): set_text_weight
         self.ffn_precision = "bf16"  # set_ffn_precision
+        self.attn_precision = "bf16"  # set_attn_precision
         self.dedup_twins = True   # block 0's self-attention half once for samples that enter with identical rows (the CFG pair); A/B switch
         self.register_load_state_dict_post_hook(lambda m, _k: m.invalidate())
 
@@ -789,6 +820,21 @@ class WanModel(nn.Module):
         self.ffn_precision = mode
         for b in self.blocks:
             b.ffn_precision = mode
+        self.invalidate()
+
+    def set_attn_precision(self, mode):
+        """Arithmetic of S = Q K^T in every block's SELF-attention: "bf16" (default; like for like with the reference) or "mxfp8_qk" - q and k
+        leave the RMSNorm + RoPE pass as OCP MXFP8 (e4m3 elements, one power-of-two scale per 32 head-dim elements) and S runs on the
+        block-scaled matrix instruction: a labelled, opt-in mode NARROWER than the reference's arithmetic (README). The softmax, P.V, V^T
+        and the output stay bf16 / fp32 as before; cross-attention stays bf16; the sequence-parallel forward raises NotImplementedError in
+        this mode. Needs head_dim 128 (ValueError otherwise, before any state changes). Independent of set_ffn_precision; the two combine.
+        Calls invalidate(): the prepared-weights generation moves on, so captured HIP graphs (WanTI2V) re-capture."""
+        _check_attn_precision(mode, self.blocks[0].self_attn.head_dim if len(self.blocks) else 128)
+        for b in self.blocks:
+            _check_attn_precision(mode, b.self_attn.head_dim)
+        self.attn_precision = mode
+        for b in self.blocks:
+            b.set_attn_precision(mode)
         self.invalidate()
 
     def prepare(self):
