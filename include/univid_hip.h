@@ -210,6 +210,53 @@ int uv_flash_attn_mxqk(const void* q_codes, long ldq, const void* q_scales, long
  * *q_blocks own 12 units of 32 queries, the others 8) or flash_attn_mxqk4_kernel (blocks of 128 queries, *n12 = 0). Host-only. */
 int uv_flash_attn_mxqk_plan(int batch, int Lq, int Lk, int H, int head_dim, char* kernel, int len, int* q_blocks, int* n12, int* grid);
 
+/* ---- DiT: self-attention with MXFP8 q / k AND an MXFP8 P.V (opt-in mode; WanModel.set_attn_precision("mxfp8_qk_pv")) ----------------
+ * uv_flash_attn_mxqk with V and the softmax weights P narrow as well: O^T = V^T P^T runs on v_mfma_scale_f32_32x32x64_f8f6f4 with f32
+ * accumulate (one instruction per 32 channels and 64-key tile in place of sixteen bf16 ones). q and k are exactly uv_flash_attn_mxqk's
+ * operands (same producer uv_rmsnorm_rope_qk_mx, every S element the same single chain). head_dim 128 only.
+ *
+ * V^T format. Elements and scales follow the MXFP8 rule above (e = clamp(exp(amax) - 8, 0, 254), clamp to +-448 then RNE, never a NaN code);
+ * a block is 32 CONSECUTIVE KEYS of one (head, head-dim channel) row, counted from EACH SAMPLE'S first key (not from column 0 of the stacked
+ * buffer). Each sample's keys are zero-padded to Lkp = roundup(Lk, 64): pad codes are 0; a block that holds no key at all has the scale byte
+ * 127 (a block with keys and pad follows the rule over its keys and zeros). No tile reads outside its sample; no pad can be a NaN.
+ *   vt_codes  uint8 [H*128, ldvc], sample b at columns [b*Lkp, (b+1)*Lkp), ldvc >= batch*Lkp, ldvc % 16 == 0, 16-byte aligned.
+ *             KEY ORDER INSIDE A 32-KEY BLOCK: key kappa (0..31) of the block is stored at byte perm34(kappa) = kappa with bits 3 and 4
+ *             swapped, i.e. the four 8-key groups in the order 0, 2, 1, 3. (The contraction does not care and the scale is per block; in this
+ *             order the instruction's A fragment is two plain 16-byte LDS reads against the lane map of the P accumulator.)
+ *   vt_scales uint8 [H, ld_vs], TILE-MAJOR: the 64-key tile t of sample b of head h owns the 256 bytes at h*ld_vs + (b*Lkp/64 + t)*256; byte
+ *             4*(r + 32*k) + d of them is the scale of channel 32*d + r (d = 0..3, r = 0..31) for the tile's key half k (keys 64 t + 32 k ..
+ *             + 31 of the sample). ld_vs >= batch*Lkp*4, ld_vs % 4 == 0, 4-byte aligned. (One 4-byte LDS-DMA per lane stages a tile's scales,
+ *             and lane l's dword holds the four bytes the instruction selects by op_sel.)
+ * P format. code = e4m3_RNE(P * 2^PSHIFT) with the instruction's scale byte 127 - PSHIFT on every lane; P = exp2((s - m) * scale * log2 e) against
+ * the query's running reference maximum m, which the query moves (once per 64-key tile, by its own scores alone) when a P would exceed
+ * 2^DEFER. DEFER + PSHIFT = 8: the largest code is 256 < 448, the conversion's overflow behaviour is never relied on. With DEFER 1 / PSHIFT 7
+ * normal codes reach down to P = 2^-13 and subnormal ones to 2^-16; smaller P are dropped from the numerator (a P of exactly 2^-17 ties to
+ * even = 0). (DEFER 8 / PSHIFT 0 would flush every P below 2^-10: at 11 440 keys a diffuse tail of that size can carry as much mass as the
+ * peak.) The denominator l sums the UNROUNDED f32 P, as the bf16 and mxqk kernels do. Masked keys (>= Lk) give code 0.
+ * A query's bits do not depend on the kernel, the query-block cut, the batch or its neighbours.
+ * Measured on one MI355X (profiles/mxpv_attn_bench.md, profiles/mxpv_parity_margins.json), against mxfp8_qk in the same process: attention launch + all
+ * producers 0.934 x (L = 11 440) / 0.870 x (L = 27 280) of its time. The price: one TI2V-5B-width block is 3.83 x (48 tokens) / 1.28 x (2 304 tokens)
+ * further from the unrounded result than the bf16 mode (mxfp8_qk: 2.87 x / 1.18 x); the kernel matches a CPU emulation of the format (truth ratio 1.0000 /
+ * 1.0018). Not measured: the 30-block model and the 121-frame step in the mode. */
+#define UV_ATT_MXPV_DEFER 1
+#define UV_ATT_MXPV_PSHIFT 7
+
+/* bf16 V^T [H*128, ldvt] as the UV_EPI_BF16_T GEMM writes it (sample b at columns [b*Lk, (b+1)*Lk); Lk % 8 == 0 when batch > 1; ldvt % 8 == 0,
+ * ldvt >= (batch-1)*Lk + roundup(Lk, 8); columns at Lk and beyond of a sample are never used) -> vt_codes / vt_scales in the format above, pads
+ * included, one pass. Replaces nothing in the reference (it is what the mode adds). For finite input the bytes of a (row, block) are a pure
+ * function of that block's 32 values. head_dim 128 only. */
+int uv_vt_mx_quant(const void* vt, long ldvt, void* vt_codes, long ldvc, void* vt_scales, long ld_vs, int batch, int Lk, int H, int head_dim,
+                   void* stream);
+
+/* uv_flash_attn_mxqk with vt_codes / vt_scales (above) in place of the bf16 V^T. q / k / out / batch / Lq / Lk / H / softmax_scale and their
+ * checks: uv_flash_attn_mxqk's. Anything else is rejected and nothing is written. */
+int uv_flash_attn_mxpv(const void* q_codes, long ldq, const void* q_scales, long ld_qs, const void* k_codes, long ldk, const void* k_scales,
+                       long ld_ks, const void* vt_codes, long ldvc, const void* vt_scales, long ld_vs, void* out, long ldo, int batch, int Lq,
+                       int Lk, int H, int head_dim, float softmax_scale, void* stream);
+
+/* The launch plan of uv_flash_attn_mxpv: uv_flash_attn_mxqk_plan's geometry with flash_attn_mxpv12_kernel / flash_attn_mxpv4_kernel. Host-only. */
+int uv_flash_attn_mxpv_plan(int batch, int Lq, int Lk, int H, int head_dim, char* kernel, int len, int* q_blocks, int* n12, int* grid);
+
 /* Operator-seam helpers: what flash_attention(q, k, v, ...) (attention.py:24-130) does around the core when it is handed
  * [B, L, N, C] tensors of any float dtype: `half(x)` casts (:59-83), and `.type(out_dtype)` of the result (:130); the
  * transpose produces the V^T operand of uv_flash_attn_* from token-major V rows.

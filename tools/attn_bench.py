@@ -27,9 +27,10 @@ print(f"attention B{B} Lq{L} Lk{Lk}: {ms:.3f} ms {4*B*L*Lk*C/ms/1e9:.1f} TFLOP/s
 
 
 if "--qk" in sys.argv and sys.argv[sys.argv.index("--qk") + 1] == "mxfp8":
-    # bf16 against the MXFP8 q / k mode (WanModel.set_attn_precision("mxfp8_qk")) on the same random operands, in ONE process: the launches
-    # and their producers (rmsnorm_rope_qk / rmsnorm_rope_qk_mx on the raw projections) alternate round by round, the first round of each is
-    # dropped, medians and the spread (min .. max) of the ROUNDS rounds are printed. The figure that counts is launch + producer.
+    # bf16 against the MXFP8 q / k mode and the MXFP8 q / k + P.V mode (WanModel.set_attn_precision("mxfp8_qk" / "mxfp8_qk_pv")) on the same
+    # random operands, in ONE process: the launches and their producers (rmsnorm_rope_qk / rmsnorm_rope_qk_mx on the raw projections, and for
+    # the P.V mode the V^T quantiser vt_mx_quant) alternate round by round, the first round of each is dropped, medians and the spread
+    # (min .. max) of the ROUNDS rounds are printed. The figure that counts is launch + ALL producers of the mode.
     import statistics
     rounds = int(os.environ.get("ROUNDS", 7))
     U8 = torch.uint8
@@ -40,13 +41,18 @@ if "--qk" in sys.argv and sys.argv[sys.argv.index("--qk") + 1] == "mxfp8":
     qc, kc = torch.empty(B * L, C, dtype=U8, device=dev), torch.empty(B * Lk, C, dtype=U8, device=dev)
     qs, ks = torch.empty(B * L, C // 32, dtype=U8, device=dev), torch.empty(B * Lk, C // 32, dtype=U8, device=dev)
     _lib.mx_quant(q, qc, qs); _lib.mx_quant(k, kc, ks)
-    out_mx = torch.empty_like(out)
+    out_mx, out_pv = torch.empty_like(out), torch.empty_like(out)
+    vcols = _lib.vt_mx_cols(B, Lk)
+    vc, vs = torch.empty(C, vcols, dtype=U8, device=dev), torch.empty(H, 4 * vcols, dtype=U8, device=dev)
+    _lib.vt_mx_quant(vt, vc, vs, Lk, H, D, batch=B)
     qn, kn = q_raw.clone(), k_raw.clone()
     assert L == Lk, "the producers run on q and k of one geometry (self-attention)"
     work = {
         "attn bf16": lambda: _lib.flash_attn(q, k, vt, out, L, Lk, H, D, 1 / math.sqrt(D), batch=B),
         "attn mxqk": lambda: _lib.flash_attn_mxqk(qc, qs, kc, ks, vt, out_mx, L, Lk, H, D, 1 / math.sqrt(D), batch=B),
         "prod bf16": lambda: _lib.rmsnorm_rope_qk(qn, kn, wq, wk, B * L, L, C, D, 1e-6, freqs, (F, Hh, Ww)),      # (in place: re-normalises its own output, same cost)
+        "attn mxpv": lambda: _lib.flash_attn_mxpv(qc, qs, kc, ks, vc, vs, out_pv, L, Lk, H, D, 1 / math.sqrt(D), batch=B),
+        "prod vtq": lambda: _lib.vt_mx_quant(vt, vc, vs, Lk, H, D, batch=B),
         "prod mxqk": lambda: _lib.rmsnorm_rope_qk_mx(q_raw, k_raw, wq, wk, qc, qs, kc, ks, B * L, L, C, D, 1e-6, freqs, (F, Hh, Ww)),
     }
     times = {name: [] for name in work}
@@ -60,7 +66,7 @@ if "--qk" in sys.argv and sys.argv[sys.argv.index("--qk") + 1] == "mxfp8":
             if rnd:
                 times[name].append(s.elapsed_time(e) / n * 1e3)
     _lib.mx_quant(q, qc, qs); _lib.mx_quant(k, kc, ks)          # (the producer rounds overwrote the codes)
-    work["attn mxqk"](); torch.cuda.synchronize()
+    work["attn mxqk"](); work["attn mxpv"](); torch.cuda.synchronize()
     med = {name: statistics.median(t) for name, t in times.items()}
     flop = 4 * B * L * Lk * C
     for name, t in times.items():
@@ -71,3 +77,7 @@ if "--qk" in sys.argv and sys.argv[sys.argv.index("--qk") + 1] == "mxfp8":
     print(f"launch + producer: bf16 {tot_b:.1f} us, mxfp8_qk {tot_m:.1f} us, ratio {tot_m / tot_b:.3f} (bf16 spread between rounds {spread:.1f} us); "
           f"kernel={_lib.attn_mxqk_plan(L, Lk, D, B, H)['kernel']}; rel rms of the mxqk output against bf16 on the same operands "
           f"{float((out_mx.float() - out.float()).pow(2).mean().sqrt() / out.float().pow(2).mean().sqrt()):.3e}")
+    tot_p = med["attn mxpv"] + med["prod mxqk"] + med["prod vtq"]
+    print(f"launch + producers (q / k producer and V^T quantiser): mxfp8_qk_pv {tot_p:.1f} us, ratio to bf16 {tot_p / tot_b:.3f}, to mxfp8_qk {tot_p / tot_m:.3f} "
+          f"(bf16 spread {spread:.1f} us); kernel={_lib.attn_mxpv_plan(L, Lk, D, B, H)['kernel']}; rel rms of the mxpv output against bf16 on the same "
+          f"operands {float((out_pv.float() - out.float()).pow(2).mean().sqrt() / out.float().pow(2).mean().sqrt()):.3e}")

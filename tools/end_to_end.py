@@ -3,8 +3,8 @@ random-init weights, synthetic prompt embeddings): 50 UniPC steps with CFG + VAE
 f32-grade bf16x6 / f16x3 modes - at the bench size (49 frames of 704 x 1280) and at UniVid's own default workload (121 frames of
 704 x 1280, inference.py:48-50).   env: STEPS (50), FRAMES ("49,121"), PRECS ("fp32,bf16x6,f16x3")
     --ffn-precision bf16|mxfp8   the DiT's FFN projections in the opt-in MXFP8 mode (WanModel.set_ffn_precision)
-    --attn-precision bf16|mxfp8_qk   the DiT's self-attention q / k in the opt-in MXFP8 mode (WanModel.set_attn_precision)
-    --attn-ab ROUNDS   instead of the table: ms per denoise step with the self-attention in bf16 against mxfp8_qk, alternating in one process"""
+    --attn-precision bf16|mxfp8_qk|mxfp8_qk_pv   the DiT's self-attention in an opt-in MXFP8 mode (WanModel.set_attn_precision)
+    --attn-ab ROUNDS   instead of the table: ms per denoise step with the self-attention in bf16, mxfp8_qk and mxfp8_qk_pv, alternating in one process"""
 import os, sys, time, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from univid_amd import _lib
@@ -37,13 +37,13 @@ def clock(fn):
 frames = [int(f) for f in os.environ.get("FRAMES", "49,121").split(",")]
 precs = os.environ.get("PRECS", "fp32,bf16x6,f16x3").split(",")
 if "--attn-ab" in sys.argv:
-    # --attn-ab ROUNDS: the denoise loop alone (t2v, decode=False) at the first FRAMES entry with the self-attention in "bf16" and in "mxfp8_qk",
+    # --attn-ab ROUNDS: the denoise loop alone (t2v, decode=False) at the first FRAMES entry with the self-attention in "bf16", "mxfp8_qk" and "mxfp8_qk_pv",
     # alternating round by round in THIS process (each switch re-prepares and re-captures: its warm-up generation is not timed), the first
     # round dropped; medians and the spread of the rounds. --ffn-precision applies to both sides.
     import statistics
     rounds, F = int(sys.argv[sys.argv.index("--attn-ab") + 1]), frames[0]
     pipe = WanTI2V(model=m, vae=Wan2_2_VAE(device=dev, seed=0, precision="f16x3"), device=dev)
-    ms = {"bf16": [], "mxfp8_qk": []}
+    ms = {"bf16": [], "mxfp8_qk": [], "mxfp8_qk_pv": []}
     for rnd in range(rounds + 1):
         for mode in ms:
             m.set_attn_precision(mode)
@@ -55,8 +55,9 @@ if "--attn-ab" in sys.argv:
                 ms[mode].append(t / steps * 1e3)
     med = {k: statistics.median(v) for k, v in ms.items()}
     for k, v in ms.items():
-        print(f"{F} frames, ffn {ffn_precision}, attn {k:8s}: median {med[k]:.2f} ms/step (min {min(v):.2f} max {max(v):.2f}, {len(v)} rounds of {steps} steps)", flush=True)
-    print(f"mxfp8_qk / bf16 = {med['mxfp8_qk'] / med['bf16']:.4f} (bf16 spread {max(ms['bf16']) - min(ms['bf16']):.2f} ms)", flush=True)
+        print(f"{F} frames, ffn {ffn_precision}, attn {k:11s}: median {med[k]:.2f} ms/step (min {min(v):.2f} max {max(v):.2f}, {len(v)} rounds of {steps} steps)", flush=True)
+    print(f"mxfp8_qk / bf16 = {med['mxfp8_qk'] / med['bf16']:.4f}, mxfp8_qk_pv / bf16 = {med['mxfp8_qk_pv'] / med['bf16']:.4f}, mxfp8_qk_pv / mxfp8_qk = "
+          f"{med['mxfp8_qk_pv'] / med['mxfp8_qk']:.4f} (bf16 spread {max(ms['bf16']) - min(ms['bf16']):.2f} ms)", flush=True)
     sys.exit(0)
 for F in frames:
     for prec in precs:

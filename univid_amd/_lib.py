@@ -47,6 +47,9 @@ SIGNATURES = {
     "uv_flash_attn_f16": [_P, _L, _P, _L, _P, _L, _P, _L, _I, _I, _I, _I, _I, _F, _P],
     "uv_flash_attn_mxqk": [_P, _L, _P, _L, _P, _L, _P, _L, _P, _L, _P, _L, _I, _I, _I, _I, _I, _F, _P],
     "uv_flash_attn_mxqk_plan": [_I, _I, _I, _I, _I, _c.c_char_p, _I, _c.POINTER(_I), _c.POINTER(_I), _c.POINTER(_I)],
+    "uv_vt_mx_quant": [_P, _L, _P, _L, _P, _L, _I, _I, _I, _I, _P],
+    "uv_flash_attn_mxpv": [_P, _L, _P, _L, _P, _L, _P, _L, _P, _L, _P, _L, _P, _L, _I, _I, _I, _I, _I, _F, _P],
+    "uv_flash_attn_mxpv_plan": [_I, _I, _I, _I, _I, _c.c_char_p, _I, _c.POINTER(_I), _c.POINTER(_I), _c.POINTER(_I)],
     "uv_flash_attn_kernel_name": [_I, _I, _L, _L, _I, _c.c_char_p, _I],
     "uv_flash_attn_plan": [_I, _I, _I, _I, _I, _L, _L, _I, _c.c_char_p, _I, _c.POINTER(_I), _c.POINTER(_I), _c.POINTER(_I)],
     "uv_transpose_16": [_P, _L, _P, _L, _I, _I, _I, _P],
@@ -541,6 +544,47 @@ def attn_mxqk_plan(Lq, Lk, D=128, batch=1, H=1):
     qb, n12, grid = _I(0), _I(0), _I(0)
     lib = load()
     if lib.uv_flash_attn_mxqk_plan(batch, Lq, Lk, H, D, buf, 96, ctypes.byref(qb), ctypes.byref(n12), ctypes.byref(grid)) != 0:
+        raise UnividHipError(lib.uv_last_error().decode())
+    return dict(kernel=buf.value.decode(), q_blocks=qb.value, n12=n12.value, grid=grid.value)
+
+
+def vt_mx_cols(batch, L):
+    """Columns of the MXFP8 V^T codes of `flash_attn_mxpv` for `batch` stacked samples of L keys: every sample padded to whole 64-key tiles
+    (sample b = columns [b*Lkp, (b+1)*Lkp), Lkp = roundup(L, 64)); the scale array has 4 bytes per column and head."""
+    return batch * ((L + 63) // 64 * 64)
+
+
+def vt_mx_quant(vt, vt_codes, vt_scales, Lk, H, D=128, batch=1):
+    """bf16 vt [H*D, >= (batch-1)*Lk + roundup(Lk, 8)] (sample b = columns b*Lk.., as the EPI_BF16_T GEMM writes it) -> vt_codes uint8
+    [H*D, >= vt_mx_cols(batch, Lk)] and vt_scales uint8 [H, >= 4 * vt_mx_cols(batch, Lk)] in the V^T format of include/univid_hip.h (keys
+    permuted inside their 32-key block, tile-major scales, pads written). head_dim 128 only."""
+    C, cols = H * D, vt_mx_cols(batch, Lk)
+    _check("vt_mx_quant", (vt, "vt", BF16, (batch - 1) * Lk + (Lk + 7) // 8 * 8, C), (vt_codes, "vt_codes", U8, cols, C),
+           (vt_scales, "vt_scales", U8, 4 * cols, H))
+    call("uv_vt_mx_quant", ptr(vt), vt.stride(-2), ptr(vt_codes), vt_codes.stride(-2), ptr(vt_scales), vt_scales.stride(-2), batch, Lk, H, D,
+         stream_ptr())
+    return vt_codes, vt_scales
+
+
+def flash_attn_mxpv(q_codes, q_scales, k_codes, k_scales, vt_codes, vt_scales, out, Lq, Lk, H, D, scale, batch=1):
+    """`flash_attn_mxqk` with the MXFP8 V^T of `vt_mx_quant` (codes uint8 [H*128, >= vt_mx_cols(batch, Lk)], scales uint8 [H, >= 4 x that]) and
+    e4m3 softmax weights: P.V on the block-scaled matrix instruction as well (include/univid_hip.h). head_dim 128 only."""
+    C, cols = H * D, vt_mx_cols(batch, Lk)
+    _check("flash_attn_mxpv", (q_codes, "q_codes", U8, C, batch * Lq), (q_scales, "q_scales", U8, C // 32, batch * Lq),
+           (k_codes, "k_codes", U8, C, batch * Lk), (k_scales, "k_scales", U8, C // 32, batch * Lk),
+           (vt_codes, "vt_codes", U8, cols, C), (vt_scales, "vt_scales", U8, 4 * cols, H), (out, "out", BF16, C, batch * Lq))
+    call("uv_flash_attn_mxpv", ptr(q_codes), q_codes.stride(-2), ptr(q_scales), q_scales.stride(-2), ptr(k_codes), k_codes.stride(-2),
+         ptr(k_scales), k_scales.stride(-2), ptr(vt_codes), vt_codes.stride(-2), ptr(vt_scales), vt_scales.stride(-2), ptr(out), out.stride(-2),
+         batch, Lq, Lk, H, D, float(scale), stream_ptr(), flops=4 * batch * Lq * Lk * H * D)
+    return out
+
+
+def attn_mxpv_plan(Lq, Lk, D=128, batch=1, H=1):
+    """Launch plan of `flash_attn_mxpv` for this geometry, as `attn_plan` reports `flash_attn`'s."""
+    buf = ctypes.create_string_buffer(96)
+    qb, n12, grid = _I(0), _I(0), _I(0)
+    lib = load()
+    if lib.uv_flash_attn_mxpv_plan(batch, Lq, Lk, H, D, buf, 96, ctypes.byref(qb), ctypes.byref(n12), ctypes.byref(grid)) != 0:
         raise UnividHipError(lib.uv_last_error().decode())
     return dict(kernel=buf.value.decode(), q_blocks=qb.value, n12=n12.value, grid=grid.value)
 

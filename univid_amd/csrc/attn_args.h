@@ -1,4 +1,4 @@
-// The flash-attention kernels' shared host and device pieces (attention.hip; attention_mx.hip; tools/diag/attn_pw4.hip): the argument block and constants,
+// The flash-attention kernels' shared host and device pieces (attention.hip; attention_mx.hip; attention_mxpv.hip; tools/diag/attn_pw4.hip): the argument block and constants,
 // plan_attn - the ONE place that decides which kernel serves a call, on what query-block cut and on what grid -, and the device code the
 // kernels have in common.
 #pragma once
@@ -7,6 +7,10 @@
 #define UV_ATT_QW 32     // queries per 32x32 MFMA block
 #define UV_ATT_KV 64     // keys per staged tile
 #define UV_ATT_DEFER 8.0f   // log2 of the largest P allowed before the reference maximum is moved
+// attention_mxpv.hip (P as e4m3 codes; include/univid_hip.h: UV_ATT_MXPV_DEFER / UV_ATT_MXPV_PSHIFT): code = e4m3(P 2^PSHIFT), P <= 2^DEFER_PV,
+// DEFER_PV + PSHIFT = 8: the largest code is 256
+#define UV_ATT_DEFER_PV 1
+#define UV_ATT_PSHIFT 7
 
 struct AttnArgs {
     const bf16_t* q;   // [Lq, ldq]   head h at column h*128
@@ -23,9 +27,10 @@ struct AttnArgs {
     const float* q_w;
 };
 
-enum AttnKernel { ATT_FWD12 = 0, ATT_FWD3 = 1, ATT_FWD_D128 = 2, ATT_FWD_D64 = 3, ATT_MXQK12 = 4, ATT_MXQK4 = 5 };
+enum AttnKernel { ATT_FWD12 = 0, ATT_FWD3 = 1, ATT_FWD_D128 = 2, ATT_FWD_D64 = 3, ATT_MXQK12 = 4, ATT_MXQK4 = 5, ATT_MXPV12 = 6, ATT_MXPV4 = 7 };
 static const char* const kAttnKernelName[] = {"flash_attn_fwd12_kernel", "flash_attn_fwd3_kernel", "flash_attn_fwd_kernel<128>",
-                                              "flash_attn_fwd_kernel<64>", "flash_attn_mxqk12_kernel", "flash_attn_mxqk4_kernel"};
+                                              "flash_attn_fwd_kernel<64>", "flash_attn_mxqk12_kernel", "flash_attn_mxqk4_kernel",
+                                              "flash_attn_mxpv12_kernel", "flash_attn_mxpv4_kernel"};
 struct AttnPlan {
     int kernel;            // AttnKernel
     int q_blocks, n12;     // query blocks per (sample, head); of them the 12-unit ones (flash_attn_fwd12_kernel only, else 0)
@@ -100,6 +105,13 @@ static inline AttnPlan plan_attn(int batch, int Lq, int Lk, int H, int head_dim,
 static inline AttnPlan plan_attn_mxqk(int batch, int Lq, int Lk, int H, int ncus, int force_cut) {
     AttnPlan plan = plan_attn(batch, Lq, Lk, H, 128, 8, 8, false, ncus, force_cut);
     plan.kernel = plan.kernel == ATT_FWD12 ? ATT_MXQK12 : ATT_MXQK4;
+    return plan;
+}
+
+// The MXFP8 q/k + P.V kernels (attention_mxpv.hip): the same decision once more, with the kernel of the same size.
+static inline AttnPlan plan_attn_mxpv(int batch, int Lq, int Lk, int H, int ncus, int force_cut) {
+    AttnPlan plan = plan_attn(batch, Lq, Lk, H, 128, 8, 8, false, ncus, force_cut);
+    plan.kernel = plan.kernel == ATT_FWD12 ? ATT_MXPV12 : ATT_MXPV4;
     return plan;
 }
 

@@ -54,7 +54,7 @@ class CrossAttentionConfig:
     lora_target_strategy: str = "your_method_here"
     lora_merge: bool = True       # CrossAttentionFusionPipeline.load_lora: fold the adapter into the dense weights (False: attach it un-merged)
     ffn_precision: str = "bf16"   # "mxfp8": the DiT's ffn.0 / ffn.2 on MXFP8 operands (WanModel.set_ffn_precision), an opt-in fast mode
-    attn_precision: str = "bf16"  # "mxfp8_qk": the DiT's self-attention q / k as MXFP8 (WanModel.set_attn_precision), an opt-in experimental mode
+    attn_precision: str = "bf16"  # "mxfp8_qk" / "mxfp8_qk_pv": the DiT's self-attention q / k (and P.V) as MXFP8 (WanModel.set_attn_precision), opt-in experimental modes
     guidance_strength: float = 1.0
     bagel_cross_attn_layers: List[int] = None
     freeze_bagel: bool = True

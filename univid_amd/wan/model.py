@@ -84,15 +84,15 @@ class _PreparedMx:
         self.b = p.b
 
 
-ATTN_PRECISIONS = ("bf16", "mxfp8_qk")
+ATTN_PRECISIONS = ("bf16", "mxfp8_qk", "mxfp8_qk_pv")
 
 
 def _check_attn_precision(mode, head_dim):
     """set_attn_precision's guards, on one self-attention's geometry: raises before any state changes."""
     if mode not in ATTN_PRECISIONS:
         raise ValueError(f"attn_precision {mode!r}: one of {ATTN_PRECISIONS}")
-    if mode == "mxfp8_qk" and head_dim != 128:
-        raise ValueError(f"attn_precision 'mxfp8_qk' needs head_dim 128 (one MX scale dword per head and row, two 64-element steps of the "
+    if mode != "bf16" and head_dim != 128:
+        raise ValueError(f"attn_precision {mode!r} needs head_dim 128 (one MX scale dword per head and row, two 64-element steps of the "
                          f"block-scaled matrix instruction); this model has head_dim {head_dim}")
 
 
@@ -272,13 +272,25 @@ class WanSelfAttention(nn.Module):
         vt = _vt_scratch("vt", C, batch, L, h.device)
         ql, kl = self._qkv(h, M, L, s0, vt)
         att = _act_buf(M, C, (self._slots["o"],), h.device)
-        if self.attn_precision == "mxfp8_qk":
+        if self.attn_precision != "bf16":
             # q and k leave the norm + RoPE pass as MXFP8 codes + scales (fresh buffers: no in-place form), S = K Q^T on the block-scaled
-            # matrix instruction; V^T, P.V and the output stay bf16
+            # matrix instruction; "mxfp8_qk": V^T, P.V and the output stay bf16
             qc, kc = (torch.empty(M, C, dtype=torch.uint8, device=h.device) for _ in range(2))
             qs, ks = (torch.empty(M, C // 32, dtype=torch.uint8, device=h.device) for _ in range(2))
             _lib.rmsnorm_rope_qk_mx(ql, kl, self.norm_q.weight, self.norm_k.weight, qc, qs, kc, ks, M, L, C, D, self.eps, freqs, grid)
-            _lib.flash_attn_mxqk(qc, qs, kc, ks, vt, att, L, Lk, H, D, 1.0 / math.sqrt(D), batch=batch)
+            if self.attn_precision == "mxfp8_qk_pv":
+                # the bf16 V^T of the GEMM (un-merged LoRA included) quantised along the keys into stable scratch (every byte, pads
+                # included, is rewritten per call), P as e4m3: P.V on the block-scaled instruction too. Lk < L: one sample, its first Lk keys
+                cols = _lib.vt_mx_cols(batch, L)
+                vc = _mx_scratch("vt_codes", (C, cols), h.device)
+                vs = _mx_scratch("vt_scales", (H, 4 * cols), h.device)
+                if Lk == L:
+                    _lib.vt_mx_quant(vt, vc, vs, L, H, D, batch=batch)
+                else:
+                    _lib.vt_mx_quant(vt, vc, vs, Lk, H, D)
+                _lib.flash_attn_mxpv(qc, qs, kc, ks, vc, vs, att, L, Lk, H, D, 1.0 / math.sqrt(D), batch=batch)
+            else:
+                _lib.flash_attn_mxqk(qc, qs, kc, ks, vt, att, L, Lk, H, D, 1.0 / math.sqrt(D), batch=batch)
             return _slotted(att, C, self._slots["o"], M, L, s0)
         # q and k of every stacked sample in one launch (RoPE positions restart with every sample)
         _lib.rmsnorm_rope_qk(ql, kl, self.norm_q.weight, self.norm_k.weight, M, L, C, D, self.eps, freqs, grid)
@@ -465,8 +477,8 @@ class WanAttentionBlock(nn.Module):
         self._prep = None
 
     def set_attn_precision(self, mode):
-        """"bf16" (default) or "mxfp8_qk": this block's self-attention with MXFP8 q / k (WanModel.set_attn_precision states the mode). No
-        prepared weight depends on it."""
+        """"bf16" (default), "mxfp8_qk": this block's self-attention with MXFP8 q / k, or "mxfp8_qk_pv": with an MXFP8 P.V as well
+        (WanModel.set_attn_precision states the modes). No prepared weight depends on it."""
         _check_attn_precision(mode, self.self_attn.head_dim)
         self.self_attn.attn_precision = mode
 
@@ -661,6 +673,17 @@ def _vt_scratch(tag, C, batch, L, device):
     return t
 
 
+def _mx_scratch(tag, shape, device):
+    """uint8 scratch of the MXFP8 V^T (codes / scales of attn_precision "mxfp8_qk_pv"): stable per (tag, device, stream) like _vt_scratch, so
+    a captured graph keeps reading and writing the same memory; never zeroed (uv_vt_mx_quant writes every byte the attention reads)."""
+    key = (tag, device, torch.cuda.current_stream(device).cuda_stream)
+    t, _ = _zero_cache.get(key, (None, None))
+    if t is None or tuple(t.shape) != tuple(shape) or (t.is_inference() and not torch.is_inference_mode_enabled()):
+        t = torch.empty(shape, dtype=torch.uint8, device=device)
+    _zero_cache[key] = (t, None)
+    return t
+
+
 def scratch_snapshot():
     """Identity of every per-stream scratch tensor (before a HIP-graph capture)."""
     return {k: id(t) for k, (t, _) in _zero_cache.items()}
@@ -827,7 +850,10 @@ class WanModel(nn.Module):
         leave the RMSNorm + RoPE pass as OCP MXFP8 (e4m3 elements, one power-of-two scale per 32 head-dim elements) and S runs on the
         block-scaled matrix instruction: a labelled, opt-in mode NARROWER than the reference's arithmetic (README). The softmax, P.V, V^T
         and the output stay bf16 / fp32 as before; cross-attention stays bf16; the sequence-parallel forward raises NotImplementedError in
-        this mode. Needs head_dim 128 (ValueError otherwise, before any state changes). Independent of set_ffn_precision; the two combine.
+        this mode. "mxfp8_qk_pv": the same q / k, and in addition V^T as MXFP8 along the key axis (uv_vt_mx_quant of the GEMM's bf16 V^T) and
+        the softmax weights P as e4m3 codes of P * 2^7, so that O = P V runs on the block-scaled instruction too (uv_flash_attn_mxpv; format
+        and its price: include/univid_hip.h, README); refused by the sequence-parallel forward likewise.
+        Needs head_dim 128 (ValueError otherwise, before any state changes). Independent of set_ffn_precision; the two combine.
         Calls invalidate(): the prepared-weights generation moves on, so captured HIP graphs (WanTI2V) re-capture."""
         _check_attn_precision(mode, self.blocks[0].self_attn.head_dim if len(self.blocks) else 128)
         for b in self.blocks:

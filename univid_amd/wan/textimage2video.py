@@ -266,7 +266,7 @@ class WanTI2V:
             # switch on self.model re-captures
             self.model.set_ffn_precision(ffn_precision)
         if attn_precision is not None and attn_precision != self.model.attn_precision:
-            # "bf16" | "mxfp8_qk" (WanModel.set_attn_precision): the opt-in MXFP8 q / k mode of the self-attention, passed on like ffn_precision
+            # "bf16" | "mxfp8_qk" | "mxfp8_qk_pv" (WanModel.set_attn_precision): the opt-in MXFP8 modes of the self-attention, passed on like ffn_precision
             self.model.set_attn_precision(attn_precision)
         if checkpoint_dir is not None:
             # textimage2video.py:88-103: the VAE and the text encoder come from the same directory. Each is loaded when its
