@@ -152,6 +152,37 @@ int uv_gemm_mxfp8_nt(const void* A, long lda, const void* A_scale, long ld_as, c
                      const void* bias_bf16, int M, int N, int K, int epilogue, void* out, long ldo, const float* gate,
                      const int32_t* gate_tid, long gate_stride, void* stream);
 
+/* ---- DiT: MXFP8 attention projections (opt-in fast mode; WanModel.set_proj_precision("mxfp8")) -----------------------------------
+ * The self-attention q / k / v / o and the cross-attention q / o Linears (models/wan/utils/modules/model.py:119-122, 138-140, 154,
+ * 170-179) on uv_gemm_mxfp8_nt, and the producer in front of them (model.py:239-251). NARROWER than the reference's bf16. */
+
+/* uv_gemm_mxfp8_nt with the transposed 16-bit output (UV_EPI_BF16_T; the v projection writing V^T): outT bf16 [N, ldo], ldo >= M and
+ * % 4 == 0, and outT[n][m] carries EXACTLY the bits uv_gemm_mxfp8_nt(UV_EPI_BF16) writes at [m][n] - that is the definition (the same
+ * product and rounding; the 16-bit values are transposed inside quads of lanes and leave as 8-byte stores along m). Columns >= M of outT
+ * are not written. The argument checks (nothing is written on rejection), the launch plan and the one fixed-order chain over K - a row's
+ * bits do not depend on M, the row offset or the tile shape - are uv_gemm_mxfp8_nt's. */
+int uv_gemm_mxfp8_nt_t(const void* A, long lda, const void* A_scale, long ld_as, const void* W, long ldw, const void* W_scale, long ld_ws,
+                       const void* bias_bf16, int M, int N, int K, void* outT, long ldo, void* stream);
+
+/* uv_gemm_mxfp8_nt(UV_EPI_BF16) plus the output's sums of squares (UV_EPI_BF16_SSQ; the cross-attention q projection in front of
+ * uv_rms_scale_from_ssq / uv_flash_attn_bf16_qnorm, model.py:170-171): out carries UV_EPI_BF16's bits, ssq f32 [M, ld_ssq],
+ * ld_ssq >= N / 32, ssq[m][g] = the sum of float(out[m][n])^2 over columns [32 g, 32 g + 32) in the ONE summation order stated at
+ * uv_gemm_bf16_nt_ssq (same device code). Columns >= N / 32 of ssq are not written. Checks, plan and K chain: uv_gemm_mxfp8_nt's. */
+int uv_gemm_mxfp8_nt_ssq(const void* A, long lda, const void* A_scale, long ld_as, const void* W, long ldw, const void* W_scale,
+                         long ld_ws, const void* bias_bf16, int M, int N, int K, void* out, long ldo, float* ssq, long ld_ssq,
+                         void* stream);
+
+/* uv_layernorm_mod (modes 1 and 2, round_ln 0 / 1, tid present or NULL) with an MXFP8 store: codes uint8 [L, ldc] and e8m0 scales uint8
+ * [L, ld_s] in the format stated above. DEFINITION: the bytes are, bit for bit, uv_mx_quant_bf16 applied to what
+ * uv_layernorm_mod(out_bf16 = 1) writes for the same inputs - the value is rounded to bf16 first, then quantised by the rule above (an
+ * all-zero block: e = 0, codes 0; the +-448 clamp is explicit; no code is ever a NaN). No bf16 copy is written: the activation does not
+ * make a bf16 round trip through memory in front of the q / k / v, cross q and ffn.0 GEMMs (WanLayerNorm + modulation, model.py:239-251).
+ * C % 256 == 0, C <= 8192, ldc >= C and % 16 == 0, ld_s >= C / 32 and % 4 == 0, x / codes 16-byte and scales 4-byte aligned. Columns >= C
+ * of codes and >= C / 32 of scales are not written. A row's bytes are a pure function of that row and its parameters. */
+int uv_layernorm_mod_mx(const float* x, long ldx, void* codes, long ldc, void* scales, long ld_s, int L, int C, float eps, int mode,
+                        const float* tab, long tab_stride, int shift_off, int scale_off, const int32_t* tid, const float* w,
+                        const float* b, int round_ln, void* stream);
+
 /* C[M,N] = A[M,K] . W[N,K]^T + bias (+ resid), all fp32, exact-f32 MFMA (16x16x4).
  * Replaces Head.head (fp32 island, model.py:286-290) and the VAE's 1x1 convolutions (vae2_2.py:211,249-250,766-767).
  * K % 4 == 0, N % 4 == 0. */

@@ -4,6 +4,9 @@ f32-grade bf16x6 / f16x3 modes - at the bench size (49 frames of 704 x 1280) and
 704 x 1280, inference.py:48-50).   env: STEPS (50), FRAMES ("49,121"), PRECS ("fp32,bf16x6,f16x3")
     --ffn-precision bf16|mxfp8   the DiT's FFN projections in the opt-in MXFP8 mode (WanModel.set_ffn_precision)
     --attn-precision bf16|mxfp8_qk|mxfp8_qk_pv   the DiT's self-attention in an opt-in MXFP8 mode (WanModel.set_attn_precision)
+    --proj-precision bf16|mxfp8   the DiT's attention projections in the opt-in MXFP8 mode (WanModel.set_proj_precision)
+    --proj-ab ROUNDS [--also-with-mx]   instead of the table: ms per denoise step with the attention projections in bf16 and mxfp8, alternating in one
+                       process; --also-with-mx repeats the comparison beside ffn_precision mxfp8 + attn_precision mxfp8_qk_pv in the same process
     --attn-ab ROUNDS   instead of the table: ms per denoise step with the self-attention in bf16, mxfp8_qk and mxfp8_qk_pv, alternating in one process"""
 import os, sys, time, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -22,7 +25,9 @@ ffn_precision = sys.argv[sys.argv.index("--ffn-precision") + 1] if "--ffn-precis
 m.set_ffn_precision(ffn_precision)
 attn_precision = sys.argv[sys.argv.index("--attn-precision") + 1] if "--attn-precision" in sys.argv else "bf16"
 m.set_attn_precision(attn_precision)
-print(f"ffn_precision {ffn_precision} attn_precision {attn_precision}", flush=True)
+proj_precision = sys.argv[sys.argv.index("--proj-precision") + 1] if "--proj-precision" in sys.argv else "bf16"
+m.set_proj_precision(proj_precision)
+print(f"ffn_precision {ffn_precision} attn_precision {attn_precision} proj_precision {proj_precision}", flush=True)
 m.prepare()
 g = torch.Generator(device=dev).manual_seed(1)
 pe = [torch.randn(40, 4096, device=dev, generator=g) * 0.1]
@@ -59,10 +64,38 @@ if "--attn-ab" in sys.argv:
     print(f"mxfp8_qk / bf16 = {med['mxfp8_qk'] / med['bf16']:.4f}, mxfp8_qk_pv / bf16 = {med['mxfp8_qk_pv'] / med['bf16']:.4f}, mxfp8_qk_pv / mxfp8_qk = "
           f"{med['mxfp8_qk_pv'] / med['mxfp8_qk']:.4f} (bf16 spread {max(ms['bf16']) - min(ms['bf16']):.2f} ms)", flush=True)
     sys.exit(0)
+if "--proj-ab" in sys.argv:
+    # --proj-ab ROUNDS: the denoise loop alone (t2v, decode=False) at the first FRAMES entry with the attention projections in "bf16" and
+    # "mxfp8", alternating round by round in THIS process (each switch re-prepares and re-captures: its warm-up generation is not timed), the
+    # first round dropped; medians and the round-to-round spread of each. --ffn-precision / --attn-precision apply to both sides;
+    # --also-with-mx runs the comparison a second time beside the other two MXFP8 modes.
+    import statistics
+    rounds, F = int(sys.argv[sys.argv.index("--proj-ab") + 1]), frames[0]
+    pipe = WanTI2V(model=m, vae=Wan2_2_VAE(device=dev, seed=0, precision="f16x3"), device=dev)
+    for ffn_p, attn_p in [(ffn_precision, attn_precision)] + ([("mxfp8", "mxfp8_qk_pv")] if "--also-with-mx" in sys.argv else []):
+        m.set_ffn_precision(ffn_p)
+        m.set_attn_precision(attn_p)
+        ms = {"bf16": [], "mxfp8": []}
+        for rnd in range(rounds + 1):
+            for mode in ms:
+                m.set_proj_precision(mode)
+                with torch.no_grad():
+                    pipe.t2v("", size=(1280, 704), frame_num=F, sampling_steps=2, seed=7, prompt_embeds=pe, negative_prompt_embeds=ne, decode=False)
+                    _, t = clock(lambda: pipe.t2v("", size=(1280, 704), frame_num=F, sampling_steps=steps, seed=7, prompt_embeds=pe,
+                                                  negative_prompt_embeds=ne, decode=False))
+                if rnd:
+                    ms[mode].append(t / steps * 1e3)
+        med = {k: statistics.median(v) for k, v in ms.items()}
+        for k, v in ms.items():
+            print(f"{F} frames, ffn {ffn_p}, attn {attn_p}, proj {k:5s}: median {med[k]:.2f} ms/step (min {min(v):.2f} max {max(v):.2f}, spread "
+                  f"{max(v) - min(v):.2f}, {len(v)} rounds of {steps} steps)", flush=True)
+        print(f"ffn {ffn_p}, attn {attn_p}: proj mxfp8 / bf16 = {med['mxfp8'] / med['bf16']:.4f}, gain {med['bf16'] - med['mxfp8']:.2f} ms/step (bf16 spread "
+              f"{max(ms['bf16']) - min(ms['bf16']):.2f} ms, mxfp8 spread {max(ms['mxfp8']) - min(ms['mxfp8']):.2f} ms)", flush=True)
+    sys.exit(0)
 for F in frames:
     for prec in precs:
         vae = Wan2_2_VAE(device=dev, seed=0, precision=prec)
-        pipe = WanTI2V(model=m, vae=vae, device=dev, ffn_precision=ffn_precision, attn_precision=attn_precision)
+        pipe = WanTI2V(model=m, vae=vae, device=dev, ffn_precision=ffn_precision, attn_precision=attn_precision, proj_precision=proj_precision)
         with torch.no_grad():
             # warm-up of both loops (2 steps each): one-time costs - the VAE's weight preparation, the HIP-graph captures of the t2v and i2v
             # forward pairs (one per latent shape and mode; a NEW PROMPT does not recapture) - stay out of the timed generations

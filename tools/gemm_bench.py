@@ -1,6 +1,7 @@
 """GEMM micro-benchmark on the DiT's shapes: every tile config, interleaved rounds in ONE process, random operands.
 
     python tools/gemm_bench.py [--cfgs 0,5,6,7] [--rounds 5] [--check]
+    python tools/gemm_bench.py --mxproj      the attention projections' shape (N = K = 3072 at 22 880 and 11 440 rows), bf16 against MXFP8, per epilogue
     python tools/gemm_bench.py --mx          the two FFN shapes, bf16 (tile_cfg 0) against MXFP8 (uv_gemm_mxfp8_nt), quantise passes included
 
 Prints median/min TFLOP/s per (shape, config). `--check` compares each config with an fp64 reference on a row sample.
@@ -96,6 +97,43 @@ def bench_mx(rounds, iters):
     print(f"pair: bf16 {bf:.1f} us, mxfp8 incl. both quantise passes {mx:.1f} us, ratio bf16 / mxfp8 = {bf / mx:.3f}", flush=True)
 
 
+def bench_mxproj(rounds, iters):
+    """The attention projections (N = K = 3072) at the CFG pair's 22 880 rows and one sample's 11 440: uv_gemm_bf16_nt (tile_cfg 0) /
+    uv_gemm_bf16_nt_ssq against uv_gemm_mxfp8_nt / _t / _ssq on pre-quantised operands, per epilogue - BF16 (q / k), T (v), SSQ (cross q),
+    GATE_RESID (o). Random operands; one process, bf16 and MXFP8 of an epilogue back to back."""
+    dev = "cuda"
+    g = torch.Generator(device=dev).manual_seed(1)
+    C, u8, bf = 3072, torch.uint8, torch.bfloat16
+    for M in (L2, L2 // 2):
+        a = (torch.rand(M, C, device=dev, generator=g) * 2 - 1).to(bf)
+        w = ((torch.rand(C, C, device=dev, generator=g) * 2 - 1) * 0.05).to(bf)
+        bias = (torch.rand(C, device=dev, generator=g) - 0.5).to(bf)
+        ac, asc = torch.empty(M, C, dtype=u8, device=dev), torch.empty(M, C // 32, dtype=u8, device=dev)
+        wc, wsc = torch.empty(C, C, dtype=u8, device=dev), torch.empty(C, C // 32, dtype=u8, device=dev)
+        _lib.mx_quant(a, ac, asc)
+        _lib.mx_quant(w, wc, wsc)
+        out = torch.zeros(M, C, device=dev, dtype=bf)
+        out_t = torch.zeros(C, (M + 63) // 64 * 64, device=dev, dtype=bf)
+        ssq = torch.zeros(M, C // 32, device=dev)
+        x = torch.rand(M, C, device=dev, generator=g)
+        gate = torch.rand(2, C, device=dev, generator=g)
+        tid = (torch.arange(M, device=dev) * 2 // M).to(torch.int32)
+        pairs = {
+            "BF16": (lambda: _lib.gemm_bf16(a, w, bias, out, EPI_BF16), lambda: _lib.gemm_mxfp8(ac, asc, wc, wsc, bias, out, EPI_BF16)),
+            "T": (lambda: _lib.gemm_bf16(a, w, bias, out_t, EPI_BF16_T), lambda: _lib.gemm_mxfp8_t(ac, asc, wc, wsc, bias, out_t)),
+            "SSQ": (lambda: _lib.gemm_bf16_ssq(a, w, bias, out, ssq), lambda: _lib.gemm_mxfp8_ssq(ac, asc, wc, wsc, bias, out, ssq)),
+            "GATE_RESID": (lambda: _lib.gemm_bf16(a, w, bias, x, EPI_GATE_RESID_F32, gate=gate, gate_tid=tid),
+                           lambda: _lib.gemm_mxfp8(ac, asc, wc, wsc, bias, x, EPI_GATE_RESID_F32, gate=gate, gate_tid=tid)),
+        }
+        fl = 2.0 * M * C * C
+        for name, (f_bf, f_mx) in pairs.items():
+            t_bf, t_mx = _median_us(f_bf, rounds, iters), _median_us(f_mx, rounds, iters)
+            print(f"M={M:6d} N=K=3072 {name:10s}: bf16 {t_bf:7.1f} us {fl / t_bf / 1e6:7.1f} TF/s | mxfp8 {t_mx:7.1f} us {fl / t_mx / 1e6:7.1f} TF/s | "
+                  f"bf16 / mxfp8 = {t_bf / t_mx:.3f}", flush=True)
+        t_q = _median_us(lambda: _lib.mx_quant(a, ac, asc), rounds, iters)
+        print(f"M={M:6d} mx_quant of the [M x 3072] bf16 activation: {t_q:7.1f} us", flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cfgs", default="0,1,2,5,6")
@@ -105,7 +143,11 @@ def main():
     ap.add_argument("--shapes", default="")
     ap.add_argument("--ws", action="store_true", help="pass a split-K workspace (tile_cfg 19 / 20; tile_cfg 0's ffn.2 strip)")
     ap.add_argument("--mx", action="store_true", help="ffn.0 + ffn.2: bf16 against MXFP8 (quantise passes timed separately, included in the pair)")
+    ap.add_argument("--mxproj", action="store_true", help="the attention projections' shape: bf16 against MXFP8 per epilogue (BF16, T, SSQ, GATE_RESID)")
     a = ap.parse_args()
+    if a.mxproj:
+        _lib.init()
+        return bench_mxproj(a.rounds, a.iters)
     if a.mx:
         _lib.init()
         return bench_mx(a.rounds, a.iters)

@@ -40,3 +40,20 @@ timeit(lambda: _lib.rmsnorm_rope(q[:L], q[:L], w, L, C, D, 1e-6, fr, (13, 22, 40
 timeit(lambda: _lib.rmsnorm_rope(q, q, w, M, C, D, 1e-6), M * C * 4, "rmsnorm_rope no RoPE (cross q), 22880 rows")
 k = torch.randn(B * L, C, device=dev, generator=g).to(torch.bfloat16)
 timeit(lambda: _lib.rmsnorm_rope_qk(q, k, w, b, M, L, C, D, 1e-6, fr, (13, 22, 40)), 2 * M * C * 4, "rmsnorm_rope_qk (q+k, 2 samples, RoPE), 4 x 11440 rows")
+# the producers of the MXFP8 projections (proj_precision / ffn_precision "mxfp8"): two passes against uv_layernorm_mod_mx, and the quantise
+# pass over the attention output in front of the o projections
+u8 = torch.uint8
+hc, hs = torch.empty(M, C, device=dev, dtype=u8), torch.empty(M, C // 32, device=dev, dtype=u8)
+timeit(lambda: _lib.mx_quant(h, hc, hs), M * C * 3 + M * C // 32, "mx_quant (bf16 -> MXFP8; the attention output), 22880 rows")
+
+
+def two_pass(**kw):
+    _lib.layernorm_mod(x, h, M, C, 1e-6, **kw)
+    _lib.mx_quant(h, hc, hs)
+
+
+ada, aff = dict(mode=1, tab=tab, shift_off=0, scale_off=C, tid=tid), dict(mode=2, w=w, b=b)
+timeit(lambda: two_pass(**ada), M * C * 5 + M * C // 32, "layernorm_mod AdaLN + mx_quant (two passes), 22880 rows")
+timeit(lambda: _lib.layernorm_mod_mx(x, hc, hs, M, C, 1e-6, **ada), M * C * 5 + M * C // 32, "layernorm_mod_mx AdaLN (f32 -> MXFP8), 22880 rows")
+timeit(lambda: two_pass(**aff), M * C * 5 + M * C // 32, "layernorm_mod affine + mx_quant (two passes), 22880 rows")
+timeit(lambda: _lib.layernorm_mod_mx(x, hc, hs, M, C, 1e-6, **aff), M * C * 5 + M * C // 32, "layernorm_mod_mx affine (f32 -> MXFP8), 22880 rows")

@@ -36,6 +36,8 @@ SIGNATURES = {
     "uv_gemm_f16_nt": [_P, _L, _P, _L, _P, _I, _I, _I, _I, _P, _L, _P, _P, _L, _I, _P],
     "uv_mx_quant_bf16": [_P, _L, _P, _L, _P, _L, _I, _I, _P],
     "uv_gemm_mxfp8_nt": [_P, _L, _P, _L, _P, _L, _P, _L, _P, _I, _I, _I, _I, _P, _L, _P, _P, _L, _P],
+    "uv_gemm_mxfp8_nt_t": [_P, _L, _P, _L, _P, _L, _P, _L, _P, _I, _I, _I, _P, _L, _P],
+    "uv_gemm_mxfp8_nt_ssq": [_P, _L, _P, _L, _P, _L, _P, _L, _P, _I, _I, _I, _P, _L, _P, _L, _P],
     "uv_gemm_f32_nt": [_P, _L, _P, _L, _P, _I, _I, _I, _P, _L, _P, _L, _P],
     "uv_gemm_bf16_nt_ssq": [_P, _L, _P, _L, _P, _I, _I, _I, _P, _L, _P, _L, _I, _P],
     "uv_rms_scale_from_ssq": [_P, _L, _I, _I, _I, _F, _P, _P],
@@ -56,6 +58,7 @@ SIGNATURES = {
     "uv_cast_f32_to16": [_P, _P, _L, _I, _P],
     "uv_cast_16_to_f32": [_P, _P, _L, _I, _P],
     "uv_layernorm_mod": [_P, _L, _P, _L, _I, _I, _F, _I, _P, _L, _I, _I, _P, _P, _P, _I, _I, _P],
+    "uv_layernorm_mod_mx": [_P, _L, _P, _L, _P, _L, _I, _I, _F, _I, _P, _L, _I, _I, _P, _P, _P, _I, _P],
     "uv_t5_attention_bf16": [_P, _L, _P, _L, _P, _L, _P, _L, _I, _I, _P, _I, _P],
     "uv_add_bf16": [_P, _P, _P, _L, _P],
     "uv_t5_gated_gelu_bf16": [_P, _P, _P, _L, _P],
@@ -392,6 +395,39 @@ def gemm_mxfp8(a, a_scale, w, w_scale, bias, out, epi, M=None, gate=None, gate_t
     return out
 
 
+def _mx_operands(fn, a, a_scale, w, w_scale, M, N, K):
+    """The shape conditions gemm_mxfp8 puts on its operands beyond _check's extents, for the two entry points beside it."""
+    if a.shape[1] < K or M > min(a.shape[0], a_scale.shape[0]) or a_scale.shape[1] * 32 < K or w_scale.shape[1] * 32 < K or w_scale.shape[0] < N:
+        raise UnividHipError(f"{fn}: a {tuple(a.shape)} / a_scale {tuple(a_scale.shape)} / w {tuple(w.shape)} / w_scale "
+                             f"{tuple(w_scale.shape)} do not fit M = {M}")
+
+
+def gemm_mxfp8_t(a, a_scale, w, w_scale, bias, out_t, M=None):
+    """gemm_mxfp8(EPI_BF16) written transposed: out_t bf16 [N, >= M], out_t[n][m] = the bits gemm_mxfp8 writes at [m][n] (V^T of the
+    MXFP8 v projection; include/univid_hip.h: uv_gemm_mxfp8_nt_t)."""
+    M = a.shape[0] if M is None else M
+    N, K = w.shape
+    _check("gemm_mxfp8_t", (a, "a", U8, K, M), (a_scale, "a_scale", U8, K // 32, M), (w, "w", U8, K, N), (w_scale, "w_scale", U8, K // 32, N),
+           (bias, "bias", BF16, N, None, True), (out_t, "out_t", BF16, M, N))
+    _mx_operands("gemm_mxfp8_t", a, a_scale, w, w_scale, M, N, K)
+    call("uv_gemm_mxfp8_nt_t", ptr(a), a.stride(-2), ptr(a_scale), a_scale.stride(-2), ptr(w), w.stride(-2), ptr(w_scale), w_scale.stride(-2),
+         ptr(bias), M, N, K, ptr(out_t), out_t.stride(-2), stream_ptr(), flops=2 * M * N * K)
+    return out_t
+
+
+def gemm_mxfp8_ssq(a, a_scale, w, w_scale, bias, out, ssq, M=None):
+    """gemm_mxfp8(EPI_BF16) plus ssq[m][g] = the output row's sum of squares over columns [32 g, 32 g + 32) (f32 [M, >= N / 32]), in
+    gemm_bf16_ssq's summation order (include/univid_hip.h: uv_gemm_mxfp8_nt_ssq)."""
+    M = a.shape[0] if M is None else M
+    N, K = w.shape
+    _check("gemm_mxfp8_ssq", (a, "a", U8, K, M), (a_scale, "a_scale", U8, K // 32, M), (w, "w", U8, K, N), (w_scale, "w_scale", U8, K // 32, N),
+           (bias, "bias", BF16, N, None, True), (out, "out", BF16, N, M), (ssq, "ssq", F32, N // 32, M))
+    _mx_operands("gemm_mxfp8_ssq", a, a_scale, w, w_scale, M, N, K)
+    call("uv_gemm_mxfp8_nt_ssq", ptr(a), a.stride(-2), ptr(a_scale), a_scale.stride(-2), ptr(w), w.stride(-2), ptr(w_scale), w_scale.stride(-2),
+         ptr(bias), M, N, K, ptr(out), out.stride(-2), ptr(ssq), ssq.stride(-2), stream_ptr(), flops=2 * M * N * K)
+    return out
+
+
 def gemm_bf16_ssq(a, w, bias, out, ssq, M=None, tile_cfg=0):
     """out = bf16(a w^T + bias) and ssq[m][g] = the output row's sum of squares over columns [32 g, 32 g + 32) (f32 [M, N / 32])."""
     M = a.shape[0] if M is None else M
@@ -633,6 +669,17 @@ def layernorm_mod(x, out, L, C, eps, mode=0, tab=None, shift_off=0, scale_off=0,
          0 if tab is None else tab.stride(-2), shift_off, scale_off, ptr(tid), ptr(w), ptr(b), int(round_ln),
          2 if out.dtype == F16 else int(out.dtype == BF16), stream_ptr())
     return out
+
+
+def layernorm_mod_mx(x, codes, scales, L, C, eps, mode=1, tab=None, shift_off=0, scale_off=0, tid=None, w=None, b=None, round_ln=False):
+    """layernorm_mod (mode 1 or 2, bf16 output) stored as OCP MXFP8: codes uint8 [L, >= C] and scales uint8 [L, >= C / 32] hold, bit for
+    bit, mx_quant of what layernorm_mod writes into a bf16 `out` for the same inputs (include/univid_hip.h: uv_layernorm_mod_mx)."""
+    _check("layernorm_mod_mx", (x, "x", F32, C, L), (codes, "codes", U8, C, L), (scales, "scales", U8, C // 32, L),
+           (tab, "tab", F32, max(shift_off, scale_off) + C, 0 if tab is None else tab.shape[0], True), (tid, "tid", I32, L, None, True),
+           (w, "w", F32, C, None, True), (b, "b", F32, C, None, True))
+    call("uv_layernorm_mod_mx", ptr(x), x.stride(-2), ptr(codes), codes.stride(-2), ptr(scales), scales.stride(-2), L, C, float(eps), mode,
+         ptr(tab), 0 if tab is None else tab.stride(-2), shift_off, scale_off, ptr(tid), ptr(w), ptr(b), int(round_ln), stream_ptr())
+    return codes, scales
 
 
 def rmsnorm_rope(x, out, weight, L, C, D, eps, freqs=None, grid=(0, 0, 0), row0=0):

@@ -30,6 +30,7 @@ struct LnArgs {
     const float* w; const float* b;                               // mode 2
     int L, C; float eps;
     int mode, round_ln, out_bf16;
+    uint8_t* sc; long ld_s;                                       // MX store: e8m0 scale bytes [L, ld_s] (out = the e4m3 codes, ldo in bytes)
 };
 
 // A 4-wave block walks 4*RPW consecutive token rows, one row per wave at a time. The modulation (or affine) parameters of
@@ -40,7 +41,9 @@ struct LnArgs {
 // SMODE >= 0: the mode is a compile-time constant, the output is bf16 and the normalised value is not rounded before the modulation (the
 // DiT's per-block calls): the output pass is straight-line code - with mode / output type / rounding as run-time branches inside the
 // chunk loop every chunk was its own basic block with its own waits.
-template <int MAXV, int RPW, bool EXACT = false, int SMODE = -1>
+// MX (uv_layernorm_mod_mx): the same arithmetic up to the bf16 rounding of the output, then uv_mx_quant_bf16's rule on the rounded values
+// instead of the bf16 store. A lane's 4 columns are an eighth of one MX block (8 neighbouring lanes), 32 lanes are one 128-column group.
+template <int MAXV, int RPW, bool EXACT = false, int SMODE = -1, bool MX = false>
 __global__ __launch_bounds__(256) void layernorm_mod_kernel(LnArgs p) {
     if constexpr (SMODE >= 0) { p.mode = SMODE; p.out_bf16 = 1; p.round_ln = 0; }
     extern __shared__ __attribute__((aligned(16))) char ln_smem[];
@@ -127,7 +130,28 @@ __global__ __launch_bounds__(256) void layernorm_mod_kernel(LnArgs p) {
                             for (int e = 0; e < 4; ++e) y[e] = __fadd_rn(__fmul_rn(y[e], pa[e]), pb[e]);
                         }
                     }
-                    if (p.out_bf16 == 2) {   // IEEE fp16 output (SigLIP2 ranker in its reference dtype)
+                    if constexpr (MX) {
+                        const u32x2 o = {pack_bf2(y[0], y[1]), pack_bf2(y[2], y[3])};
+                        const float z[4] = {__builtin_bit_cast(float, o[0] << 16), __builtin_bit_cast(float, o[0] & 0xffff0000u),
+                                            __builtin_bit_cast(float, o[1] << 16), __builtin_bit_cast(float, o[1] & 0xffff0000u)};
+                        // amax through the integer magnitudes, over the block's 8 lanes (as mx_quant_bf16_kernel does over its 2)
+                        uint32_t amax = max(max(o[0] << 16 & 0x7fffffffu, o[0] & 0x7fff0000u), max(o[1] << 16 & 0x7fffffffu, o[1] & 0x7fff0000u));
+                        amax = max(amax, (uint32_t)__shfl_xor((int)amax, 1, 64));
+                        amax = max(amax, (uint32_t)__shfl_xor((int)amax, 2, 64));
+                        amax = max(amax, (uint32_t)__shfl_xor((int)amax, 4, 64));
+                        const int eb = max((int)(amax >> 23) - 8, 0);
+                        const float inv = __builtin_bit_cast(float, (uint32_t)(254 - eb) << 23);
+                        float sv[4];
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) sv[e] = fminf(fmaxf(__fmul_rn(z[e], inv), -448.f), 448.f);      // exact scaling, explicit clamp
+                        int pk = __builtin_amdgcn_cvt_pk_fp8_f32(sv[0], sv[1], 0, false);
+                        pk = __builtin_amdgcn_cvt_pk_fp8_f32(sv[2], sv[3], pk, true);
+                        *(uint32_t*)((uint8_t*)p.out + (long)row * p.ldo + c) = (uint32_t)pk;
+                        // the four scale bytes of the 128-column group, gathered in its first lane
+                        const int base = lane & 32;
+                        const uint32_t e1 = (uint32_t)__shfl(eb, base + 8, 64), e2 = (uint32_t)__shfl(eb, base + 16, 64), e3 = (uint32_t)__shfl(eb, base + 24, 64);
+                        if ((lane & 31) == 0) *(uint32_t*)(p.sc + (long)row * p.ld_s + i * 8 + (lane >> 3)) = (uint32_t)eb | e1 << 8 | e2 << 16 | e3 << 24;
+                    } else if (p.out_bf16 == 2) {   // IEEE fp16 output (SigLIP2 ranker in its reference dtype)
                         u32x2 o = {pack16_2<true>(y[0], y[1]), pack16_2<true>(y[2], y[3])};
                         *(u32x2*)((bf16_t*)p.out + (long)row * p.ldo + c) = o;
                     } else if (p.out_bf16) {
@@ -155,7 +179,7 @@ extern "C" int uv_layernorm_mod(const float* x, long ldx, void* out, long ldo, i
     if (mode == 1) UV_CHECK_ARG(tab && tab_stride % 4 == 0 && shift_off % 4 == 0 && scale_off % 4 == 0,
                                 "uv_layernorm_mod: modulation table missing / misaligned");
     if (mode == 2) UV_CHECK_ARG(w && b, "uv_layernorm_mod: affine weight/bias missing");
-    LnArgs a{x, ldx, out, ldo, tab, tab_stride, shift_off, scale_off, tid, w, b, L, C, eps, mode, round_ln, out_bf16};
+    LnArgs a{x, ldx, out, ldo, tab, tab_stride, shift_off, scale_off, tid, w, b, L, C, eps, mode, round_ln, out_bf16, nullptr, 0};
     // one row per wave: measured 4.2-4.4 TB/s; 2 or 4 rows per wave run the waves of a CU in lockstep (all loading, then
     // all storing) and lose 15-30 %, so the LDS staging only trims the parameter reads to one copy per 4 rows
     const dim3 grid((L + 3) / 4), block(256);
@@ -172,6 +196,38 @@ extern "C" int uv_layernorm_mod(const float* x, long ldx, void* out, long ldo, i
     else if (C <= 4096) hipLaunchKernelGGL((layernorm_mod_kernel<16, 1>), grid, block, lds, st, a);
     else hipLaunchKernelGGL((layernorm_mod_kernel<32, 1>), grid, block, lds, st, a);
     UV_CHECK_LAUNCH("uv_layernorm_mod");
+    return 0;
+}
+
+// uv_layernorm_mod(out_bf16 = 1) with an MXFP8 store (include/univid_hip.h): the producer in front of the MX projections and ffn.0
+// (WanModel.set_proj_precision / set_ffn_precision "mxfp8"; norm1 / norm3 / norm2 of model.py:239-251). Same kernel, same launch shape:
+// the values up to the bf16 rounding are those of uv_layernorm_mod, the bytes those of uv_mx_quant_bf16 on them. No bf16 copy is written.
+extern "C" int uv_layernorm_mod_mx(const float* x, long ldx, void* codes, long ldc, void* scales, long ld_s, int L, int C, float eps,
+                                   int mode, const float* tab, long tab_stride, int shift_off, int scale_off, const int32_t* tid,
+                                   const float* w, const float* b, int round_ln, void* stream) {
+    UV_CHECK_ARG(x && codes && scales && L > 0, "uv_layernorm_mod_mx: null pointer / empty");
+    UV_CHECK_ARG(C % 256 == 0 && C > 0 && C <= 8192, "uv_layernorm_mod_mx: C=%d must be a multiple of 256 and <= 8192", C);
+    UV_CHECK_ARG(ldx % 4 == 0 && ldx >= C, "uv_layernorm_mod_mx: ldx must be >= C and a multiple of 4");
+    UV_CHECK_ARG(ldc >= C && ldc % 16 == 0, "uv_layernorm_mod_mx: ldc must be >= C and a multiple of 16 bytes");
+    UV_CHECK_ARG(ld_s >= C / 32 && ld_s % 4 == 0, "uv_layernorm_mod_mx: ld_s must be >= C / 32 = %d and a multiple of 4 (ld_s=%ld)", C / 32, ld_s);
+    UV_CHECK_ARG(((uintptr_t)x & 15) == 0 && ((uintptr_t)codes & 15) == 0 && ((uintptr_t)scales & 3) == 0,
+                 "uv_layernorm_mod_mx: x / codes must be 16-byte, scales 4-byte aligned");
+    UV_CHECK_ARG(mode == 1 || mode == 2, "uv_layernorm_mod_mx: bad mode %d (1 and 2 are built)", mode);
+    if (mode == 1) UV_CHECK_ARG(tab && tab_stride % 4 == 0 && shift_off % 4 == 0 && scale_off % 4 == 0,
+                                "uv_layernorm_mod_mx: modulation table missing / misaligned");
+    if (mode == 2) UV_CHECK_ARG(w && b, "uv_layernorm_mod_mx: affine weight/bias missing");
+    LnArgs a{x, ldx, codes, ldc, tab, tab_stride, shift_off, scale_off, tid, w, b, L, C, eps, mode, round_ln != 0, 1, (uint8_t*)scales, ld_s};
+    const dim3 grid((L + 3) / 4), block(256);
+    const size_t lds = (size_t)2 * (C / 4) * 16;
+    hipStream_t st = (hipStream_t)stream;
+    if (C == 3072 && !round_ln && mode == 1) hipLaunchKernelGGL((layernorm_mod_kernel<12, 1, true, 1, true>), grid, block, lds, st, a);
+    else if (C == 3072 && !round_ln && mode == 2) hipLaunchKernelGGL((layernorm_mod_kernel<12, 1, true, 2, true>), grid, block, lds, st, a);
+    else if (C == 3072) hipLaunchKernelGGL((layernorm_mod_kernel<12, 1, true, -1, true>), grid, block, lds, st, a);
+    else if (C <= 1024) hipLaunchKernelGGL((layernorm_mod_kernel<4, 1, false, -1, true>), grid, block, lds, st, a);
+    else if (C <= 3072) hipLaunchKernelGGL((layernorm_mod_kernel<12, 1, false, -1, true>), grid, block, lds, st, a);
+    else if (C <= 4096) hipLaunchKernelGGL((layernorm_mod_kernel<16, 1, false, -1, true>), grid, block, lds, st, a);
+    else hipLaunchKernelGGL((layernorm_mod_kernel<32, 1, false, -1, true>), grid, block, lds, st, a);
+    UV_CHECK_LAUNCH("uv_layernorm_mod_mx");
     return 0;
 }
 

@@ -28,6 +28,47 @@ struct MxArgs {
     long ld_as, ld_ws;
 };
 
+// UV_EPI_BF16_T on the plain product's fragment (the lane holds n = nb + 4 fq + {0..3} of m = mb + frow): the 16-bit values are those of
+// epi_frag<UV_EPI_BF16> - same additions, same packed rounding - and are then transposed 4 x 4 inside each quad of lanes (three quad
+// permutes), after which lane (frow = 4 a + i, fq) owns the rows m = mb + 4 a + {0..3} of column n = nb + 4 fq + i: one 8-byte store along
+// m. The exchange moves bits only, so outT[n][m] IS the UV_EPI_BF16 value of [m][n]. Every lane of the wave must be active.
+// A ragged M tail stores element by element like epi_frag's T branch (ldo pads M to a multiple of 4 at least).
+__device__ __forceinline__ void epi_frag_mx_t(const GemmArgs& p, int mb, int nb, const f32x4& a, int frow, int fq) {
+    float v[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] = a[e];
+    if (p.bias) {
+        const u32x2 bb = *(const u32x2*)(p.bias + min(nb + 4 * fq, p.N - 4));
+        v[0] += in16<false>((bf16_t)(bb[0] & 0xffff));
+        v[1] += in16<false>((bf16_t)(bb[0] >> 16));
+        v[2] += in16<false>((bf16_t)(bb[1] & 0xffff));
+        v[3] += in16<false>((bf16_t)(bb[1] >> 16));
+    }
+    const uint64_t own = (uint64_t)pack16_2<false>(v[0], v[1]) | (uint64_t)pack16_2<false>(v[2], v[3]) << 32;
+    const int i = frow & 3;
+    // round r: the lane hands its element i ^ r to lane i ^ r of its quad and takes that lane's element i, which is row 4 a + (i ^ r)
+    uint64_t t = (own >> (16 * i) & 0xffffu) << (16 * i);
+    {
+        const int s1 = (int)(own >> (16 * (i ^ 1)) & 0xffffu);
+        const int r1 = __builtin_amdgcn_update_dpp(0, s1, 0xB1, 0xf, 0xf, true);      // quad_perm [1, 0, 3, 2]
+        t |= (uint64_t)(uint32_t)r1 << (16 * (i ^ 1));
+        const int s2 = (int)(own >> (16 * (i ^ 2)) & 0xffffu);
+        const int r2 = __builtin_amdgcn_update_dpp(0, s2, 0x4E, 0xf, 0xf, true);      // quad_perm [2, 3, 0, 1]
+        t |= (uint64_t)(uint32_t)r2 << (16 * (i ^ 2));
+        const int s3 = (int)(own >> (16 * (i ^ 3)) & 0xffffu);
+        const int r3 = __builtin_amdgcn_update_dpp(0, s3, 0x1B, 0xf, 0xf, true);      // quad_perm [3, 2, 1, 0]
+        t |= (uint64_t)(uint32_t)r3 << (16 * (i ^ 3));
+    }
+    const int n = nb + 4 * fq + i, m = mb + (frow & ~3);
+    if (n >= p.N || m >= p.M) return;
+    bf16_t* op = (bf16_t*)p.out + (long)n * p.ldo + m;
+    if (m + 3 < p.M) {
+        *(u32x2*)op = (u32x2){(uint32_t)t, (uint32_t)(t >> 32)};
+    } else {
+        for (int e = 0; e < 4 && m + e < p.M; ++e) op[e] = (bf16_t)(t >> (16 * e) & 0xffffu);
+    }
+}
+
 template <int BM, int BN, int WM, int WN, int NS, int EPI>
 __global__ __launch_bounds__(WM* WN * 64) void gemm_mx_nt_kernel(MxArgs q) {
     const GemmArgs& p = q.g;
@@ -179,6 +220,19 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_mx_nt_kernel(MxArgs q) {
                 av[j * TN + i] = acc[i][j];
             }
         epi_rmw_pipe<EPI, NF, (NF >= 8 ? 4 : 2)>(p, mb, nb, av, frow, fq);
+    } else if constexpr (EPI == UV_EPI_BF16_SSQ) {
+        static_assert(TN % 2 == 0 && (BN / WN) % 32 == 0, "UV_EPI_BF16_SSQ needs whole 32-column groups per wave");
+#pragma unroll
+        for (int j = 0; j < TM; ++j)
+#pragma unroll
+            for (int i = 0; i < TN; i += 2)
+                epi_pair_ssq<false>(p, m0 + wm * (BM / WM) + j * 16, n0 + wn * (BN / WN) + i * 16, acc[i][j], acc[i + 1][j], frow, fq);
+    } else if constexpr (EPI == UV_EPI_BF16_T) {
+#pragma unroll
+        for (int j = 0; j < TM; ++j)
+#pragma unroll
+            for (int i = 0; i < TN; ++i)
+                epi_frag_mx_t(p, m0 + wm * (BM / WM) + j * 16, n0 + wn * (BN / WN) + i * 16, acc[i][j], frow, fq);
     } else {
 #pragma unroll
         for (int j = 0; j < TM; ++j)
@@ -210,70 +264,103 @@ static MxArgs mx_rows_of(const MxArgs& a, int epilogue, long m0, int rows) {
     r.g.A = (const bf16_t*)((const uint8_t*)a.g.A + m0 * a.g.lda);
     r.As = a.As + m0 * a.ld_as;
     if (a.g.gate_tid) r.g.gate_tid = a.g.gate_tid + m0;
-    if (epilogue == UV_EPI_BF16 || epilogue == UV_EPI_GELU_BF16) r.g.out = (bf16_t*)a.g.out + m0 * a.g.ldo;
+    if (a.g.ssq) r.g.ssq = a.g.ssq + m0 * a.g.ld_ssq;
+    if (epilogue == UV_EPI_BF16_T) r.g.out = (bf16_t*)a.g.out + m0;
+    else if (epilogue == UV_EPI_BF16 || epilogue == UV_EPI_GELU_BF16 || epilogue == UV_EPI_BF16_SSQ) r.g.out = (bf16_t*)a.g.out + m0 * a.g.ldo;
     else r.g.out = (float*)a.g.out + m0 * a.g.ldo;
     return r;
 }
 
 constexpr unsigned UV_MX_EPIS = 1u << UV_EPI_BF16 | 1u << UV_EPI_GELU_BF16 | 1u << UV_EPI_F32_FROM_BF16 | 1u << UV_EPI_RESID_F32 |
                                 1u << UV_EPI_GATE_RESID_F32;
+// (every epilogue the kernel is built with; each entry point accepts its own subset: uv_gemm_mxfp8_nt the five above)
+constexpr unsigned UV_MX_EPIS_BUILT = UV_MX_EPIS | 1u << UV_EPI_BF16_T | 1u << UV_EPI_BF16_SSQ;
 
 template <int BM, int BN, int WM, int WN, int NS>
-static int launch_mx(const MxArgs& a0, int epi, hipStream_t stream) {
+static int launch_mx(const MxArgs& a0, int epi, const char* fn, hipStream_t stream) {
     MxArgs a = a0;
     a.g.tiles_m = (a.g.M + BM - 1) / BM;
     a.g.tiles_n = a.g.N / BN;
     const dim3 grid(a.g.tiles_m * a.g.tiles_n);
     constexpr int LDS = NS * (BM + BN) * 132;
-    return launch_epi<UV_MX_EPIS>(epi, [&](auto e) {
+    return launch_epi<UV_MX_EPIS_BUILT>(epi, [&](auto e) {
         auto kern = gemm_mx_nt_kernel<BM, BN, WM, WN, NS, decltype(e)::value>;
         UV_ONCE_PER_DEVICE(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
         hipLaunchKernelGGL(kern, grid, dim3(WM * WN * 64), LDS, stream, a);
-        UV_CHECK_LAUNCH("uv_gemm_mxfp8_nt");
+        UV_CHECK_LAUNCH(fn);
         return 0;
     });
 }
 
-extern "C" int uv_gemm_mxfp8_nt(const void* A, long lda, const void* A_scale, long ld_as, const void* W, long ldw, const void* W_scale,
-                                long ld_ws, const void* bias_bf16, int M, int N, int K, int epilogue, void* out, long ldo,
-                                const float* gate, const int32_t* gate_tid, long gate_stride, void* stream) {
-    UV_CHECK_ARG(A && W && out, "uv_gemm_mxfp8_nt: null pointer");
-    UV_CHECK_ARG(A_scale && W_scale, "uv_gemm_mxfp8_nt: null scale pointer");
-    UV_CHECK_ARG(M > 0 && N > 0 && K > 0, "uv_gemm_mxfp8_nt: bad shape M=%d N=%d K=%d", M, N, K);
-    UV_CHECK_ARG(K % 128 == 0, "uv_gemm_mxfp8_nt: K=%d must be a multiple of 128", K);
-    UV_CHECK_ARG(N % 256 == 0, "uv_gemm_mxfp8_nt: N=%d must be a multiple of 256", N);
-    UV_CHECK_ARG(epi_in(UV_MX_EPIS, epilogue), "uv_gemm_mxfp8_nt: epilogue %d is not built for MXFP8 operands (0 - 4 are)", epilogue);
-    UV_CHECK_ARG(lda >= K && ldw >= K && lda % 16 == 0 && ldw % 16 == 0, "uv_gemm_mxfp8_nt: lda/ldw must be >= K and multiples of 16 bytes");
+// The one body of the three entry points. `fn`: the entry point's name (error texts); `epis`: the epilogues it accepts.
+static int gemm_mx_entry(const char* fn, unsigned epis, const void* A, long lda, const void* A_scale, long ld_as, const void* W, long ldw,
+                         const void* W_scale, long ld_ws, const void* bias_bf16, int M, int N, int K, int epilogue, void* out, long ldo,
+                         const float* gate, const int32_t* gate_tid, long gate_stride, float* ssq, long ld_ssq, void* stream) {
+    UV_CHECK_ARG(A && W && out, "%s: null pointer", fn);
+    UV_CHECK_ARG(A_scale && W_scale, "%s: null scale pointer", fn);
+    UV_CHECK_ARG(M > 0 && N > 0 && K > 0, "%s: bad shape M=%d N=%d K=%d", fn, M, N, K);
+    UV_CHECK_ARG(K % 128 == 0, "%s: K=%d must be a multiple of 128", fn, K);
+    UV_CHECK_ARG(N % 256 == 0, "%s: N=%d must be a multiple of 256", fn, N);
+    UV_CHECK_ARG(epi_in(epis, epilogue), "%s: epilogue %d is not built for MXFP8 operands here", fn, epilogue);
+    UV_CHECK_ARG(lda >= K && ldw >= K && lda % 16 == 0 && ldw % 16 == 0, "%s: lda/ldw must be >= K and multiples of 16 bytes", fn);
     UV_CHECK_ARG(ld_as >= K / 32 && ld_ws >= K / 32 && ld_as % 4 == 0 && ld_ws % 4 == 0,
-                 "uv_gemm_mxfp8_nt: ld_as/ld_ws must be >= K / 32 = %d and multiples of 4 (ld_as=%ld ld_ws=%ld)", K / 32, ld_as, ld_ws);
+                 "%s: ld_as/ld_ws must be >= K / 32 = %d and multiples of 4 (ld_as=%ld ld_ws=%ld)", fn, K / 32, ld_as, ld_ws);
     UV_CHECK_ARG(((uintptr_t)A & 15) == 0 && ((uintptr_t)W & 15) == 0 && ((uintptr_t)out & 15) == 0,
-                 "uv_gemm_mxfp8_nt: pointers must be 16-byte aligned");
+                 "%s: pointers must be 16-byte aligned", fn);
     UV_CHECK_ARG(((uintptr_t)A_scale & 3) == 0 && ((uintptr_t)W_scale & 3) == 0 && ((uintptr_t)bias_bf16 & 7) == 0,
-                 "uv_gemm_mxfp8_nt: scale pointers must be 4-byte, the bias 8-byte aligned");
-    UV_CHECK_ARG((long)M * ld_as < (1L << 31) && (long)N * ld_ws < (1L << 31), "uv_gemm_mxfp8_nt: scale arrays of 2 GiB and more are not supported");
-    UV_CHECK_ARG(ldo >= N && ldo % 4 == 0, "uv_gemm_mxfp8_nt: ldo must be >= N and a multiple of 4 elements");
+                 "%s: scale pointers must be 4-byte, the bias 8-byte aligned", fn);
+    UV_CHECK_ARG((long)M * ld_as < (1L << 31) && (long)N * ld_ws < (1L << 31), "%s: scale arrays of 2 GiB and more are not supported", fn);
+    if (epilogue == UV_EPI_BF16_T)
+        UV_CHECK_ARG(ldo >= M && ldo % 4 == 0, "%s: ldo must be >= M and a multiple of 4 elements", fn);
+    else
+        UV_CHECK_ARG(ldo >= N && ldo % 4 == 0, "%s: ldo must be >= N and a multiple of 4 elements", fn);
+    if (epilogue == UV_EPI_BF16_SSQ)
+        UV_CHECK_ARG(ssq && ((uintptr_t)ssq & 3) == 0 && ld_ssq >= N / 32, "%s: ssq required, ld_ssq >= N / 32 = %d (ld_ssq=%ld)", fn, N / 32, ld_ssq);
     if (epilogue == UV_EPI_GATE_RESID_F32)
-        UV_CHECK_ARG(gate && gate_stride % 4 == 0, "uv_gemm_mxfp8_nt: gate table required (stride %% 4 == 0)");
+        UV_CHECK_ARG(gate && gate_stride % 4 == 0, "%s: gate table required (stride %% 4 == 0)", fn);
     MxArgs a;
     GemmArgs& g = a.g;
     g.A = (const bf16_t*)A; g.W = (const bf16_t*)W; g.bias = (const bf16_t*)bias_bf16;
     g.out = out; g.gate = gate; g.gate_tid = gate_tid;
     g.lda = lda; g.ldw = ldw; g.ldo = ldo; g.gate_stride = gate_stride;
     g.M = M; g.N = N; g.K = K; g.tiles_m = g.tiles_n = 0;
-    g.ssq = nullptr; g.ld_ssq = 0; g.ws_slab = nullptr; g.ws_cnt = nullptr; g.gm = 0;
+    g.ssq = ssq; g.ld_ssq = ld_ssq; g.ws_slab = nullptr; g.ws_cnt = nullptr; g.gm = 0;
     g.zeros = uv_zero_page();
-    UV_CHECK_ARG(g.zeros, "uv_gemm_mxfp8_nt: zero page missing (call uv_init)");
+    UV_CHECK_ARG(g.zeros, "%s: zero page missing (call uv_init)", fn);
     a.As = (const uint8_t*)A_scale; a.Ws = (const uint8_t*)W_scale;
     a.ld_as = ld_as; a.ld_ws = ld_ws;
     const MxPlan plan = plan_gemm_mx(M, N, uv_num_cus());
     for (int i = 0; i < plan.n; ++i) {
         const MxStep& st = plan.step[i];
         const MxArgs r = mx_rows_of(a, epilogue, st.m0, st.rows);
-        const int rc = st.kernel == MK_T256 ? launch_mx<256, 256, 2, 4, 2>(r, epilogue, (hipStream_t)stream)
-                                            : launch_mx<128, 128, 2, 2, 2>(r, epilogue, (hipStream_t)stream);
+        const int rc = st.kernel == MK_T256 ? launch_mx<256, 256, 2, 4, 2>(r, epilogue, fn, (hipStream_t)stream)
+                                            : launch_mx<128, 128, 2, 2, 2>(r, epilogue, fn, (hipStream_t)stream);
         if (rc) return rc;
     }
     return 0;
+}
+
+extern "C" int uv_gemm_mxfp8_nt(const void* A, long lda, const void* A_scale, long ld_as, const void* W, long ldw, const void* W_scale,
+                                long ld_ws, const void* bias_bf16, int M, int N, int K, int epilogue, void* out, long ldo,
+                                const float* gate, const int32_t* gate_tid, long gate_stride, void* stream) {
+    return gemm_mx_entry("uv_gemm_mxfp8_nt", UV_MX_EPIS, A, lda, A_scale, ld_as, W, ldw, W_scale, ld_ws, bias_bf16, M, N, K, epilogue, out, ldo,
+                         gate, gate_tid, gate_stride, nullptr, 0, stream);
+}
+
+// outT[n][m] = the bits uv_gemm_mxfp8_nt(UV_EPI_BF16) writes at [m][n] (V^T for the attention kernels): same checks, plan and K chain.
+extern "C" int uv_gemm_mxfp8_nt_t(const void* A, long lda, const void* A_scale, long ld_as, const void* W, long ldw, const void* W_scale,
+                                  long ld_ws, const void* bias_bf16, int M, int N, int K, void* outT, long ldo, void* stream) {
+    return gemm_mx_entry("uv_gemm_mxfp8_nt_t", 1u << UV_EPI_BF16_T, A, lda, A_scale, ld_as, W, ldw, W_scale, ld_ws, bias_bf16, M, N, K,
+                         UV_EPI_BF16_T, outT, ldo, nullptr, nullptr, 0, nullptr, 0, stream);
+}
+
+// UV_EPI_BF16's output plus ssq[m][n / 32], the header's one summation order (ssq_group32): the cross-attention q projection in front of
+// uv_rms_scale_from_ssq and the q-norm attention kernel.
+extern "C" int uv_gemm_mxfp8_nt_ssq(const void* A, long lda, const void* A_scale, long ld_as, const void* W, long ldw, const void* W_scale,
+                                    long ld_ws, const void* bias_bf16, int M, int N, int K, void* out, long ldo, float* ssq, long ld_ssq,
+                                    void* stream) {
+    return gemm_mx_entry("uv_gemm_mxfp8_nt_ssq", 1u << UV_EPI_BF16_SSQ, A, lda, A_scale, ld_as, W, ldw, W_scale, ld_ws, bias_bf16, M, N, K,
+                         UV_EPI_BF16_SSQ, out, ldo, nullptr, nullptr, 0, ssq, ld_ssq, stream);
 }
 
 // ---- quantiser ------------------------------------------------------------------------------------------------------------------------

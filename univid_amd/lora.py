@@ -205,6 +205,11 @@ def attach_adapter_(model: nn.Module, name: str, factors, cfg: dict, weight: flo
                 f"{path!r}: an un-merged adapter (merge=False) on ffn.0 / ffn.2 cannot be combined with ffn_precision 'mxfp8' (the MXFP8 GEMM "
                 f"has no adapter slot). Merge the adapter (merge=True: the merged weights are re-quantised) or call "
                 f"set_ffn_precision('bf16') first. Un-merged adapters on the attention projections work in both modes.")
+        if getattr(own, "proj_precision", "bf16") == "mxfp8" and any(lin is getattr(own, n, None) for n in getattr(own, "_mx_proj", ())):
+            raise NotImplementedError(
+                f"{path!r}: an un-merged adapter (merge=False) on self_attn.q / k / v / o or cross_attn.q / o cannot be combined with "
+                f"proj_precision 'mxfp8' (the MXFP8 GEMM has no adapter slot). Merge the adapter (merge=True: the merged weights are "
+                f"re-quantised) or call set_proj_precision('bf16') first. Un-merged adapters on cross_attn.k / v work in both modes.")
         todo.append((path, lin, a, b, module_scaling(cfg, path, a.shape[0])))
     for path, lin, a, b, s in todo:
         dev = lin.weight.device

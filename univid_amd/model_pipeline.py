@@ -54,6 +54,7 @@ class CrossAttentionConfig:
     lora_target_strategy: str = "your_method_here"
     lora_merge: bool = True       # CrossAttentionFusionPipeline.load_lora: fold the adapter into the dense weights (False: attach it un-merged)
     ffn_precision: str = "bf16"   # "mxfp8": the DiT's ffn.0 / ffn.2 on MXFP8 operands (WanModel.set_ffn_precision), an opt-in fast mode
+    proj_precision: str = "bf16"  # "mxfp8": the DiT's self-attention q / k / v / o and cross-attention q / o projections on MXFP8 operands (WanModel.set_proj_precision), an opt-in experimental mode
     attn_precision: str = "bf16"  # "mxfp8_qk" / "mxfp8_qk_pv": the DiT's self-attention q / k (and P.V) as MXFP8 (WanModel.set_attn_precision), opt-in experimental modes
     guidance_strength: float = 1.0
     bagel_cross_attn_layers: List[int] = None
@@ -384,6 +385,9 @@ class CrossAttentionFusionPipeline:
         attn_precision = getattr(config, "attn_precision", "bf16")
         if attn_precision != "bf16" and hasattr(self.dit_model, "set_attn_precision") and attn_precision != self.dit_model.attn_precision:
             self.dit_model.set_attn_precision(attn_precision)
+        proj_precision = getattr(config, "proj_precision", "bf16")
+        if proj_precision != "bf16" and hasattr(self.dit_model, "set_proj_precision") and proj_precision != self.dit_model.proj_precision:
+            self.dit_model.set_proj_precision(proj_precision)
         self.vae_model = wan_pipeline.vae
         self.text_encoder = wan_pipeline.text_encoder
         # native_text_weight=False: the reference's closures on the model's generic path (kept as the comparison the tests and bench use)
@@ -412,7 +416,8 @@ class CrossAttentionFusionPipeline:
         try:
             return WanTI2V(config=wan_config, checkpoint_dir=path, device_id=self.config.wan_gpu, rank=0, t5_fsdp=False, dit_fsdp=False,
                            use_sp=False, ffn_precision=getattr(self.config, "ffn_precision", "bf16"),
-                           attn_precision=getattr(self.config, "attn_precision", "bf16"))
+                           attn_precision=getattr(self.config, "attn_precision", "bf16"),
+                           proj_precision=getattr(self.config, "proj_precision", "bf16"))
         except Exception as e:
             raise RuntimeError(f"Wan2.2 initialization failed: {e}") from e
 

@@ -111,6 +111,32 @@ def _check_ffn_precision(mode, dim, ffn_dim, ffn):
                 "Un-merged adapters on the attention projections work in both modes.")
 
 
+PROJ_PRECISIONS = ("bf16", "mxfp8")
+
+
+def _check_proj_precision(mode, dim, attns):
+    """set_proj_precision's guards on one block's geometry and its attention modules: raises before any state changes."""
+    if mode not in PROJ_PRECISIONS:
+        raise ValueError(f"proj_precision {mode!r}: one of {PROJ_PRECISIONS}")
+    if mode == "mxfp8":
+        if dim % 256:
+            raise ValueError(f"proj_precision 'mxfp8' needs dim to be a multiple of 256 (dim {dim}): uv_gemm_mxfp8_nt takes N % 256 == 0 and "
+                             "K % 128 == 0, uv_layernorm_mod_mx C % 256 == 0")
+        if any(getattr(getattr(a, n), "_uv_lora", None) for a in attns for n in a._mx_proj):
+            raise NotImplementedError(
+                "proj_precision 'mxfp8' and an un-merged LoRA adapter (merge=False) on self_attn.q / k / v / o or cross_attn.q / o cannot be "
+                "combined: the MXFP8 GEMM has no adapter slot. Detach the adapter or merge it (merge=True: the merged weights are "
+                "re-quantised), or keep proj_precision 'bf16'. Un-merged adapters on cross_attn.k / v work in both modes.")
+
+
+def _mx_act(t, M, K):
+    """bf16 activation [>= M, >= K] -> its MXFP8 form (codes, scales) over M rows (uv_mx_quant_bf16): the input of an MXFP8 projection."""
+    c = torch.empty(M, K, dtype=torch.uint8, device=t.device)
+    sc = torch.empty(M, K // 32, dtype=torch.uint8, device=t.device)
+    _lib.mx_quant(t, c, sc, M=M, K=K)
+    return c, sc
+
+
 # ---- un-merged LoRA (univid_amd/lora.py attaches; peft lora/layer.py Linear.forward) ---------------------------------------------
 # An attached adapter lives on its nn.Linear as `lin._uv_lora = {adapter name: {"A": [r, in], "B": [out, r], "scaling": s, "weight": w}}`
 # and never touches the fp32 master weight. The projections that read ONE activation share one slot of whole 128-column groups behind
@@ -241,12 +267,21 @@ class WanSelfAttention(nn.Module):
         self._slots = {}
         self._kv_cache = {}
         self.attn_precision = "bf16"     # WanModel.set_attn_precision: instance state, never a module global
+        self.proj_precision = "bf16"     # WanModel.set_proj_precision: likewise
 
     _groups = {"qkv": ("q", "k", "v"), "o": ("o",)}      # projections by the activation they read (one LoRA slot each)
+    _mx_proj = ("q", "k", "v", "o")                      # the projections proj_precision "mxfp8" puts on uv_gemm_mxfp8_nt
 
     def prepare(self):
         self._prep, self._slots = {}, {}
+        mx = self.proj_precision == "mxfp8"
+        if mx:
+            _check_proj_precision("mxfp8", self.dim, (self,))
         for g, names in self._groups.items():
+            if mx and all(n in self._mx_proj for n in names):       # codes + scales; the bf16 operand copies are not kept, no slot
+                self._prep.update({n: _PreparedMx(getattr(self, n)) for n in names})
+                self._slots[g] = None
+                continue
             preps, self._slots[g] = _prepare_group({n: getattr(self, n) for n in names})
             self._prep.update(preps)
         self._kv_cache = {}
@@ -256,6 +291,15 @@ class WanSelfAttention(nn.Module):
         per-sample adapter weights): the slot's down-projection, then q and k as bf16 [M, C] (returned) and V^T into vt's first M columns
         (sample b = columns b*seg_rows..)."""
         C, p = self.dim, self._prep
+        if self.proj_precision == "mxfp8":
+            # h = (codes, scales) of the modulated input (uv_layernorm_mod_mx, or mx_quant of a bf16 input): the three GEMMs on MXFP8 operands
+            hc, hs = h
+            ql = torch.empty(M, C, dtype=BF16, device=hc.device)
+            kl = torch.empty(M, C, dtype=BF16, device=hc.device)
+            _lib.gemm_mxfp8(hc, hs, p["q"].w, p["q"].s, p["q"].b, ql, EPI_BF16, M=M)
+            _lib.gemm_mxfp8(hc, hs, p["k"].w, p["k"].s, p["k"].b, kl, EPI_BF16, M=M)
+            _lib.gemm_mxfp8_t(hc, hs, p["v"].w, p["v"].s, p["v"].b, vt, M=M)
+            return ql, kl
         h = _slotted(h, C, self._slots["qkv"], M, seg_rows, s0)
         ql = torch.empty(M, C, dtype=BF16, device=h.device)
         kl = torch.empty(M, C, dtype=BF16, device=h.device)
@@ -265,25 +309,27 @@ class WanSelfAttention(nn.Module):
         return ql, kl
 
     def _attn(self, h, L, Lk, grid, freqs, batch, s0):
-        """Self-attention of h (bf16 [batch*L, C], samples stacked along the token axis) over each sample's first Lk keys (Lk < L: the
-        rest of L is padding; one sample only) -> the attention output as the o projection reads it."""
+        """Self-attention of h (bf16 [batch*L, C], samples stacked along the token axis; proj_precision "mxfp8": its (codes, scales)) over
+        each sample's first Lk keys (Lk < L: the rest of L is padding; one sample only) -> the attention output (bf16) as the o projection
+        reads it (proj_precision "mxfp8": as _o_proj quantises it)."""
         C, H, D = self.dim, self.num_heads, self.head_dim
         M = batch * L
-        vt = _vt_scratch("vt", C, batch, L, h.device)
+        dev = h[0].device if isinstance(h, tuple) else h.device
+        vt = _vt_scratch("vt", C, batch, L, dev)
         ql, kl = self._qkv(h, M, L, s0, vt)
-        att = _act_buf(M, C, (self._slots["o"],), h.device)
+        att = _act_buf(M, C, (self._slots["o"],), dev)
         if self.attn_precision != "bf16":
             # q and k leave the norm + RoPE pass as MXFP8 codes + scales (fresh buffers: no in-place form), S = K Q^T on the block-scaled
             # matrix instruction; "mxfp8_qk": V^T, P.V and the output stay bf16
-            qc, kc = (torch.empty(M, C, dtype=torch.uint8, device=h.device) for _ in range(2))
-            qs, ks = (torch.empty(M, C // 32, dtype=torch.uint8, device=h.device) for _ in range(2))
+            qc, kc = (torch.empty(M, C, dtype=torch.uint8, device=dev) for _ in range(2))
+            qs, ks = (torch.empty(M, C // 32, dtype=torch.uint8, device=dev) for _ in range(2))
             _lib.rmsnorm_rope_qk_mx(ql, kl, self.norm_q.weight, self.norm_k.weight, qc, qs, kc, ks, M, L, C, D, self.eps, freqs, grid)
             if self.attn_precision == "mxfp8_qk_pv":
                 # the bf16 V^T of the GEMM (un-merged LoRA included) quantised along the keys into stable scratch (every byte, pads
                 # included, is rewritten per call), P as e4m3: P.V on the block-scaled instruction too. Lk < L: one sample, its first Lk keys
                 cols = _lib.vt_mx_cols(batch, L)
-                vc = _mx_scratch("vt_codes", (C, cols), h.device)
-                vs = _mx_scratch("vt_scales", (H, 4 * cols), h.device)
+                vc = _mx_scratch("vt_codes", (C, cols), dev)
+                vs = _mx_scratch("vt_scales", (H, 4 * cols), dev)
                 if Lk == L:
                     _lib.vt_mx_quant(vt, vc, vs, L, H, D, batch=batch)
                 else:
@@ -303,9 +349,17 @@ class WanSelfAttention(nn.Module):
         s0: the first stacked sample's index among the samples of per-sample adapter weights (WanModel.set_adapter_weights)."""
         if sp is not None:
             return self._self_attn_sp(h, L, grid, freqs, x_resid, gate, gate_tid, batch, sp, s0=s0)
+        self._o_proj(self._attn(h, L, L, grid, freqs, batch, s0), x_resid, EPI_GATE_RESID_F32, batch * L, gate=gate, gate_tid=gate_tid)
+
+    def _o_proj(self, att, out, epi, M, gate=None, gate_tid=None):
+        """The o projection of the attention output att (bf16, its slot filled) into `out` through epilogue `epi`; proj_precision "mxfp8":
+        one quantise pass over att (the attention kernels store bf16), then the MXFP8 GEMM with the same epilogue."""
         p = self._prep["o"]
-        _lib.gemm_bf16(self._attn(h, L, L, grid, freqs, batch, s0), p.w, p.b, x_resid, EPI_GATE_RESID_F32, M=batch * L, gate=gate,
-                       gate_tid=gate_tid)
+        if self.proj_precision == "mxfp8":
+            ac, asc = _mx_act(att, M, self.dim)
+            _lib.gemm_mxfp8(ac, asc, p.w, p.s, p.b, out, epi, M=M, gate=gate, gate_tid=gate_tid)
+        else:
+            _lib.gemm_bf16(att, p.w, p.b, out, epi, M=M, gate=gate, gate_tid=gate_tid)
 
     def _self_attn_sp(self, h, n, grid, freqs, x_resid, gate, gate_tid, batch, sp, s0=0):
         """Ulysses form (distributed/sequence_parallel.py:147-176, ulysses.py:9-47): projections, RMSNorm and RoPE on the
@@ -314,6 +368,9 @@ class WanSelfAttention(nn.Module):
         if self.attn_precision != "bf16":
             raise NotImplementedError(f"attn_precision {self.attn_precision!r} is not built for the sequence-parallel forward (the Ulysses "
                                       f"exchange carries bf16 q / k): set_attn_precision('bf16') or run without sequence parallelism")
+        if self.proj_precision != "bf16":
+            raise NotImplementedError(f"proj_precision {self.proj_precision!r} is not built for the sequence-parallel forward (its projections "
+                                      f"read a bf16 activation): set_proj_precision('bf16') or run without sequence parallelism")
         par, Lt, r0 = sp
         C, H, D = self.dim, self.num_heads, self.head_dim
         P = par.size
@@ -351,11 +408,14 @@ class WanSelfAttention(nn.Module):
         _ensure_prepared(self)
         outs = []
         fr = _freqs_device(freqs, x.device)
-        L, p = x.size(1), self._prep["o"]
+        L = x.size(1)
         for b in range(x.size(0)):      # (sample b of the batch takes its own row of per-sample adapter weights)
-            att = self._attn(x[b].to(BF16).contiguous(), L, int(seq_lens[b]), tuple(int(v) for v in grid_sizes[b]), fr, 1, b)
+            xb = x[b].to(BF16).contiguous()
+            if self.proj_precision == "mxfp8":
+                xb = _mx_act(xb, L, self.dim)
+            att = self._attn(xb, L, int(seq_lens[b]), tuple(int(v) for v in grid_sizes[b]), fr, 1, b)
             y = torch.empty(L, self.dim, dtype=BF16, device=x.device)
-            _lib.gemm_bf16(att, p.w, p.b, y, EPI_BF16, M=L)
+            self._o_proj(att, y, EPI_BF16, L)
             outs.append(y)
         return torch.stack(outs)
 
@@ -365,6 +425,7 @@ class WanCrossAttention(WanSelfAttention):
     part of UniVid's contract: Wan22ContextWrapper finds modules by `__class__.__name__ == 'WanCrossAttention'`
     and replaces `module.forward` with a closure that rescales `context` (model_pipeline.py:1745-1807)."""
     _groups = {"q": ("q",), "kv": ("k", "v"), "o": ("o",)}
+    _mx_proj = ("q", "o")       # k / v are context-side, computed once per generation: they stay bf16 in proj_precision "mxfp8"
     _s0 = 0     # a re-assigned `forward` (UniVid's closure) calls the original with (x, context, None) and cannot carry the sample offset:
                 # the block sets this around THAT call only (WanAttentionBlock._run); every other path takes s0 as an argument
 
@@ -401,16 +462,27 @@ class WanCrossAttention(WanSelfAttention):
         return kl, vt
 
     def _attend(self, hq, ctx, L, Lc, batch=1, kv_key=None, kv=None, s0=0):
-        """hq bf16 [batch*L, C] (normed queries' input), ctx bf16 [batch*Lc, C] -> attention output bf16 [batch*L, C].
+        """hq bf16 [batch*L, C] (normed queries' input; proj_precision "mxfp8": its (codes, scales)), ctx bf16 [batch*Lc, C] -> attention
+        output bf16 [batch*L, C].
         kv = (k, V^T) of the stacked contexts in the caller's own buffers (WanModel.forward's context_kv=): ctx is then not read."""
         C, H, D = self.dim, self.num_heads, self.head_dim
         p = self._prep
-        dev = hq.device
+        mx = self.proj_precision == "mxfp8"
+        dev = hq[0].device if mx else hq.device
         M = batch * L
-        hq = _slotted(hq, C, self._slots["q"], M, L, s0)
+        if not mx:
+            hq = _slotted(hq, C, self._slots["q"], M, L, s0)
         ql = torch.empty(M, C, dtype=BF16, device=dev)
         kl, vt = kv if kv is not None else self._context_kv(ctx, Lc, batch, kv_key, s0=s0)
         att = _act_buf(M, C, (self._slots["o"],), dev)
+        if mx:
+            # the q projection on MXFP8 operands with the sums of squares in its epilogue; norm_q and the attention are the bf16 path's
+            ssq = torch.empty(M, C // 32, dtype=torch.float32, device=dev)
+            rs = torch.empty(M, dtype=torch.float32, device=dev)
+            _lib.gemm_mxfp8_ssq(hq[0], hq[1], p["q"].w, p["q"].s, p["q"].b, ql, ssq, M=M)
+            _lib.rms_scale_from_ssq(ssq, rs, M, C, self.eps)
+            _lib.flash_attn(ql, kl, vt, att, L, Lc, H, D, 1.0 / math.sqrt(D), batch=batch, q_rs=rs, q_weight=self.norm_q.weight)
+            return att
         if C % 32 == 0:
             # norm_q without a pass of its own over q (round 5): the q GEMM's epilogue leaves each output row's sums of squares per 32-column
             # group, a tiny kernel turns them into the row scale 1 / sqrt(mean + eps), and the attention kernel's Q prologue applies scale and
@@ -428,8 +500,7 @@ class WanCrossAttention(WanSelfAttention):
 
     def _cross_fused(self, hq, ctx, L, Lc, x_resid, batch=1, kv_key=None, kv=None, s0=0):
         att = _slotted(self._attend(hq, ctx, L, Lc, batch, kv_key, kv, s0), self.dim, self._slots["o"], batch * L, L, s0)
-        p = self._prep["o"]
-        _lib.gemm_bf16(att, p.w, p.b, x_resid, EPI_RESID_F32, M=batch * L)
+        self._o_proj(att, x_resid, EPI_RESID_F32, batch * L)
 
     def forward(self, x, context, context_lens=None):
         """x [B, L1, C], context [B, L2, C] -> [B, L1, C] bf16 (the caller adds it to the residual stream)."""
@@ -437,13 +508,15 @@ class WanCrossAttention(WanSelfAttention):
             raise NotImplementedError("context_lens is always None on UniVid's path (model.py:472)")
         _ensure_prepared(self)
         outs = []
-        L, Lc, p = x.size(1), context.size(1), self._prep["o"]
+        L, Lc = x.size(1), context.size(1)
         for b in range(x.size(0)):
             s0 = self._s0 + b       # (sample b of the batch takes its own row of per-sample adapter weights)
-            att = _slotted(self._attend(x[b].to(BF16).contiguous(), context[b].to(BF16).contiguous(), L, Lc, s0=s0), self.dim,
-                           self._slots["o"], s0=s0)
+            xb = x[b].to(BF16).contiguous()
+            if self.proj_precision == "mxfp8":
+                xb = _mx_act(xb, L, self.dim)
+            att = _slotted(self._attend(xb, context[b].to(BF16).contiguous(), L, Lc, s0=s0), self.dim, self._slots["o"], s0=s0)
             y = torch.empty(L, self.dim, dtype=BF16, device=x.device)
-            _lib.gemm_bf16(att, p.w, p.b, y, EPI_BF16)
+            self._o_proj(att, y, EPI_BF16, L)
             outs.append(y)
         return torch.stack(outs)
 
@@ -463,6 +536,7 @@ class WanAttentionBlock(nn.Module):
         self._prep = None
         self._slots = {}
         self.ffn_precision = "bf16"      # set_ffn_precision: instance state, never a module global
+        self.proj_precision = "bf16"     # set_proj_precision: likewise (the attention modules carry their own copy)
 
     def prepare(self):
         self.self_attn.prepare()
@@ -481,6 +555,17 @@ class WanAttentionBlock(nn.Module):
         (WanModel.set_attn_precision states the modes). No prepared weight depends on it."""
         _check_attn_precision(mode, self.self_attn.head_dim)
         self.self_attn.attn_precision = mode
+
+    def set_proj_precision(self, mode):
+        """"bf16" (default: the reference's arithmetic) or "mxfp8": this block's self-attention q / k / v / o and cross-attention q / o on
+        uv_gemm_mxfp8_nt, fed by uv_layernorm_mod_mx (WanModel.set_proj_precision states the mode). The projections' operands are
+        re-prepared on the next forward."""
+        _check_proj_precision(mode, self.dim, (self.self_attn, self.cross_attn))
+        self.proj_precision = mode
+        for a in (self.self_attn, self.cross_attn):
+            a.proj_precision = mode
+            a._prep = None
+            a._kv_cache = {}
 
     def _prepare_ffn(self):
         if self.ffn_precision == "mxfp8":
@@ -514,26 +599,46 @@ class WanAttentionBlock(nn.Module):
         # (rows of the block's bf16 activations: L, or L rounded up to whole 256-row tiles for ffn.0 - see below; the pad rows are never
         # written and their products never read, so they need no zeroing and no scratch that outlives the forward)
         Lf = _ffn0_rows(L, self.ffn_dim, dev)
-        h_full = _act_buf(Lf, C, (self.self_attn._slots["qkv"], self.cross_attn._slots["q"], self._slots["ffn0"]), dev)
-        h = h_full[:L]
+        mxp, mxf = self.proj_precision == "mxfp8", self.ffn_precision == "mxfp8"
+        hooked = "forward" in self.cross_attn.__dict__
+        # the block's bf16 activation, unless every producer below stores MXFP8 (uv_layernorm_mod_mx: no bf16 copy is written)
+        if not (mxp and mxf) or hooked or not self.cross_attn_norm or sp is not None:
+            h_full = _act_buf(Lf, C, (self.self_attn._slots["qkv"], self.cross_attn._slots["q"], self._slots["ffn0"]), dev)
+            h = h_full[:L]
+        if mxp or mxf:
+            u8 = torch.uint8
+            hq, hs = torch.empty(L, C, dtype=u8, device=dev), torch.empty(L, C // 32, dtype=u8, device=dev)
         # NOTE for consumers of `mid` (ffn.0's output, below): its rows >= L are the GELU of whatever the allocator left in h_full[L:]
         # - UNDEFINED, possibly NaN / Inf. Rows are independent in every kernel of the block and ffn.2 reads L rows only.
         # self-attention (model.py:243-247)
         twin = twin_rows and batch > 1 and sp is None and all(s is None or s.rows_equal(s0, batch) for s in self.self_attn._slots.values())
         # the rows and samples the self-attention half runs on: sample 0's for twins (no views on the common path: a slice costs the host
         # as much as a launch)
-        xa, ha, ta, nb = (x[:Ls], h[:Ls], None if tid is None else tid[:Ls], 1) if twin else (x, h, tid, batch)
-        _lib.layernorm_mod(xa, ha, nb * Ls, C, self.eps, mode=1, tab=tab, shift_off=0, scale_off=C, tid=ta, round_ln=first_block)
+        xa, ta, nb = (x[:Ls], None if tid is None else tid[:Ls], 1) if twin else (x, tid, batch)
+        if mxp and sp is None:
+            # norm1 + modulation stored as MXFP8: the bytes of layernorm_mod followed by mx_quant, without the bf16 round trip
+            _lib.layernorm_mod_mx(xa, hq, hs, nb * Ls, C, self.eps, mode=1, tab=tab, shift_off=0, scale_off=C, tid=ta, round_ln=first_block)
+            ha = (hq, hs)
+        else:       # (the sequence-parallel forward refuses the mode in _self_attn_sp)
+            ha = h[:Ls] if twin else h
+            _lib.layernorm_mod(xa, ha, nb * Ls, C, self.eps, mode=1, tab=tab, shift_off=0, scale_off=C, tid=ta, round_ln=first_block)
         self.self_attn._self_attn(ha, Ls, grid, freqs, xa, tab[:, 2 * C:], ta, nb, sp, s0=s0)
         for b in range(nb, batch):
             x[b * Ls:(b + 1) * Ls].copy_(x[:Ls])
         # cross-attention (model.py:251)
-        if self.cross_attn_norm:
+        hc = h if not mxp or hooked or not self.cross_attn_norm else None
+        if hc is None:
+            _lib.layernorm_mod_mx(x, hq, hs, L, C, self.eps, mode=2, w=self.norm3.weight, b=self.norm3.bias)
+            hc = (hq, hs)
+        elif self.cross_attn_norm:
             _lib.layernorm_mod(x, h, L, C, self.eps, mode=2, w=self.norm3.weight, b=self.norm3.bias)
         else:
             _lib.cast_f32_bf16(x, h, L, C)
+        if mxp and not hooked and not isinstance(hc, tuple):      # no norm3: the bf16 cast, then one quantise pass
+            _lib.mx_quant(h, hq, hs, M=L, K=C)
+            hc = (hq, hs)
         Lc = (ctx if kv is None else kv[0]).shape[0] // batch
-        if "forward" in self.cross_attn.__dict__:
+        if hooked:
             # forward was re-assigned on the instance (UniVid hook): honour it, then add the residual un-fused. The closure calls the original
             # forward(x, context, None), which reads the sample offset from the module: set for this call only
             self.cross_attn._s0 = s0
@@ -544,24 +649,24 @@ class WanAttentionBlock(nn.Module):
             y = y.reshape(L, C).contiguous()
             _lib.add_bf16_resid(x, y, L, C)
         else:
-            self.cross_attn._cross_fused(h, ctx, Ls, Lc, x, batch, kv_key, kv, s0)
+            self.cross_attn._cross_fused(hc, ctx, Ls, Lc, x, batch, kv_key, kv, s0)
         # FFN (model.py:252-255)
         # ffn.0 on rows rounded up to whole 256-row tiles where the extra tiles ride in the last, partial round of the persistent GEMM
         # (22 880 rows x 14 336 columns: 19.47 -> 19.69 rounds, both 20) instead of a leftover-row launch behind it: the pad rows of the
         # input hold whatever the buffer held (rows are independent: nothing of them reaches a row that is read), their outputs are never
         # read (ffn.2 runs on L rows); results unchanged (a row's arithmetic is the same in both kernels)
-        _lib.layernorm_mod(x, h, L, C, self.eps, mode=1, tab=tab, shift_off=3 * C, scale_off=4 * C, tid=tid)
-        if self.ffn_precision == "mxfp8":
-            # the opt-in fast mode: both projections' operands as OCP MXFP8 (quantised per row: no pad rows, no slot), same fused epilogues
-            p0, p2, F, u8 = self._prep["ffn0"], self._prep["ffn2"], self.ffn_dim, torch.uint8
-            hq, hs = torch.empty(L, C, dtype=u8, device=dev), torch.empty(L, C // 32, dtype=u8, device=dev)
-            _lib.mx_quant(h, hq, hs, M=L, K=C)
+        if mxf:
+            # the opt-in fast mode: both projections' operands as OCP MXFP8 (quantised per row: no pad rows, no slot), same fused epilogues.
+            # ffn.0's input leaves norm2 + modulation as MXFP8 (uv_layernorm_mod_mx: the bytes of layernorm_mod followed by mx_quant)
+            p0, p2, F = self._prep["ffn0"], self._prep["ffn2"], self.ffn_dim
+            _lib.layernorm_mod_mx(x, hq, hs, L, C, self.eps, mode=1, tab=tab, shift_off=3 * C, scale_off=4 * C, tid=tid)
             mid = torch.empty(L, F, dtype=BF16, device=dev)
             _lib.gemm_mxfp8(hq, hs, p0.w, p0.s, p0.b, mid, EPI_GELU_BF16, M=L)
             mq, ms = torch.empty(L, F, dtype=u8, device=dev), torch.empty(L, F // 32, dtype=u8, device=dev)
             _lib.mx_quant(mid, mq, ms)
             _lib.gemm_mxfp8(mq, ms, p2.w, p2.s, p2.b, x, EPI_GATE_RESID_F32, M=L, gate=tab[:, 5 * C:], gate_tid=tid)
             return
+        _lib.layernorm_mod(x, h, L, C, self.eps, mode=1, tab=tab, shift_off=3 * C, scale_off=4 * C, tid=tid)
         h_full = _slotted(h_full, C, self._slots["ffn0"], L, Ls, s0)
         mid = _act_buf(Lf, self.ffn_dim, (self._slots["ffn2"],), dev)
         _lib.gemm_bf16(h_full, self._prep["ffn0"].w, self._prep["ffn0"].b, mid, EPI_GELU_BF16, M=Lf)
@@ -783,6 +888,7 @@ class WanModel(nn.Module):
         self._text_weight = None  # (per-sample weights, rows, layers | None): set_text_weight
         self.ffn_precision = "bf16"  # set_ffn_precision
         self.attn_precision = "bf16"  # set_attn_precision
+        self.proj_precision = "bf16"  # set_proj_precision
         self.dedup_twins = True   # block 0's self-attention half once for samples that enter with identical rows (the CFG pair); A/B switch
         self.register_load_state_dict_post_hook(lambda m, _k: m.invalidate())
 
@@ -861,6 +967,27 @@ class WanModel(nn.Module):
         self.attn_precision = mode
         for b in self.blocks:
             b.set_attn_precision(mode)
+        self.invalidate()
+
+    def set_proj_precision(self, mode):
+        """Arithmetic of the attention projections of every block: "bf16" (default; like for like with the reference) or "mxfp8" - the
+        self-attention q / k / v / o and the cross-attention q / o Linears on OCP MXFP8 operands (uv_gemm_mxfp8_nt and its V^T / sums-of-
+        squares entry points), the activations produced as MXFP8 by the LayerNorm + modulation kernel itself (uv_layernorm_mod_mx; the
+        attention outputs by one quantise pass): a labelled, opt-in mode NARROWER than the reference's arithmetic (README). The blocks then
+        hold codes + scales instead of the bf16 copies of those six weights. Cross-attention k / v (context side, once per generation),
+        the attention cores and everything else are untouched. Merged LoRA works (re-quantised after invalidate()); an un-merged adapter
+        on a covered projection raises NotImplementedError here - and attaching one in the mode raises in LoRAManager -, un-merged
+        adapters on cross_attn.k / v keep working. Needs dim % 256 == 0 (ValueError otherwise). The sequence-parallel forward raises
+        NotImplementedError in the mode. Every guard runs before any state changes. Independent of set_ffn_precision and
+        set_attn_precision; all combinations are legal. Calls invalidate(): the prepared-weights generation moves on, so cached
+        cross-attention K / V^T and captured HIP graphs (WanTI2V) of the other mode can never be replayed."""
+        if not len(self.blocks):
+            _check_proj_precision(mode, self.dim, ())
+        for b in self.blocks:
+            _check_proj_precision(mode, b.dim, (b.self_attn, b.cross_attn))
+        self.proj_precision = mode
+        for b in self.blocks:
+            b.set_proj_precision(mode)
         self.invalidate()
 
     def prepare(self):
