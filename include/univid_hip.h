@@ -409,7 +409,7 @@ int uv_conv3d_f32(const float* in, long ld_in, int Tin, int Hin, int Win, const 
 /* The launch plan of a uv_conv3d_* call of this geometry on the current device (256 CUs without one) under the current UV_OPT_CONV_HALO:
  * the kernel's name (one of 23: 16 gather-kernel instantiations "G<rows>x<columns>+<prec>" / "G160+<prec>", 7 LDS-halo kernels "HALO_*"),
  * and its grid, tiles_m row tiles (halo kernels: pixel patches) x tiles_n output-channel tiles. prec: 0 uv_conv3d_f32, 1 / 2 uv_conv3d_bf16x3
- * without / with in_split, 3 uv_conv3d_bf16x6, 4 uv_conv3d_f16x3. Runs the geometry checks of the call itself. Host only. */
+ * without / with in_split, 3 uv_conv3d_bf16x6, 4 uv_conv3d_f16x3 (and uv_conv3d_f16, asked with HALF its Cin). Runs the geometry checks of the call itself. Host only. */
 int uv_conv3d_plan(int prec, int Tout, int Hout, int Wout, int Hin, int Win, int Cin, int Cout, int kt, int kh, int kw, int st, int sh,
                    int sw, int ph, int pw, int up, int interleave, char* kernel, int len, int* tiles_m, int* tiles_n);
 /* uv_conv3d_f32 with the products computed on the bf16 matrix pipe by exact three-way splitting of both f32 operands (x = x0 + x1 + x2,
@@ -443,6 +443,22 @@ int uv_split_weights_bf16x3(const float* w, void* out, long n, void* stream);
 int uv_conv3d_f16x3(const float* in, long ld_in, int Tin, int Hin, int Win, const void* w_split, const float* bias, float* out, long ldo,
                     int Tout, int Hout, int Wout, int Cin, int Cout, int kt, int kh, int kw, int st, int sh, int sw, int t_off, int ph,
                     int pw, int up, int interleave, const float* resid, long ldr, float w_scale, const float* act_scale, void* stream);
+/* The same convolution in ONE fp16 MFMA pass ("f16"): an opt-in NARROW arithmetic (11-bit operands), a third of f16x3's MFMA work and half
+ * its operand bytes. out = (sum_k fp16(x_k * s_a) * fp16(w_k * s_w)) / (s_a * s_w) + bias (+ resid): products exact, f32 accumulate on
+ * v_mfma_f32_16x16x32_f16, descale an exact power-of-two multiply. `in` holds PLAIN fp16 channels-last rows (uv_vae_rms_silu(split_out=3):
+ * s_a = 1; uv_vae_cast_f16: s_a found on the device, 1 / s_a passed as act_scale); here ld_in and Cin count CHANNELS (fp16 elements):
+ * Cin % 64 == 0, ld_in % 8 == 0. w16 = [Cout][kt*kh*kw*Cin] fp16 of w * w_scale, tap-major and channel-minor (uv_cast_weights_f16; w_scale
+ * a power of two by uv_split_weights_f16x3's rule). Everything else as uv_conv3d_f16x3. Launch plan: that of an f16x3 call of HALF the
+ * channels, uv_conv3d_plan(4, .., Cin / 2, ..); the kernel it names runs in its plain-row form. */
+int uv_conv3d_f16(const float* in, long ld_in, int Tin, int Hin, int Win, const void* w16, const float* bias, float* out, long ldo,
+                  int Tout, int Hout, int Wout, int Cin, int Cout, int kt, int kh, int kw, int st, int sh, int sw, int t_off, int ph,
+                  int pw, int up, int interleave, const float* resid, long ldr, float w_scale, const float* act_scale, void* stream);
+/* w [n] f32 (n % 64 == 0) -> out [n] fp16 = fp16(w * scale), scale = 2^s: the hi pieces of uv_split_weights_f16x3 as one plain matrix */
+int uv_cast_weights_f16(const float* w, void* out, long n, float scale, void* stream);
+/* uv_vae_split_f16 for uv_conv3d_f16: the same scale search and scale[0] <- 1 / s contract, stream-ordered, no host round trip; `out` rows
+ * (ld_out in f32-sized slots, >= C / 2) receive PLAIN fp16: fp16(x * s) of channel c at fp16 slot c = the hi pieces of uv_vae_split_f16.
+ * C % 64 == 0. `out` must not alias `x`. */
+int uv_vae_cast_f16(const float* x, long ld, float* out, long ld_out, long P, int C, float* scale, void* stream);
 /* x [P, C] f32 rows (any feature map; C % 32 == 0) -> `out`: the same bytes per pixel holding [C/32][32 hi | 32 lo] IEEE fp16 pieces of
  * x * s, s a per-tensor power of two found on the device: 1 while max|x| < 2^15 (then this equals uv_vae_rms_silu's split_out=2 format of
  * the same values), else the scale that puts max|x| into [2^14, 2^15). scale: two device floats; scale[0] <- 1 / s for uv_conv3d_f16x3's
@@ -452,7 +468,9 @@ int uv_vae_split_f16(const float* x, long ld, float* out, long ld_out, long P, i
 /* w [n] f32 (rows of K, K % 32 == 0) -> [n/32][32 hi | 32 lo] IEEE fp16 with hi = fp16(w * scale), lo = fp16(w * scale - hi); scale = 2^s */
 int uv_split_weights_f16x3(const float* w, void* out, long n, float scale, void* stream);
 /* y = x / max(||x||,1e-12) * sqrt(C) * gamma [-> SiLU] per pixel (RMS_norm + SiLU, vae2_2.py:45-59, 201-206).
- * split_out: 0 = f32 rows; 1 = [C/32][32 hi | 32 lo] bf16 pieces (uv_conv3d_bf16x3 in_split); 2 = the same layout in IEEE fp16 (uv_conv3d_f16x3). */
+ * split_out: 0 = f32 rows; 1 = [C/32][32 hi | 32 lo] bf16 pieces (uv_conv3d_bf16x3 in_split); 2 = the same layout in IEEE fp16 (uv_conv3d_f16x3);
+ * 3 = plain fp16 (uv_conv3d_f16; C % 64 == 0): the row's C values in its first C / 2 f32-sized slots, bit for bit the hi pieces of 2; the slots
+ * behind them are not written. ld_out counts f32-sized slots in every format. */
 int uv_vae_rms_silu(const float* in, long ld_in, const float* gamma, float* out, long ld_out, long P, int C, int do_silu,
                     int split_out, void* stream);
 /* in-place row softmax of x*scale (AttentionBlock's SDPA, vae2_2.py:267-271) */

@@ -1,7 +1,9 @@
 """End-to-end generation time (developer tool): WanTI2V.t2v / i2v with the production model sizes (30-block TI2V-5B DiT, full-width VAE,
 random-init weights, synthetic prompt embeddings): 50 UniPC steps with CFG + VAE decode, per stage, for the exact-f32 VAE and the
 f32-grade bf16x6 / f16x3 modes - at the bench size (49 frames of 704 x 1280) and at UniVid's own default workload (121 frames of
-704 x 1280, inference.py:48-50).   env: STEPS (50), FRAMES ("49,121"), PRECS ("fp32,bf16x6,f16x3")
+704 x 1280, inference.py:48-50).   env: STEPS (50), FRAMES ("49,121"), PRECS ("fp32,bf16x6,f16x3"; also bf16x3 and the opt-in narrow f16)
+    --vae-ab ROUNDS   instead of the table, and without the DiT: seconds per VAE decode (z [48, 13, 45, 80]) and encode (49 x 720 x 1280) in
+                      precision f16x3 and f16, alternating in one process after a warm-up of each; every round is printed
     --ffn-precision bf16|mxfp8   the DiT's FFN projections in the opt-in MXFP8 mode (WanModel.set_ffn_precision)
     --attn-precision bf16|mxfp8_qk|mxfp8_qk_pv   the DiT's self-attention in an opt-in MXFP8 mode (WanModel.set_attn_precision)
     --proj-precision bf16|mxfp8   the DiT's attention projections in the opt-in MXFP8 mode (WanModel.set_proj_precision)
@@ -17,6 +19,41 @@ from univid_amd.wan.vae2_2 import Wan2_2_VAE
 _lib.init()
 dev = "cuda"
 steps = int(os.environ.get("STEPS", 50))
+
+
+def clock(fn):
+    torch.cuda.synchronize(); t0 = time.perf_counter(); r = fn(); torch.cuda.synchronize()
+    return r, time.perf_counter() - t0
+
+
+if "--vae-ab" in sys.argv:
+    # --vae-ab ROUNDS: the VAE alone. One object per mode (each keeps its arena), one untimed decode and encode of each, then ROUNDS rounds of
+    # decode f16x3, decode f16, encode f16x3, encode f16; every round printed, then medians, the spread of each and the distance between the
+    # two modes' results
+    import statistics
+    rounds = int(sys.argv[sys.argv.index("--vae-ab") + 1])
+    g = torch.Generator(device=dev).manual_seed(7)
+    z = torch.randn(48, 13, 45, 80, device=dev, generator=g)
+    vid = torch.tanh(torch.randn(3, 49, 720, 1280, device=dev, generator=g))
+    vaes = {p: Wan2_2_VAE(device=dev, seed=0, precision=p) for p in ("f16x3", "f16")}
+    res, ts = {}, {(w, p): [] for w in ("decode", "encode") for p in vaes}
+    with torch.no_grad():
+        for p, v in vaes.items():
+            res["decode", p], res["encode", p] = v.decode([z])[0], v.encode([vid])[0]
+        for rnd in range(rounds):
+            for what in ("decode", "encode"):
+                for p, v in vaes.items():
+                    _, t = clock((lambda: v.decode([z])) if what == "decode" else (lambda: v.encode([vid])))
+                    ts[what, p].append(t)
+            print(f"round {rnd}: " + ", ".join(f"{w} {p} {ts[w, p][-1]:.4f} s" for w, p in ts), flush=True)
+    for what in ("decode", "encode"):
+        med = {p: statistics.median(ts[what, p]) for p in vaes}
+        spread = {p: max(ts[what, p]) - min(ts[what, p]) for p in vaes}
+        a, b = res[what, "f16x3"].double(), res[what, "f16"].double()
+        print(f"{what}: f16x3 median {med['f16x3']:.4f} s (spread {spread['f16x3']:.4f}), f16 median {med['f16']:.4f} s (spread {spread['f16']:.4f}); "
+              f"gain {med['f16x3'] - med['f16']:.4f} s, f16 / f16x3 = {med['f16'] / med['f16x3']:.4f}; rel rms f16 vs f16x3 "
+              f"{float((a - b).pow(2).mean().sqrt() / a.pow(2).mean().sqrt()):.3e}, finite {bool(torch.isfinite(res[what, 'f16']).all())}", flush=True)
+    sys.exit(0)
 with torch.device(dev):
     m = WanModel.from_config(TI2VConfig.dit)
 m = m.eval().requires_grad_(False)
@@ -32,11 +69,6 @@ m.prepare()
 g = torch.Generator(device=dev).manual_seed(1)
 pe = [torch.randn(40, 4096, device=dev, generator=g) * 0.1]
 ne = [torch.randn(9, 4096, device=dev, generator=g) * 0.1]
-
-
-def clock(fn):
-    torch.cuda.synchronize(); t0 = time.perf_counter(); r = fn(); torch.cuda.synchronize()
-    return r, time.perf_counter() - t0
 
 
 frames = [int(f) for f in os.environ.get("FRAMES", "49,121").split(",")]

@@ -1,6 +1,6 @@
 """Per-layer table of a full-size VAE decode / encode (developer tool): every convolution launch of the engine timed with HIP events (one
 synchronisation per launch: the sum is a little above the untimed decode), grouped by geometry, with the algorithmic and - f16x3 / bf16x6 -
-the EXECUTED MFMA rate (3 / 6 passes).   python3 tools/vae_layer_table.py [decode|encode] [precision] [UV_OPT_CONV_HALO value: -1 auto, 0 gather kernels only, 1]"""
+the EXECUTED MFMA rate (3 / 6 passes; precision f16: 1 pass where the input is plain fp16, split 3).   python3 tools/vae_layer_table.py [decode|encode] [precision] [UV_OPT_CONV_HALO value: -1 auto, 0 gather kernels only, 1]"""
 import os, sys, collections, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from univid_amd import _lib
@@ -40,5 +40,5 @@ print(f"{what} {prec} 49x720x1280: {e0.elapsed_time(e1):.1f} ms with per-launch 
 print("| Cin | Cout | kt x kh x kw | Tout x Hout x Wout | up | split | launches | ms | % of conv time | TFLOP/s algorithmic | executed (passes) |")
 print("|---|---|---|---|---|---|---|---|---|---|---|")
 for (ci, co, kt, kh, kw_, T, H, W, up, sp, sh), (n, ms, fl) in sorted(rows.items(), key=lambda kv: -kv[1][1]):
-    passes = 1 if prec == "fp32" else 3 if (prec == "bf16x3" or (prec == "f16x3" and sp == 2)) else 6
+    passes = 1 if prec == "fp32" or sp == 3 else 3 if (prec == "bf16x3" or (prec in ("f16x3", "f16") and sp == 2)) else 6
     print(f"| {ci} | {co} | {kt}x{kh}x{kw_}{' /2' if sh == 2 else ''} | {T}x{H}x{W} | {up} | {sp} | {n} | {ms:.1f} | {100 * ms / tot:.1f} | {fl / ms / 1e9:.0f} | {passes * fl / ms / 1e9:.0f} ({passes}) |")

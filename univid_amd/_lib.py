@@ -88,6 +88,10 @@ SIGNATURES = {
                          _P, _L, _I, _P],
     "uv_conv3d_f16x3": [_P, _L, _I, _I, _I, _P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I,
                         _P, _L, _F, _P, _P],
+    "uv_conv3d_f16": [_P, _L, _I, _I, _I, _P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I,
+                      _P, _L, _F, _P, _P],
+    "uv_cast_weights_f16": [_P, _P, _L, _F, _P],
+    "uv_vae_cast_f16": [_P, _L, _P, _L, _L, _I, _P, _P],
     "uv_conv3d_plan": [_I] * 18 + [_c.c_char_p, _I, _c.POINTER(_I), _c.POINTER(_I)],
     "uv_vae_split_f16": [_P, _L, _P, _L, _L, _I, _P, _P],
     "uv_split_weights_f16x3": [_P, _P, _L, _F, _P],
@@ -628,7 +632,7 @@ def attn_mxpv_plan(Lq, Lk, D=128, batch=1, H=1):
 def conv_plan(prec, Tout, Hout, Wout, Hin, Win, Cin, Cout, kt, kh, kw, st=1, sh=1, sw=1, ph=0, pw=0, up=0, interleave=0):
     """Launch plan of a uv_conv3d_* call of this geometry on the current device - 256 CUs without one - under the current OPT_CONV_HALO:
     dict(kernel=name, tiles_m=row tiles or pixel patches, tiles_n=output-channel tiles). prec: 0 f32, 1 / 2 bf16x3 without / with
-    in_split, 3 bf16x6, 4 f16x3."""
+    in_split, 3 bf16x6, 4 f16x3 - and the single-pass 'f16' entry asked with HALF its Cin (it runs the plain-row form of that kernel)."""
     buf = ctypes.create_string_buffer(32)
     tm, tn = _I(0), _I(0)
     lib = load()
@@ -877,38 +881,55 @@ def split_weights_f16x3(w, out, scale):
     return out
 
 
+def cast_weights_f16(w, out, scale):
+    """w f32 [rows, K] -> out fp16, w.numel() elements: fp16(w * scale) (scale a power of two), the weight matrix of uv_conv3d_f16."""
+    _check("cast_weights_f16", (w, "w", F32, w.numel()), (out, "out", F16, w.numel()))
+    call("uv_cast_weights_f16", ptr(w), ptr(out), w.numel(), float(scale), stream_ptr())
+    return out
+
+
 # conv3d's entry points: name, and the weight operand's (element dtype, elements per f32 weight)
 _CONV = {"f32": ("uv_conv3d_f32", F32, 1), "bf16x6": ("uv_conv3d_bf16x6", BF16, 3), "bf16x3": ("uv_conv3d_bf16x3", BF16, 2),
-         "f16x3": ("uv_conv3d_f16x3", F16, 2)}
+         "f16x3": ("uv_conv3d_f16x3", F16, 2), "f16": ("uv_conv3d_f16", F16, 1)}
 
 
 def conv3d(precision, src, weights, bias, out, Tin, Hin, Win, Tout, Hout, Wout, Cin, Cout, kt, kh, kw, st=1, sh=1, sw=1, t_off=0, ph=0, pw=0,
            up=0, interleave=0, resid=None, in_split=0, act_scale=None, flops=0):
     """One causal 3D / 2D convolution (include/univid_hip.h: uv_conv3d_*). The VAE's arithmetic `precision` ('fp32' | 'bf16x6' | 'f16x3' |
-    'bf16x3') and `in_split`, the format of src (0 f32 rows, 1 bf16 pieces, 2 fp16 pieces), select the entry: bf16x3 throughout its
-    mode; in f16x3 mode, f16x3 where src holds fp16 pieces and bf16x6 elsewhere. weights(kind) -> (the weight operand of entry `kind`:
-    the 'f32' [Cout, kt kh kw Cin] matrix or its 'bf16x6' | 'bf16x3' | 'f16x3' split, the scale of the f16x3 split).
-    src [Tin, Hin, Win, Cin]; out / resid: the output pixels' rows with Cout channels (interleave: Cout / 2 and twice the frames;
+    'bf16x3' | 'f16') and `in_split`, the format of src (0 f32 rows, 1 bf16 pieces, 2 fp16 pieces, 3 plain fp16), select the entry: bf16x3
+    throughout its mode; in f16x3 and f16 mode, f16x3 where src holds fp16 pieces and bf16x6 where it holds f32 rows; in f16 mode, the
+    single-pass f16 entry where src holds plain fp16. weights(kind) -> (the weight operand of entry `kind`: the 'f32' [Cout, kt kh kw Cin]
+    matrix, its 'bf16x6' | 'bf16x3' | 'f16x3' split or its 'f16' cast, the power-of-two scale of the two fp16 forms).
+    src [Tin, Hin, Win, Cin] - plain fp16 (in_split 3): the f32-typed [Tin, Hin, Win, Cin / 2] tensor whose rows hold the Cin fp16 values;
+    out / resid: the output pixels' rows with Cout channels (interleave: Cout / 2 and twice the frames;
     up >= 2: the [Tout, 2 Hout, 2 Wout] image of which this call writes one phase)."""
-    kind = "bf16x3" if precision == "bf16x3" else "f16x3" if precision == "f16x3" and in_split == 2 else \
-        "bf16x6" if precision in ("bf16x6", "f16x3") else "f32"
+    if in_split == 3 and precision != "f16":
+        raise UnividHipError(f"conv3d: plain fp16 rows (in_split 3) belong to precision 'f16', not {precision!r}")
+    kind = "bf16x3" if precision == "bf16x3" else "f16" if in_split == 3 else "f16x3" if precision in ("f16x3", "f16") and in_split == 2 else \
+        "bf16x6" if precision in ("bf16x6", "f16x3", "f16") else "f32"
+    if kind == "f16" and Cin % 64:
+        raise UnividHipError(f"conv3d: the single-pass f16 entry needs Cin % 64 == 0, got {Cin}")
+    half = 2 if kind == "f16" else 1         # fp16 channels per f32-sized slot of src
     entry, wdtype, planes = _CONV[kind]
     w, w_scale = weights(kind)
     rows = Tout * Hout * Wout * (2 if interleave else 4 if up >= 2 else 1)
     cols = Cout // 2 if interleave else Cout
-    _check("conv3d", (src, "src", F32, Cin, Tin * Hin * Win), (w, "weights", wdtype, planes * Cout * kt * kh * kw * Cin),
+    _check("conv3d", (src, "src", F32, Cin // half, Tin * Hin * Win), (w, "weights", wdtype, planes * Cout * kt * kh * kw * Cin),
            (bias, "bias", F32, Cout), (out, "out", F32, cols, rows), (resid, "resid", F32, cols, rows, True),
            (act_scale, "act_scale", F32, 1, None, True))
-    tail = (int(in_split == 1),) if kind == "bf16x3" else (w_scale, ptr(act_scale)) if kind == "f16x3" else ()
-    call(entry, ptr(src), src.stride(-2), Tin, Hin, Win, ptr(w), ptr(bias), ptr(out), out.stride(-2), Tout, Hout, Wout, Cin, Cout, kt, kh, kw,
+    tail = (int(in_split == 1),) if kind == "bf16x3" else (w_scale, ptr(act_scale)) if kind in ("f16x3", "f16") else ()
+    call(entry, ptr(src), src.stride(-2) * half, Tin, Hin, Win, ptr(w), ptr(bias), ptr(out), out.stride(-2), Tout, Hout, Wout, Cin, Cout, kt, kh, kw,
          st, sh, sw, t_off, ph, pw, up, interleave, ptr(resid), 0 if resid is None else resid.stride(-2), *tail, stream_ptr(), flops=flops)
     return out
 
 
 def vae_rms_silu(x, gamma, out, silu=True, split=0):
-    """RMS_norm (+ SiLU) per pixel: x f32 [..., C] -> out, the same bytes per pixel as f32 rows (split 0) or bf16 / fp16 pieces (1 / 2)."""
+    """RMS_norm (+ SiLU) per pixel: x f32 [..., C] -> out, the same bytes per pixel as f32 rows (split 0) or bf16 / fp16 pieces (1 / 2); split 3:
+    plain fp16, the C values of a pixel in the first C / 2 f32-sized slots of its row (C % 64 == 0), so out may be [..., C / 2]."""
     P, C = x.numel() // x.shape[-1], x.shape[-1]
-    _check("vae_rms_silu", (x, "x", F32, C, P), (gamma, "gamma", F32, C), (out, "out", F32, C, P))
+    if split == 3 and C % 64:
+        raise UnividHipError(f"vae_rms_silu: plain fp16 output (split 3) needs C % 64 == 0, got {C}")
+    _check("vae_rms_silu", (x, "x", F32, C, P), (gamma, "gamma", F32, C), (out, "out", F32, C // 2 if split == 3 else C, P))
     call("uv_vae_rms_silu", ptr(x), x.stride(-2), ptr(gamma), ptr(out), out.stride(-2), P, C, int(silu), int(split), stream_ptr())
     return out
 
@@ -918,6 +939,17 @@ def vae_split_f16(x, out, scale):
     P, C = x.numel() // x.shape[-1], x.shape[-1]
     _check("vae_split_f16", (x, "x", F32, C, P), (out, "out", F32, C, P), (scale, "scale", F32, 2))
     call("uv_vae_split_f16", ptr(x), x.stride(-2), ptr(out), out.stride(-2), P, C, ptr(scale), stream_ptr())
+    return out
+
+
+def vae_cast_f16(x, out, scale):
+    """Plain fp16 of a raw feature map x f32 [..., C] (C % 64 == 0) under vae_split_f16's device-found power-of-two scale: out f32-typed
+    [..., >= C / 2], the C fp16 values of a pixel at the start of its row; scale f32 [2] <- (1 / s, work space)."""
+    P, C = x.numel() // x.shape[-1], x.shape[-1]
+    if C % 64:
+        raise UnividHipError(f"vae_cast_f16: C must be a multiple of 64, got {C}")
+    _check("vae_cast_f16", (x, "x", F32, C, P), (out, "out", F32, C // 2, P), (scale, "scale", F32, 2))
+    call("uv_vae_cast_f16", ptr(x), x.stride(-2), ptr(out), out.stride(-2), P, C, ptr(scale), stream_ptr())
     return out
 
 

@@ -43,6 +43,11 @@ typedef __attribute__((address_space(3))) void lds_void_c;
 //         and must stay below 65 504 in magnitude - uv_vae_rms_silu(split_out = 2) writes them, and an RMS-normalised row is bounded by
 //         sqrt(C) max|gamma| (the host checks that bound per convolution and keeps PREC 3 where it does not hold). Activation lo pieces
 //         of |x| < 2^-3 are subnormal fp16: an ABSOLUTE error <= 2^-25 there, i.e. below f32's own rounding of the row's O(1) elements.
+//         PLAIN (PREC 4 only; uv_conv3d_f16, "f16"): ONE fp16 pass, NOT f32-grade. The same 128-byte rows hold 64 plain fp16 channels
+//         (activations fp16(x * s_a), weights fp16(w * s_w)) instead of 32 split ones, so the two fragment reads of a row (byte offsets o
+//         and o ^ 64) are channels 0..31 and 32..63 and feed TWO MFMAs, w(fq) a(fq) and w(4 + fq) a(4 + fq), where f16x3 issues three:
+//         a third of the MFMA work and half the bytes per output. Staging, swizzle, LDS image, barriers and epilogue are PREC 4's; Cin,
+//         ld_in and K count f32-sized units = half the channels. Products exact, f32 accumulate; the operands carry 11 bits.
 // PREC 3: "bf16x6", f32-GRADE: every f32 operand is three bf16 planes (x = x0 + x1 + x2 exactly) and the product keeps the six
 //         terms with i + j <= 2 (error < 2^-26 |x w|, under f32's own rounding), f32 accumulate. Activations f32 in HBM/LDS, split in
 //         registers; weights pre-split on the host into [Cout][K/32][32 p0 | 32 p1 | 32 p2] bf16 and staged as three plane sub-tiles.
@@ -50,8 +55,9 @@ typedef __attribute__((address_space(3))) void lds_void_c;
 // three bf16 planes (64-byte rows, one [BN][64 B] sub-tile per plane) instead of f32 rows
 constexpr int conv_stage_bytes(int BM, int BN, int PREC) { return BM * 128 + BN * (PREC == 3 ? 192 : 128); }
 
-template <int BM, int BN, int WM, int WN, int PREC>
+template <int BM, int BN, int WM, int WN, int PREC, bool PLAIN = false>
 __global__ __launch_bounds__(WM* WN * 64) void conv3d_f32_kernel(ConvArgs p) {
+    static_assert(!PLAIN || PREC == 4, "plain fp16 rows are a form of PREC 4");
     constexpr int NW = WM * WN;
     constexpr int TM = BM / WM / 16, TN = BN / WN / 16;
     constexpr int A_BYTES = BM * 128, STAGE = conv_stage_bytes(BM, BN, PREC), W_BYTES = STAGE - A_BYTES;
@@ -277,6 +283,21 @@ __global__ __launch_bounds__(WM* WN * 64) void conv3d_f32_kernel(ConvArgs p) {
                     acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wp[i][0], ap[j][1], acc[i][j], 0, 0, 0);
                     acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wp[i][0], ap[j][0], acc[i][j], 0, 0, 0);
                 }
+        } else if (PLAIN) {
+            // 64 plain fp16 channels per row: two K = 32 MFMA steps per k-tile, channels 0..31 (chunks fq) then 32..63 (chunks 4 + fq); the
+            // fragments of a half are dead before the next half's are read
+#pragma unroll
+            for (int hf = 0; hf < 2; ++hf) {
+                bf16x8 af[TM], wf[TN];
+#pragma unroll
+                for (int j = 0; j < TM; ++j) af[j] = *(const bf16x8*)(base + a_off[j] + (((4 * hf + fq) ^ a_key[j]) << 4));
+#pragma unroll
+                for (int i = 0; i < TN; ++i) wf[i] = *(const bf16x8*)(base + w_off[i] + (((4 * hf + fq) ^ w_key[i]) << 4));
+#pragma unroll
+                for (int i = 0; i < TN; ++i)
+#pragma unroll
+                    for (int j = 0; j < TM; ++j) acc[i][j] = mfma_16x16x32<true>(wf[i], af[j], acc[i][j]);
+            }
         } else {
             // one K = 32 MFMA step per k-tile: lane (row, fq) owns k = 8*fq .. 8*fq+7 of both operands
             bf16x8 ah[TM], al[TM], wh[TN], wl[TN];
@@ -361,13 +382,22 @@ __global__ __launch_bounds__(WM* WN * 64) void conv3d_f32_kernel(ConvArgs p) {
 
 const float* uv_zero_page();
 
-template <int BM, int BN, int WM, int WN, int PREC>
+template <int BM, int BN, int WM, int WN, int PREC, bool PLAIN = false>
 static void launch_conv(const ConvArgs& a, const ConvPlan& plan, hipStream_t stream) {
-    conv_launch<conv3d_f32_kernel<BM, BN, WM, WN, PREC>, WM * WN * 64, 2 * conv_stage_bytes(BM, BN, PREC)>(a, plan, stream);
+    conv_launch<conv3d_f32_kernel<BM, BN, WM, WN, PREC, PLAIN>, WM * WN * 64, 2 * conv_stage_bytes(BM, BN, PREC)>(a, plan, stream);
 }
 
-// the gather kernel's 16 instantiations: plan.kernel = tile + PREC
+// the gather kernel's 16 instantiations: plan.kernel = tile + PREC; the four "+4" tiles once more for plain fp16 rows (ConvArgs::plain)
 static void launch_conv_gather(const ConvArgs& a, const ConvPlan& plan, hipStream_t s) {
+    if (a.plain) {
+        switch (plan.kernel) {
+            case G256x16 + 4: return launch_conv<256, 16, 4, 1, 4, true>(a, plan, s);
+            case G128x128 + 4: return launch_conv<128, 128, 2, 2, 4, true>(a, plan, s);
+            case G256x128 + 4: return launch_conv<256, 128, 4, 2, 4, true>(a, plan, s);
+            case G256x256 + 4: return launch_conv<256, 256, 4, 4, 4, true>(a, plan, s);
+        }
+        return;
+    }
     switch (plan.kernel) {
         case G256x16 + 0: return launch_conv<256, 16, 4, 1, 0>(a, plan, s);
         case G256x16 + 3: return launch_conv<256, 16, 4, 1, 3>(a, plan, s);
@@ -391,7 +421,7 @@ static void launch_conv_gather(const ConvArgs& a, const ConvPlan& plan, hipStrea
 static int conv_common(const float* in, long ld_in, int Tin, int Hin, int Win, const void* w, const float* bias, float* out,
                        long ldo, int Tout, int Hout, int Wout, int Cin, int Cout, int kt, int kh, int kw, int st, int sh,
                        int sw, int t_off, int ph, int pw, int up, int interleave, const float* resid, long ldr, int prec,
-                       void* stream, float out_scale = 1.0f, const float* act_scale = nullptr) {
+                       void* stream, float out_scale = 1.0f, const float* act_scale = nullptr, int plain = 0) {
     UV_CHECK_ARG(in && w && out, "uv_conv3d: null pointer");
     ConvArgs a;
     if (conv_geometry(a, Tout, Hout, Wout, Hin, Win, Cin, Cout, kt, kh, kw, st, sh, sw, ph, pw, up, interleave) != 0) return -1;
@@ -406,6 +436,7 @@ static int conv_common(const float* in, long ld_in, int Tin, int Hin, int Win, c
     a.Tin = Tin; a.t_off = t_off;
     a.out_scale = out_scale;
     a.act_scale = act_scale;
+    a.plain = plain;
     const ConvPlan plan = plan_conv(a, prec, uv_option(UV_OPT_CONV_HALO), uv_num_cus());
     const bool halo16 = plan.kernel >= HALO_F16_N16, halo = !halo16 && plan.kernel >= HALO_BF16X6;
     (halo16 ? launch_conv_halo16 : halo ? launch_conv_halo : launch_conv_gather)(a, plan, (hipStream_t)stream);
@@ -415,7 +446,8 @@ static int conv_common(const float* in, long ld_in, int Tin, int Hin, int Win, c
 
 // The plan a uv_conv3d_* call of this geometry launches on the current device (256 CUs without one) under the current UV_OPT_CONV_HALO:
 // kernel name (kConvKernelName) and the grid, row tiles x output-channel tiles. prec = the PREC above: 0 uv_conv3d_f32, 1 / 2
-// uv_conv3d_bf16x3 without / with in_split, 3 uv_conv3d_bf16x6, 4 uv_conv3d_f16x3. Host only.
+// uv_conv3d_bf16x3 without / with in_split, 3 uv_conv3d_bf16x6, 4 uv_conv3d_f16x3 - and uv_conv3d_f16 with HALF its channel count (it runs
+// the plain-row instantiation of the kernel that plan names). Host only.
 extern "C" int uv_conv3d_plan(int prec, int Tout, int Hout, int Wout, int Hin, int Win, int Cin, int Cout, int kt, int kh, int kw, int st,
                               int sh, int sw, int ph, int pw, int up, int interleave, char* kernel, int len, int* tiles_m, int* tiles_n) {
     UV_CHECK_ARG(kernel && len > 0 && tiles_m && tiles_n, "uv_conv3d_plan: null pointer");
@@ -483,6 +515,39 @@ extern "C" int uv_conv3d_f16x3(const float* in, long ld_in, int Tin, int Hin, in
     UV_CHECK_ARG(w_scale > 0.f && frexpf(w_scale, &ex) == 0.5f, "uv_conv3d_f16x3: w_scale=%g must be a power of two", (double)w_scale);
     return conv_common(in, ld_in, Tin, Hin, Win, w_split, bias, out, ldo, Tout, Hout, Wout, Cin, Cout, kt, kh, kw, st, sh, sw, t_off,
                        ph, pw, up, interleave, resid, ldr, 4, stream, 1.0f / w_scale, act_scale);
+}
+
+// Same convolution in ONE fp16 MFMA pass (PLAIN above): an opt-in NARROW arithmetic, 11-bit operands.
+//   out = (sum_k fp16(x_k * s_a) * fp16(w_k * s_w)) / (s_a * s_w) + bias (+ residual), products exact, f32 accumulate.
+// `in` holds plain fp16 channels-last rows (uv_vae_rms_silu split_out = 3: s_a = 1; uv_vae_cast_f16: s_a found on the device, 1 / s_a in
+// *act_scale); Cin and ld_in count CHANNELS here (Cin % 64 == 0, ld_in % 8 == 0: whole 128-byte rows and 16-byte chunks); w16 =
+// [Cout][taps * Cin] fp16 of w * w_scale (uv_cast_weights_f16). Runs as conv_common on Cin / 2 and ld_in / 2 f32-sized units: planned
+// like an f16x3 call of half the channels (uv_conv3d_plan(4, .., Cin / 2, ..)).
+extern "C" int uv_conv3d_f16(const float* in, long ld_in, int Tin, int Hin, int Win, const void* w16, const float* bias, float* out,
+                             long ldo, int Tout, int Hout, int Wout, int Cin, int Cout, int kt, int kh, int kw, int st, int sh, int sw,
+                             int t_off, int ph, int pw, int up, int interleave, const float* resid, long ldr, float w_scale,
+                             const float* act_scale, void* stream) {
+    int ex = 0;
+    UV_CHECK_ARG(w_scale > 0.f && frexpf(w_scale, &ex) == 0.5f, "uv_conv3d_f16: w_scale=%g must be a power of two", (double)w_scale);
+    UV_CHECK_ARG(Cin > 0 && Cin % 64 == 0, "uv_conv3d_f16: Cin=%d must be a multiple of 64 (whole 128-byte rows of plain fp16)", Cin);
+    UV_CHECK_ARG(ld_in % 8 == 0, "uv_conv3d_f16: ld_in=%ld must be a multiple of 8 (16-byte chunks of fp16)", ld_in);
+    return conv_common(in, ld_in / 2, Tin, Hin, Win, w16, bias, out, ldo, Tout, Hout, Wout, Cin / 2, Cout, kt, kh, kw, st, sh, sw, t_off,
+                       ph, pw, up, interleave, resid, ldr, 4, stream, 1.0f / w_scale, act_scale, 1);
+}
+
+// w [n] f32 -> fp16(w * scale), element for element: the hi pieces of uv_split_weights_f16x3 as one plain matrix
+__global__ void cast_weights_f16_kernel(const float* w, _Float16* out, long n, float scale) {
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) out[i] = (_Float16)(w[i] * scale);
+}
+
+extern "C" int uv_cast_weights_f16(const float* w, void* out, long n, float scale, void* stream) {
+    int ex = 0;
+    UV_CHECK_ARG(w && out && n > 0 && n % 64 == 0, "uv_cast_weights_f16: n must be a positive multiple of 64");
+    UV_CHECK_ARG(scale > 0.f && frexpf(scale, &ex) == 0.5f, "uv_cast_weights_f16: scale=%g must be a power of two", (double)scale);
+    hipLaunchKernelGGL(cast_weights_f16_kernel, dim3((unsigned)min((n + 255) / 256, (long)4096)), dim3(256), 0, (hipStream_t)stream, w,
+                       (_Float16*)out, n, scale);
+    UV_CHECK_LAUNCH("uv_cast_weights_f16");
+    return 0;
 }
 
 // w [rows][K] f32 (K % 32 == 0) -> [rows][K/32][32 hi | 32 lo] IEEE fp16 with hi = fp16(w * scale), lo = fp16(w * scale - hi); scale is a

@@ -34,7 +34,9 @@ constexpr int halo16_pixels(int TW) { return (256 / TW + 2) * (TW + 2); }
 constexpr int halo16_image_bytes(int TW) { return (halo16_pixels(TW) + 7) / 8 * 1024; }
 constexpr int halo16_lds_bytes(int BN, int TAPS, int TW) { return 2 * halo16_image_bytes(TW) + 2 * TAPS * BN * 128; }
 
-template <int BN = 128, int TAPS = 2, int TW = 32>
+// PLAIN = the single-pass fp16 arithmetic (uv_conv3d_f16; conv3d_f32.hip, PREC 4 PLAIN): the same 128-byte halo and weight rows hold 64 plain
+// fp16 channels, the two reads of a row (o and o ^ 64) are its channel halves, and a tap issues two MFMAs per fragment pair, not three.
+template <int BN = 128, int TAPS = 2, int TW = 32, bool PLAIN = false>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void conv3d_halo_f16_kernel(ConvArgs p) {
     constexpr int TH = 256 / TW, HW_ = TW + 2, NHP = halo16_pixels(TW);      // 340 / 324 halo pixels
     constexpr int FPR = TW / 16, RPW = TH / 4;                               // 16-pixel fragments per patch row; patch rows per wave row group
@@ -119,6 +121,24 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     auto compute = [&](int tap, const char* wb, const char* halo) __attribute__((always_inline)) {
         const int dh = tap / 3, dw = tap - dh * 3;
         const int toff = dh * HW_ + dw;
+        if constexpr (PLAIN) {           // channels 0..31 (byte offset o), then 32..63 (o ^ 64): two MFMAs per fragment pair
+#pragma unroll
+            for (int hf = 0; hf < 2; ++hf) {
+                bf16x8 af[TM], wf[TN];
+#pragma unroll
+                for (int j = 0; j < TM; ++j) {
+                    const int hp = hpb[j] + toff;
+                    af[j] = *(const bf16x8*)(halo + ((hp * 128 + ((fq ^ ((hp >> 1) & 7)) << 4)) ^ (hf * 64)));
+                }
+#pragma unroll
+                for (int i = 0; i < TN; ++i) wf[i] = *(const bf16x8*)(wb + (w_off[i] ^ (hf * 64)));
+#pragma unroll
+                for (int i = 0; i < TN; ++i)
+#pragma unroll
+                    for (int j = 0; j < TM; ++j) acc[i][j] = mfma_16x16x32<true>(wf[i], af[j], acc[i][j]);
+            }
+            return;
+        }
         bf16x8 ah[TM], al[TM], wh[TN], wl[TN];
 #pragma unroll
         for (int j = 0; j < TM; ++j) {
@@ -208,6 +228,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 // ds_read_b128 per tap and wave - the kernel is bound by the LDS reads of the activation fragments (each is used for one 16-channel
 // fragment only), ~1 us per workgroup and group, an order of magnitude under the gather form's L2 traffic.
 // ------------------------------------------------------------------------------------------------------------------------------------
+template <bool PLAIN = false>
 __global__ __launch_bounds__(512) void conv3d_halo_f16_n16_kernel(ConvArgs p) {
     constexpr int TW = 32, TH = 8, HW_ = TW + 2, NHP = halo16_pixels(TW);
     constexpr int NW = 8;
@@ -290,6 +311,11 @@ __global__ __launch_bounds__(512) void conv3d_halo_f16_n16_kernel(ConvArgs p) {
                 const int o = hp * 128 + ((fq ^ ((hp >> 1) & 7)) << 4);
                 const bf16x8 ah = *(const bf16x8*)(halo + o);
                 const bf16x8 al = *(const bf16x8*)(halo + (o ^ 64));
+                if constexpr (PLAIN) {
+                    acc[j] = mfma_16x16x32<true>(wh, ah, acc[j]);
+                    acc[j] = mfma_16x16x32<true>(wl, al, acc[j]);
+                    continue;
+                }
                 acc[j] = mfma_16x16x32<true>(wl, ah, acc[j]);
                 acc[j] = mfma_16x16x32<true>(wh, al, acc[j]);
                 acc[j] = mfma_16x16x32<true>(wh, ah, acc[j]);
@@ -323,11 +349,17 @@ __global__ __launch_bounds__(512) void conv3d_halo_f16_n16_kernel(ConvArgs p) {
     }
 }
 
-void launch_conv_halo16(const ConvArgs& a, const ConvPlan& plan, hipStream_t stream) {
+template <bool PLAIN>
+static void launch_halo16(const ConvArgs& a, const ConvPlan& plan, hipStream_t stream) {
     switch (plan.kernel) {      // 122, 126, 146 and 150 KiB of LDS: one workgroup per CU
-        case HALO_F16_N16: return conv_launch<conv3d_halo_f16_n16_kernel, 512, halo16_lds_bytes(16, 9, 32)>(a, plan, stream);
-        case HALO_F16_160: return conv_launch<conv3d_halo_f16_kernel<160, 1, 32>, 512, halo16_lds_bytes(160, 1, 32)>(a, plan, stream);
-        case HALO_F16_SQUARE: return conv_launch<conv3d_halo_f16_kernel<128, 2, 16>, 512, halo16_lds_bytes(128, 2, 16)>(a, plan, stream);
-        case HALO_F16_128: return conv_launch<conv3d_halo_f16_kernel<128, 2, 32>, 512, halo16_lds_bytes(128, 2, 32)>(a, plan, stream);
+        case HALO_F16_N16: return conv_launch<conv3d_halo_f16_n16_kernel<PLAIN>, 512, halo16_lds_bytes(16, 9, 32)>(a, plan, stream);
+        case HALO_F16_160: return conv_launch<conv3d_halo_f16_kernel<160, 1, 32, PLAIN>, 512, halo16_lds_bytes(160, 1, 32)>(a, plan, stream);
+        case HALO_F16_SQUARE: return conv_launch<conv3d_halo_f16_kernel<128, 2, 16, PLAIN>, 512, halo16_lds_bytes(128, 2, 16)>(a, plan, stream);
+        case HALO_F16_128: return conv_launch<conv3d_halo_f16_kernel<128, 2, 32, PLAIN>, 512, halo16_lds_bytes(128, 2, 32)>(a, plan, stream);
     }
+}
+
+void launch_conv_halo16(const ConvArgs& a, const ConvPlan& plan, hipStream_t stream) {
+    if (a.plain) launch_halo16<true>(a, plan, stream);
+    else launch_halo16<false>(a, plan, stream);
 }

@@ -19,10 +19,15 @@ struct ConvArgs {
                          // (t, 2y + a, 2x + b) of a [Tout, 2 Hout, 2 Wout] tensor (one phase of a 2x-upsampling convolution, see uv_conv3d_f32)
     const float* act_scale;   // f16x3: nullptr, or a device scalar the result is multiplied by as well (uv_vae_split_f16's 1 / s)
     float out_scale;     // f16x3 (PREC 4): the accumulators carry the power-of-two scale of the split weights; out = acc * out_scale + bias
+    int plain;           // PREC 4 only: the 128-byte operand rows hold 64 PLAIN fp16 channels instead of [32 hi | 32 lo] (uv_conv3d_f16: ONE fp16
+                         // pass); Cin, ld_in and the weight rows are still counted in f32-sized units = HALF the channels
 };
 
 // The 23 kernels. A gather tile + prec names conv3d_f32_kernel<BM, BN, .., prec> (G160: 128 x 160, 64 x 160 for bf16x6); which of the sums
 // exist is plan_conv's ladder below and launch_conv_gather's switch. The halo kernels carry their arithmetic in the name.
+// The single-pass fp16 arithmetic (uv_conv3d_f16, ConvArgs::plain) adds NO names: it is planned as prec 4 of HALF its channel count (its
+// 64-channel rows are the 128-byte rows of 32 split channels) and runs the PLAIN instantiation of whichever "+4" gather tile or HALO_F16_*
+// kernel that plan names - eight more instantiations behind the same 23 names, and uv_conv3d_plan(4, .., Cin / 2, ..) reports its plan.
 enum ConvKernel {
     G256x16 = 0, G160 = 8, G128x128 = 16, G256x128 = 24, G256x256 = 32,
     HALO_BF16X6 = 40, HALO_F32_160, HALO_F32_128,                      // conv3d_halo.hip

@@ -9,7 +9,8 @@
 
 // y = x / max(||x||_2, 1e-12) * sqrt(C) * gamma  [-> SiLU]      (F.normalize(x, dim=C) * scale * gamma)
 // split_out: write each value as bf16 hi + bf16 lo in the [C/32][32 hi | 32 lo] layout uv_conv3d_bf16x3(in_split=1) reads
-// (same bytes per pixel as f32).
+// (same bytes per pixel as f32); 2: the same layout in IEEE fp16; 3: plain fp16, the row's C values in its first C / 2 f32-sized slots
+// (uv_conv3d_f16; the slots behind them are not written).
 // One wave per RPW consecutive rows (pixels): the loads of all RPW rows are issued before the first reduction, so a wave keeps RPW rows
 // in flight - at C = 160 a row is 640 bytes, and one row per wave left the kernel latency-bound at 2.9 TB/s (32 waves x 640 B per CU).
 // MAXV = ceil(C / 256) exactly (chosen by the launcher): every load is issued unconditionally from a clamped column (lanes beyond the
@@ -60,7 +61,11 @@ __global__ __launch_bounds__(256) void vae_rms_silu_kernel(const float* in, long
                 y[e] = t;
             }
             if (c4 < nv) {
-                if (split_out == 2) {        // two IEEE fp16 pieces (uv_conv3d_f16x3): hi = fp16(y), lo = fp16(y - hi)
+                if (split_out == 3) {        // plain fp16 (uv_conv3d_f16): the hi pieces of split_out 2, channel c at fp16 slot c of the row
+                    auto pk = [](_Float16 a, _Float16 b) { return (uint32_t)__builtin_bit_cast(uint16_t, a) | ((uint32_t)__builtin_bit_cast(uint16_t, b) << 16); };
+                    *(u32x2*)((bf16_t*)(out + row * ld_out) + c4 * 4) =
+                        (u32x2){pk((_Float16)y[0], (_Float16)y[1]), pk((_Float16)y[2], (_Float16)y[3])};
+                } else if (split_out == 2) { // two IEEE fp16 pieces (uv_conv3d_f16x3): hi = fp16(y), lo = fp16(y - hi)
                     const int c = c4 * 4;
                     bf16_t* ob = (bf16_t*)(out + row * ld_out) + (c >> 5) * 64 + (c & 31);
                     _Float16 hi[4], lo[4];
@@ -91,8 +96,9 @@ __global__ __launch_bounds__(256) void vae_rms_silu_kernel(const float* in, long
 extern "C" int uv_vae_rms_silu(const float* in, long ld_in, const float* gamma, float* out, long ld_out, long P, int C,
                                int do_silu, int split_out, void* stream) {
     UV_CHECK_ARG(in && gamma && out && P > 0, "uv_vae_rms_silu: bad arguments");
-    UV_CHECK_ARG(split_out >= 0 && split_out <= 2, "uv_vae_rms_silu: split_out must be 0 (f32 rows), 1 (bf16 pieces) or 2 (fp16 pieces), got %d", split_out);
+    UV_CHECK_ARG(split_out >= 0 && split_out <= 3, "uv_vae_rms_silu: split_out must be 0 (f32 rows), 1 (bf16 pieces), 2 (fp16 pieces) or 3 (plain fp16), got %d", split_out);
     UV_CHECK_ARG(!split_out || C % 32 == 0, "uv_vae_rms_silu: split output needs C %% 32 == 0 (C=%d)", C);
+    UV_CHECK_ARG(split_out != 3 || C % 64 == 0, "uv_vae_rms_silu: plain fp16 output needs C %% 64 == 0 (C=%d)", C);
     UV_CHECK_ARG(C % 4 == 0 && C <= 2048 && ld_in % 4 == 0 && ld_out % 4 == 0, "uv_vae_rms_silu: C=%d unsupported", C);
     const dim3 block(256);
     const int maxv = (C + 255) / 256;                    // float4 chunks per lane
@@ -317,7 +323,8 @@ extern "C" int uv_vae_video_out(const float* y, long ld, float* vid, int F, int 
 // floats order like their bit patterns; fmaxf drops NaNs - a NaN input leaves the scale at that of the finite values and propagates through the
 // products). !SPECULATIVE = the second launch: writes 1 / s and, only if s != 1 (max |x| >= 2^15: no realistic activation), splits again under s;
 // otherwise every block returns after one load. (Round 4: the separate max pass in front of the split cost a second read of every raw tensor.)
-template <bool SPECULATIVE>
+// PLAIN: only the hi pieces, as plain fp16 rows (channel c at fp16 slot c: uv_vae_cast_f16, for uv_conv3d_f16), under the same scale rule.
+template <bool SPECULATIVE, bool PLAIN = false>
 __global__ __launch_bounds__(256) void split_f16_scaled_kernel(const float* x, long ld, float* out, long ld_out, long P, int C, float* scale) {
     float s = 1.f;
     if constexpr (!SPECULATIVE) {
@@ -346,6 +353,10 @@ __global__ __launch_bounds__(256) void split_f16_scaled_kernel(const float* x, l
             lo[e] = (_Float16)(y - (float)hi[e]);
         }
         auto pk = [](_Float16 a, _Float16 b) { return (uint32_t)__builtin_bit_cast(uint16_t, a) | ((uint32_t)__builtin_bit_cast(uint16_t, b) << 16); };
+        if constexpr (PLAIN) {
+            *(u32x2*)((bf16_t*)(out + row * ld_out) + c) = (u32x2){pk(hi[0], hi[1]), pk(hi[2], hi[3])};
+            continue;
+        }
         bf16_t* ob = (bf16_t*)(out + row * ld_out) + (c >> 5) * 64 + (c & 31);
         *(u32x2*)ob = (u32x2){pk(hi[0], hi[1]), pk(hi[2], hi[3])};
         *(u32x2*)(ob + 32) = (u32x2){pk(lo[0], lo[1]), pk(lo[2], lo[3])};
@@ -376,5 +387,24 @@ extern "C" int uv_vae_split_f16(const float* x, long ld, float* out, long ld_out
     hipLaunchKernelGGL(split_f16_scaled_kernel<true>, dim3(blocks), dim3(256), 0, st, x, ld, out, ld_out, P, C, scale);
     hipLaunchKernelGGL(split_f16_scaled_kernel<false>, dim3(blocks), dim3(256), 0, st, x, ld, out, ld_out, P, C, scale);
     UV_CHECK_LAUNCH("uv_vae_split_f16");
+    return 0;
+}
+
+// uv_vae_split_f16 for the single-pass fp16 convolution (uv_conv3d_f16): the same scale search and scale[0] <- 1 / s contract, the same three
+// stream-ordered operations, but `out` receives plain fp16 rows - fp16(x * s) of channel c at fp16 slot c, i.e. the hi pieces of
+// uv_vae_split_f16 in the first C / 2 f32-sized slots of a row (ld_out counts f32-sized slots, as in uv_vae_rms_silu).
+extern "C" int uv_vae_cast_f16(const float* x, long ld, float* out, long ld_out, long P, int C, float* scale, void* stream) {
+    UV_CHECK_ARG(x && out && scale && P > 0 && C > 0 && C % 64 == 0 && ld % 4 == 0 && ld_out % 4 == 0 && ld >= C && ld_out >= C / 2,
+                 "uv_vae_cast_f16: bad arguments (C=%d must be a multiple of 64)", C);
+    UV_CHECK_ARG((const void*)x != (const void*)out, "uv_vae_cast_f16: out must not alias x (the second launch may re-read x)");
+    hipStream_t st = (hipStream_t)stream;
+    if (hipMemsetAsync(scale, 0, 2 * sizeof(float), st) != hipSuccess) {
+        uv_set_error("uv_vae_cast_f16: memset failed");
+        return -2;
+    }
+    const unsigned blocks = (unsigned)min((P * (C >> 2) + 255) / 256, (long)8192);
+    hipLaunchKernelGGL((split_f16_scaled_kernel<true, true>), dim3(blocks), dim3(256), 0, st, x, ld, out, ld_out, P, C, scale);
+    hipLaunchKernelGGL((split_f16_scaled_kernel<false, true>), dim3(blocks), dim3(256), 0, st, x, ld, out, ld_out, P, C, scale);
+    UV_CHECK_LAUNCH("uv_vae_cast_f16");
     return 0;
 }

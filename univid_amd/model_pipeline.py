@@ -29,7 +29,7 @@ from typing import Callable, List, Optional, Tuple
 import torch
 
 from .lora import LoRAManager
-from .wan.textimage2video import TI2VConfig, WanTI2V
+from .wan.textimage2video import TI2VConfig, WanTI2V, set_vae_precision
 
 
 @dataclass
@@ -55,6 +55,7 @@ class CrossAttentionConfig:
     lora_merge: bool = True       # CrossAttentionFusionPipeline.load_lora: fold the adapter into the dense weights (False: attach it un-merged)
     ffn_precision: str = "bf16"   # "mxfp8": the DiT's ffn.0 / ffn.2 on MXFP8 operands (WanModel.set_ffn_precision), an opt-in fast mode
     proj_precision: str = "bf16"  # "mxfp8": the DiT's self-attention q / k / v / o and cross-attention q / o projections on MXFP8 operands (WanModel.set_proj_precision), an opt-in experimental mode
+    vae_precision: Optional[str] = None   # "f16": the VAE's opt-in narrow arithmetic (WanVAE_.prepare; one fp16 pass where f16x3 takes three); None keeps the VAE's own mode ("f16x3")
     attn_precision: str = "bf16"  # "mxfp8_qk" / "mxfp8_qk_pv": the DiT's self-attention q / k (and P.V) as MXFP8 (WanModel.set_attn_precision), opt-in experimental modes
     guidance_strength: float = 1.0
     bagel_cross_attn_layers: List[int] = None
@@ -388,6 +389,7 @@ class CrossAttentionFusionPipeline:
         proj_precision = getattr(config, "proj_precision", "bf16")
         if proj_precision != "bf16" and hasattr(self.dit_model, "set_proj_precision") and proj_precision != self.dit_model.proj_precision:
             self.dit_model.set_proj_precision(proj_precision)
+        set_vae_precision(getattr(wan_pipeline, "vae", None), getattr(config, "vae_precision", None))
         self.vae_model = wan_pipeline.vae
         self.text_encoder = wan_pipeline.text_encoder
         # native_text_weight=False: the reference's closures on the model's generic path (kept as the comparison the tests and bench use)
@@ -417,7 +419,8 @@ class CrossAttentionFusionPipeline:
             return WanTI2V(config=wan_config, checkpoint_dir=path, device_id=self.config.wan_gpu, rank=0, t5_fsdp=False, dit_fsdp=False,
                            use_sp=False, ffn_precision=getattr(self.config, "ffn_precision", "bf16"),
                            attn_precision=getattr(self.config, "attn_precision", "bf16"),
-                           proj_precision=getattr(self.config, "proj_precision", "bf16"))
+                           proj_precision=getattr(self.config, "proj_precision", "bf16"),
+                           vae_precision=getattr(self.config, "vae_precision", None))
         except Exception as e:
             raise RuntimeError(f"Wan2.2 initialization failed: {e}") from e
 

@@ -223,10 +223,19 @@ class _GraphedPair:
         return self.out[0], self.out[1]      # static outputs: consumed by the sampler update before the next replay
 
 
+def set_vae_precision(vae, precision):
+    """The VAE's arithmetic (WanVAE_.prepare: "fp32" | "bf16x6" | "f16x3" | "bf16x3" | the opt-in narrow "f16") on a Wan2_2_VAE that is
+    already built - an injected one, too. None, or the mode it is in, leaves it alone; so does a stage that is not a Wan2_2_VAE."""
+    model = getattr(vae, "model", None)
+    if precision is not None and hasattr(model, "prepare") and precision != getattr(model, "precision", None):
+        model.prepare(precision)
+
+
 class WanTI2V:
     def __init__(self, config=TI2VConfig, checkpoint_dir=None, device_id=0, rank=0, t5_fsdp=False, dit_fsdp=False,
                  use_sp=False, t5_cpu=False, init_on_cpu=True, convert_model_dtype=False, *, model: WanModel = None,
-                 vae=None, text_encoder: Optional[Callable] = None, device=None, ffn_precision=None, attn_precision=None, proj_precision=None):
+                 vae=None, text_encoder: Optional[Callable] = None, device=None, ffn_precision=None, attn_precision=None, proj_precision=None,
+                 vae_precision=None):
         if t5_fsdp or dit_fsdp:
             raise NotImplementedError("FSDP is not part of this build (UniVid passes False, models/model_pipeline.py:2205-2207; "
                                       "the fp32 masters + bf16 operands of the 5B DiT are 30 GB of a 288 GB GPU)")
@@ -278,13 +287,17 @@ class WanTI2V:
             vae_pth = os.path.join(checkpoint_dir, getattr(config, "vae_checkpoint", "Wan2.2_VAE.pth"))
             if self.vae is None and os.path.exists(vae_pth):
                 from .vae2_2 import Wan2_2_VAE
-                self.vae = Wan2_2_VAE(vae_pth=vae_pth, device=self.device, **dict(getattr(config, "vae_kwargs", {}) or {}))
+                vae_kwargs = dict(getattr(config, "vae_kwargs", {}) or {})
+                if vae_precision is not None:
+                    vae_kwargs["precision"] = vae_precision
+                self.vae = Wan2_2_VAE(vae_pth=vae_pth, device=self.device, **vae_kwargs)
             t5_pth = os.path.join(checkpoint_dir, getattr(config, "t5_checkpoint", "models_t5_umt5-xxl-enc-bf16.pth"))
             t5_tok = os.path.join(checkpoint_dir, getattr(config, "t5_tokenizer", "google/umt5-xxl"))
             if self.text_encoder is None and os.path.exists(t5_pth) and os.path.isdir(t5_tok):
                 from .t5 import T5EncoderModel
                 self.text_encoder = T5EncoderModel(text_len=config.text_len, dtype=torch.bfloat16, device=self.device, checkpoint_path=t5_pth,
                                                    tokenizer_path=t5_tok, encoder_kwargs=getattr(config, "t5_kwargs", None))
+        set_vae_precision(self.vae, vae_precision)      # an injected VAE too; None keeps its mode
         if use_sp:
             # textimage2video.py:106-118: Ulysses sequence parallelism over all ranks of the default process group; every rank
             # runs the same sample (same seed) and holds the full result after each forward

@@ -182,6 +182,7 @@ class _ConvOp:
         self.w_split = None
         self.w_split6 = None
         self.w_split_f16 = None      # (fp16 hi | lo pieces of w * scale, scale) for the f16x3 kernel
+        self.w_f16 = None            # (fp16(w * scale), scale) for the single-pass f16 kernel
         self.caches = {}     # (H, W, prefix) -> the cached frames [prefix, H, W, cin_pad] (zeros = the causal zero padding)
         self.rings = {}      # private input rings of the few convolutions whose channel count is padded (see _Engine.conv_input)
 
@@ -210,10 +211,21 @@ class _ConvOp:
             self.w_split_f16 = (buf, float(scale))
         return self.w_split_f16
 
+    def cast_f16(self):
+        """plain fp16 of w * scale ([Cout][taps * Cin], the hi pieces of split_f16 under the same scale) for the single-pass f16 kernel."""
+        if self.w_f16 is None:
+            scale = f16_weight_scale(float(self.w.abs().max()))
+            buf = torch.empty(self.w.numel(), dtype=torch.float16, device=self.w.device)
+            _lib.cast_weights_f16(self.w, buf, scale)
+            self.w_f16 = (buf, float(scale))
+        return self.w_f16
+
     def weights(self, kind):
-        """(weight operand, scale of the f16x3 split) of the convolution entry `kind` (_lib.conv3d)."""
+        """(weight operand, scale of the fp16 forms) of the convolution entry `kind` (_lib.conv3d)."""
         if kind == "f16x3":
             return self.split_f16()
+        if kind == "f16":
+            return self.cast_f16()
         return (self.split6() if kind == "bf16x6" else self.split() if kind == "bf16x3" else self.w), 1.0
 
     def phases(self):
@@ -239,26 +251,29 @@ class _ConvOp:
                     ph = object.__new__(_ConvOp)
                     ph.cout, ph.cin, ph.kt, ph.kh, ph.kw, ph.cin_pad = self.cout, self.cin, 1, 2, 2, self.cin_pad
                     ph.w = wp.float().reshape(self.cout, -1).contiguous()
-                    ph.w2d, ph.b, ph.w_split, ph.w_split6, ph.w_split_f16 = None, self.b, None, None, None
+                    ph.w2d, ph.b, ph.w_split, ph.w_split6, ph.w_split_f16, ph.w_f16 = None, self.b, None, None, None, None
                     ph.caches, ph.rings = {}, {}
                     out.append(ph)
             self._phases = out
         return self._phases
 
-    def cache(self, H, W, prefix=CACHE_T):
-        key = (H, W, prefix)
+    def cache(self, H, W, prefix=CACHE_T, slots=None):
+        """slots: f32-sized slots per cached pixel, cin_pad unless the input is plain fp16 (cin_pad / 2: _Engine.conv_input)."""
+        slots = self.cin_pad if slots is None else slots
+        key = (H, W, prefix) if slots == self.cin_pad else (H, W, prefix, slots)
         c = self.caches.get(key)
         if c is None:
-            c = self.caches[key] = torch.zeros(prefix, H, W, self.cin_pad, dtype=torch.float32, device=self.w.device)
+            c = self.caches[key] = torch.zeros(prefix, H, W, slots, dtype=torch.float32, device=self.w.device)
         return c
 
 
 class _Engine:
     def __init__(self, model: "WanVAE_", precision="fp32"):
-        if precision not in ("fp32", "bf16x6", "f16x3", "bf16x3"):
+        if precision not in ("fp32", "bf16x6", "f16x3", "bf16x3", "f16"):
             raise ValueError("precision must be 'fp32' (f32 MFMA, like the reference), 'bf16x6' (f32-grade: exact 3-way operand "
                              "splitting on the bf16 MFMA), 'f16x3' (f32-grade: 2-way fp16 splitting, 3 passes, for the convolutions "
-                             "behind an RMS_norm; bf16x6 elsewhere) or 'bf16x3' (2-way bf16 split, ~1e-5)")
+                             "behind an RMS_norm; bf16x6 elsewhere), 'bf16x3' (2-way bf16 split, ~1e-5) or 'f16' (narrow, opt-in: f16x3 "
+                             "with ONE pass on plain fp16 operands where the input channels are a multiple of 64)")
         self.m = model
         self.precision = precision
         self.ops = {}
@@ -268,16 +283,17 @@ class _Engine:
             elif isinstance(mod, nn.Conv2d):
                 self.ops[mod] = _ConvOp(mod, is2d=True)
         self.dev = next(model.parameters()).device
-        self.scratch = {}    # (H, W, channels) -> shared conv-input buffer [frames, H, W, channels]
+        self.scratch = {}    # (H, W, channels, format) -> shared conv-input buffer [frames, H, W, f32-sized slots per pixel]
         self._fmt = {}       # RMS_norm module -> activation format its output is written in (see split_fmt)
         self.phase_upsample = True      # upsampling 3x3 convolutions as four 2x2 phase convolutions (every mode but 'fp32'); A/B switch
 
     def split_fmt(self, norm, cin, cout):
         """Format in which RMS_norm (+ SiLU) writes the input of the convolution behind it: 0 = f32 rows, 1 = two bf16 pieces per
-        element (bf16x3), 2 = two IEEE fp16 pieces (f16x3). The fp16 form needs |activation| < 65 504: an RMS-normalised row is bounded
+        element (bf16x3), 2 = two IEEE fp16 pieces (f16x3), 3 = plain fp16 (f16 mode, cin % 64 == 0: the convolution runs ONE fp16 pass;
+        its other convolutions keep 2). The fp16 forms need |activation| < 65 504: an RMS-normalised row is bounded
         by sqrt(C) * max|gamma| (|x_i| / ||x|| <= 1; SiLU does not grow a magnitude), checked here ONCE per norm; a norm whose bound
         does not hold keeps f32 rows and its convolution runs as bf16x6 (exact splitting, no range limit)."""
-        if cin % 32 or cout % 4 or self.precision not in ("bf16x3", "f16x3"):
+        if cin % 32 or cout % 4 or self.precision not in ("bf16x3", "f16x3", "f16"):
             return 0
         if self.precision == "bf16x3":
             return 1 if cout % 32 == 0 else 0
@@ -285,7 +301,12 @@ class _Engine:
         if f is None:
             bound = math.sqrt(norm.gamma.numel()) * float(norm.gamma.detach().abs().max())
             f = self._fmt[norm] = 2 if bound < 6.0e4 else 0
-        return f
+        return 3 if f == 2 and self._plain(cin) else f
+
+    def _plain(self, cin):
+        """f16 mode runs a convolution f16x3 would run in three fp16 passes in ONE, on plain fp16 operands, where whole 128-byte rows of
+        64 fp16 channels exist."""
+        return self.precision == "f16" and cin % 64 == 0
 
     def reset(self):
         """WanVAE_.clear_cache (vae2_2.py:853-860): all cached frames back to the causal zero padding."""
@@ -295,15 +316,18 @@ class _Engine:
             for r in op.rings.values():
                 r.zero_()
 
-    def conv_input(self, op, H, W, T, fill, prefix=CACHE_T):
+    def conv_input(self, op, H, W, T, fill, prefix=CACHE_T, fmt=0):
         """The input of a cached (time-causal) convolution: [cached frames (prefix) | the T current frames, written by fill(dst)]
         as one [prefix + T, H, W, cin_pad] tensor, with the cache advanced to the last `prefix` frames of it for the next pass
         (the feature-cache update of vae2_2.py:219-232). The reference keeps 2 frames per convolution; so does this: the
         [prefix + T]-frame tensor itself is a scratch buffer SHARED by all convolutions of one (H, W, channels) shape, so its size
         follows the pass length T without multiplying by the number of convolutions. Convolutions whose channel count is padded
         (the first convolution of encoder and decoder) keep a small private ring instead: their pad channels must stay zero.
+        fmt = the format the filler writes (split_fmt): plain fp16 rows (3) are half the bytes, [.., cin_pad / 2] f32-sized slots, and the
+        shared buffers are keyed by format as well, so a plain ring is never handed to a consumer of f32-sized rows.
         Returns (input tensor, None | callable to run after the convolution has been launched)."""
         need = prefix + T
+        slots = op.cin_pad // 2 if fmt == 3 else op.cin_pad
         if op.cin != op.cin_pad:
             key = (H, W, prefix)
             ring = op.rings.get(key)
@@ -315,12 +339,12 @@ class _Engine:
             fill(ring[prefix:need])
             nxt = ring[T:need].clone()
             return ring[:need], lambda: ring[:prefix].copy_(nxt)
-        key = (H, W, op.cin_pad)
+        key = (H, W, op.cin_pad, 3 if fmt == 3 else 0)
         ring = self.scratch.get(key)
         if ring is None or ring.shape[0] < need:
             self.scratch[key] = None         # release the smaller buffer before allocating the larger one
-            ring = self.scratch[key] = torch.empty(need, H, W, op.cin_pad, dtype=torch.float32, device=self.dev)
-        cache = op.cache(H, W, prefix)
+            ring = self.scratch[key] = torch.empty(need, H, W, slots, dtype=torch.float32, device=self.dev)
+        cache = op.cache(H, W, prefix, slots)
         ring[:prefix].copy_(cache)
         fill(ring[prefix:need])
         cache.copy_(ring[T:need])
@@ -340,11 +364,16 @@ class _Engine:
 
     def _split16(self, x):
         """fp16 pieces of a RAW feature map (not an RMS_norm output) for uv_conv3d_f16x3, under the per-tensor power-of-two scale the
-        device finds (uv_vae_split_f16: 1 unless max |x| >= 2^15). Returns (split tensor, [1 / s, work] device scalars)."""
-        xs = torch.empty_like(x)
+        device finds (uv_vae_split_f16: 1 unless max |x| >= 2^15) - in f16 mode and with whole 64-channel rows, plain fp16 under the same
+        scale for uv_conv3d_f16 (uv_vae_cast_f16; half the bytes). Returns (fp16 tensor, [1 / s, work] device scalars, its in_split)."""
         sc = torch.empty(2, dtype=torch.float32, device=self.dev)
+        if self._plain(x.shape[-1]):
+            xs = torch.empty(*x.shape[:-1], x.shape[-1] // 2, dtype=torch.float32, device=self.dev)
+            _lib.vae_cast_f16(x, xs, sc)
+            return xs, sc, 3
+        xs = torch.empty_like(x)
         _lib.vae_split_f16(x, xs, sc)
-        return xs, sc
+        return xs, sc, 2
 
     def _pointwise(self, op, x, resid=None):
         """1x1(x1) convolution = fp32 GEMM over pixel rows."""
@@ -354,10 +383,10 @@ class _Engine:
     # -- blocks --
     def causal_conv(self, conv, fill, T, H, W, resid=None, in_split=0):
         """3x3x3 causal conv over [cache(2) | T frames]; `fill(dst)` writes the current frames.
-        in_split: the filler writes split activations (1 = bf16 pieces, bf16x3 mode; 2 = fp16 pieces, f16x3 mode; zeros stay zeros,
-        so the cache logic is unchanged)."""
+        in_split: the filler writes split activations (1 = bf16 pieces, bf16x3 mode; 2 = fp16 pieces, f16x3 mode; 3 = plain fp16, f16 mode;
+        zeros stay zeros, so the cache logic is unchanged)."""
         op = self.ops[conv]
-        ring, after = self.conv_input(op, H, W, T, fill)
+        ring, after = self.conv_input(op, H, W, T, fill, fmt=in_split)
         y = self._conv(op, ring, CACHE_T + T, H, W, T, H, W, t_off=0, ph=1, pw=1, resid=resid, in_split=in_split)
         if after is not None:
             after()
@@ -369,11 +398,11 @@ class _Engine:
         res = blk.residual
         if isinstance(blk.shortcut, nn.Identity):
             h = x
-        elif self.precision == "f16x3" and C % 32 == 0 and blk.out_dim % 4 == 0 and x.is_contiguous() and H * W >= 16384:     # (per-FRAME size: the choice never depends on the pass length)
+        elif self.precision in ("f16x3", "f16") and C % 32 == 0 and blk.out_dim % 4 == 0 and x.is_contiguous() and H * W >= 16384:     # (per-FRAME size: the choice never depends on the pass length)
             # the 1x1x1 shortcut of the channel-changing blocks (1024 -> 512, 512 -> 256 on 16 large frames: 8 ms each on the exact-f32
             # GEMM) as a three-pass fp16 product too: raw rows, so under the device-found per-tensor scale (uv_vae_split_f16)
-            xs, sc = self._split16(x)
-            h = self._conv(self.ops[blk.shortcut], xs, T, H, W, T, H, W, in_split=2, act_scale=sc)
+            xs, sc, fmt = self._split16(x)
+            h = self._conv(self.ops[blk.shortcut], xs, T, H, W, T, H, W, in_split=fmt, act_scale=sc)
         else:
             h = self._pointwise(self.ops[blk.shortcut], x)
         sp1, sp2 = self.split_fmt(res[0], C, blk.out_dim), self.split_fmt(res[3], blk.out_dim, blk.out_dim)
@@ -411,11 +440,11 @@ class _Engine:
         if rs.mode == "upsample3d" and not first_chunk:
             op = self.ops[rs.time_conv]
             ring, after = self.conv_input(op, H, W, T, lambda dst: dst.copy_(x))
-            if self.precision == "f16x3" and C % 32 == 0 and ring.is_contiguous():
+            if self.precision in ("f16x3", "f16") and C % 32 == 0 and ring.is_contiguous():
                 # raw residual-stream rows: the whole [cache | pass] input as fp16 pieces under ONE device-found scale (the cache frames
                 # stay f32 in the ring, so passes with different scales never mix), three fp16 passes instead of bf16x6's six
-                r16, sc = self._split16(ring)
-                x = self._conv(op, r16, CACHE_T + T, H, W, T, H, W, t_off=0, interleave=1, in_split=2, act_scale=sc)
+                r16, sc, fmt = self._split16(ring)
+                x = self._conv(op, r16, CACHE_T + T, H, W, T, H, W, t_off=0, interleave=1, in_split=fmt, act_scale=sc)
             else:
                 x = self._conv(op, ring, CACHE_T + T, H, W, T, H, W, t_off=0, interleave=1)
             if after is not None:
@@ -429,9 +458,8 @@ class _Engine:
         # (2.25 x fewer multiply-adds; _ConvOp.phases). precision='fp32' keeps the reference's 36 separate products.
         out = torch.empty(T, 2 * H, 2 * W, op.cout, dtype=torch.float32, device=self.dev)
         fmt, sc = 0, None
-        if self.precision == "f16x3" and C % 32 == 0 and x.is_contiguous():
-            x, sc = self._split16(x)        # raw residual-stream rows: fp16 pieces under a device-found per-tensor scale
-            fmt = 2
+        if self.precision in ("f16x3", "f16") and C % 32 == 0 and x.is_contiguous():
+            x, sc, fmt = self._split16(x)   # raw residual-stream rows: fp16 pieces under a device-found per-tensor scale
         for k, ph in enumerate(op.phases()):
             a, b = k >> 1, k & 1
             self._conv(ph, x, T, H, W, T, H, W, ph=1 - a, pw=1 - b, up=2 + k, out=out, in_split=fmt, act_scale=sc)
@@ -440,9 +468,9 @@ class _Engine:
     def downsample(self, rs, x, first_chunk):
         """Resample.forward (downsample2d / downsample3d) vae2_2.py:153-169."""
         T, H, W, C = x.shape
-        if self.precision == "f16x3" and C % 32 == 0 and x.is_contiguous():
-            xs, sc = self._split16(x)
-            y = self._conv(self.ops[rs.resample[1]], xs, T, H, W, T, H // 2, W // 2, sh=2, sw=2, in_split=2, act_scale=sc)
+        if self.precision in ("f16x3", "f16") and C % 32 == 0 and x.is_contiguous():
+            xs, sc, fmt = self._split16(x)
+            y = self._conv(self.ops[rs.resample[1]], xs, T, H, W, T, H // 2, W // 2, sh=2, sw=2, in_split=fmt, act_scale=sc)
         else:
             y = self._conv(self.ops[rs.resample[1]], x, T, H, W, T, H // 2, W // 2, sh=2, sw=2)
         if rs.mode == "downsample3d":
@@ -563,7 +591,9 @@ class WanVAE_(nn.Module):
         bf16 matrix pipe by exact three-way operand splitting (6 passes; as close to an fp64 convolution as the f32 MFMA kernel,
         1.45 x faster) | 'f16x3' (default) = f32-grade too, in 3 passes: the convolutions behind an RMS_norm (ResidualBlocks, heads: ~90 % of
         the FLOPs) take both operands as two IEEE fp16 pieces (22 significant bits; their error against fp64 equals the f32 MFMA's,
-        which is accumulation-bound), the others run as bf16x6 | 'bf16x3' = two-way bf16 split, 3 passes (~1e-5 relative error).
+        which is accumulation-bound), the others run as bf16x6 | 'bf16x3' = two-way bf16 split, 3 passes (~1e-5 relative error) |
+        'f16' = NARROW, opt-in: f16x3 with every three-pass convolution whose input channels are a multiple of 64 run as ONE fp16 pass on
+        plain fp16 operands (11-bit operands, exact products, f32 accumulate: ~5e-4 rms on a [-1, 1] video; everything else as f16x3).
         The 1x1 convolutions, norms and the per-frame attention stay on the f32 kernels in every mode."""
         if next(self.parameters()).device.type != "cuda":
             raise _lib.UnividHipError("WanVAE_.prepare: parameters must be on the GPU - there is no CPU path in univid_amd")
@@ -670,7 +700,8 @@ class Wan2_2_VAE:
         """precision (extension; WanVAE_.prepare): 'f16x3' - the DEFAULT since round 4: f32-grade arithmetic (measured as close to an
         fp64 convolution as the exact f32 MFMA, every element of a full 49 x 720 x 1280 clip inside rtol 1e-3 / atol 1e-4 of the fp32 CPU
         oracle) at a third of the exact mode's time; 'fp32' = the reference's dtype executed literally on the f32 MFMA; 'bf16x6';
-        'bf16x3'. Tensors in and out are fp32 in every mode (vae2_2.py:897)."""
+        'bf16x3'; 'f16' = the opt-in narrow mode (one fp16 pass instead of three where Cin % 64 == 0, not f32-grade: WanVAE_.prepare).
+        Tensors in and out are fp32 in every mode (vae2_2.py:897)."""
         self.dtype = dtype
         self.device = torch.device(device)
         mean = torch.tensor(_MEAN, dtype=dtype, device=device)
