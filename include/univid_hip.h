@@ -37,10 +37,12 @@ int uv_host_blocking_sync(int on);
  *                     the LDS-halo kernel instead of the gather kernel (the two sum their k-tiles in different orders: ~1e-5 apart)
  *   UV_OPT_GEMM_GM    0 automatic (default) | 1..64: tile-walk group height of the persistent GEMM (tile order only, results unchanged)
  *   UV_OPT_ATTN_CUT   0 automatic (default) | v: flash_attn_fwd12_kernel cuts every head with v - 1 eight-unit blocks (results unchanged)
+ *   UV_OPT_ATTN_WIN_FORM   0 automatic (default: the span rule of uv_flash_attn_win_plan) | 1 the 12-wave | 2 the 4-wave form of uv_flash_attn_win_bf16 (results unchanged)
  * uv_set_option rejects unknown keys / out-of-range values; uv_reset_options restores every default. Host-only, thread-safe. */
 #define UV_OPT_CONV_HALO 0
 #define UV_OPT_GEMM_GM 1
 #define UV_OPT_ATTN_CUT 2
+#define UV_OPT_ATTN_WIN_FORM 3
 int uv_set_option(int key, int value);
 int uv_get_option(int key, int* value);
 int uv_reset_options(void);
@@ -220,6 +222,25 @@ int uv_flash_attn_kernel_name(int Lk, int head_dim, long ldk, long ldvt, int f16
  * 128 queries), and *grid = q_blocks * H * batch workgroups. Host-only; for tests and tuning tools. */
 int uv_flash_attn_plan(int batch, int Lq, int Lk, int H, int head_dim, long ldk, long ldvt, int f16, char* kernel, int len,
                        int* q_blocks, int* n12, int* grid);
+
+/* ---- DiT: sliding-window / causal self-attention (opt-in; WanModel.set_attn_window) -----------------------------------------------
+ * uv_flash_attn_bf16 for Lq == Lk == L with flash_attn_varlen_func's window_size = (win_left, win_right) (attention.py:113-127 as called at
+ * model.py:145-150; WanModel's window_size, a key of every checkpoint's config.json): query i of a sample attends key j iff
+ * max(0, i - win_left) <= j <= min(L - 1, i + win_right), -1 = unbounded on that side; causal is win_right = 0. Every sample of the batch
+ * restarts at i = 0. Exact - the same softmax over fewer keys: key tiles outside a workgroup's window are neither staged nor visited, and
+ * (-1, -1), which visits every tile, or any window that covers every key reproduces uv_flash_attn_bf16 bit for bit. A query's bits do
+ * not depend on the kernel form, the query-block cut, the batch or its neighbours. q / k / vt / out / ld* / batch / H / softmax_scale:
+ * uv_flash_attn_bf16's meaning and checks (the ldvt cover and its finite pad, L % 8 == 0 when batch > 1), and 64 ldk, 128 ldvt < 2^30
+ * elements. head_dim 128 only; win_left, win_right >= -1. Anything else is rejected and nothing is written. Bottom-right alignment for
+ * Lq != Lk and ragged key lengths are not built. */
+int uv_flash_attn_win_bf16(const void* q, long ldq, const void* k, long ldk, const void* vt, long ldvt, void* out, long ldo, int batch, int L,
+                           int H, int head_dim, float softmax_scale, int win_left, int win_right, void* stream);
+
+/* The launch plan of uv_flash_attn_win_bf16, as uv_flash_attn_plan reports uv_flash_attn_bf16's: flash_attn_win12_kernel when the keys one
+ * workgroup streams, min(L, 384 + win_left + win_right) with an unbounded side counted as L, are at least 2048 (the cut and grid of
+ * uv_flash_attn_plan for the same batch, L, H), else flash_attn_win4_kernel (blocks of 128 queries, *n12 = 0). Host-only. */
+int uv_flash_attn_win_plan(int batch, int L, int H, int head_dim, int win_left, int win_right, char* kernel, int len, int* q_blocks, int* n12,
+                           int* grid);
 
 /* ---- DiT: self-attention with MXFP8 q / k (opt-in mode; WanModel.set_attn_precision("mxfp8_qk")) ------------------------------
  * uv_flash_attn_bf16 with q and k in the MXFP8 format stated above (e4m3fn codes, one e8m0 byte per 32 consecutive elements of a row, e =

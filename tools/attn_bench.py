@@ -1,4 +1,8 @@
-"""Attention-only micro benchmark (developer tool): full-size self-attention launches for profiling."""
+"""Attention-only micro benchmark (developer tool): full-size self-attention launches for profiling.   env: L (11440), B (1), LK (L), N (5), ROUNDS (7)
+    --qk mxfp8          bf16 against the MXFP8 q / k and q / k + P.V modes, launches and producers alternating in one process
+    --window L,R[:L,R...]   the dense launch against uv_flash_attn_win_bf16 under each window (-1 = unbounded; -1,0 = causal), and against (-1,-1)
+                        through the same entry - which visits every tile: what the classification costs -, all alternating in one process;
+                        --forms: every window also on the 12-wave and on the 4-wave form (OPT_ATTN_WIN_FORM), whatever the plan's rule says"""
 import math, os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from univid_amd import _lib
@@ -81,3 +85,55 @@ if "--qk" in sys.argv and sys.argv[sys.argv.index("--qk") + 1] == "mxfp8":
     print(f"launch + producers (q / k producer and V^T quantiser): mxfp8_qk_pv {tot_p:.1f} us, ratio to bf16 {tot_p / tot_b:.3f}, to mxfp8_qk {tot_p / tot_m:.3f} "
           f"(bf16 spread {spread:.1f} us); kernel={_lib.attn_mxpv_plan(L, Lk, D, B, H)['kernel']}; rel rms of the mxpv output against bf16 on the same "
           f"operands {float((out_pv.float() - out.float()).pow(2).mean().sqrt() / out.float().pow(2).mean().sqrt()):.3e}")
+
+
+if "--window" in sys.argv:
+    # Dense and windowed launches on the same random operands, alternating round by round in ONE process, the first round dropped; medians and
+    # the spread (min .. max) of the ROUNDS rounds. Per launch also the 32-query x 64-key tiles the waves COMPUTE (host arithmetic, the kernels'
+    # own rule) and the time per computed tile, next to the dense kernel's. plan_attn_win's 12-wave rule is measured with windows on either
+    # side of span 2048, e.g. 832,831 (span 2047: the 4-wave form) against 832,832 (2048: the 12-wave form) - the same work to one key.
+    import statistics
+    assert L == Lk, "windows are built for self-attention (Lq == Lk)"
+    rounds = int(os.environ.get("ROUNDS", 7))
+    wins = [tuple(int(x) for x in w.split(",")) for w in sys.argv[sys.argv.index("--window") + 1].split(":")]
+    wins = [(-1, -1)] + [w for w in wins if w != (-1, -1)]
+
+    def wave_tiles(win):
+        le, ri = (L if w < 0 else min(w, L) for w in win)
+        return B * H * sum(min(L - 1, min(u * 32 + 31, L - 1) + ri) // 64 - max(0, u * 32 - le) // 64 + 1 for u in range((L + 31) // 32))
+
+    forms = (0, 1, 2) if "--forms" in sys.argv else (0,)
+    outs = {(w, f): torch.empty_like(out) for w in wins for f in forms}
+
+    def win_launch(w, f):
+        _lib.set_option(_lib.OPT_ATTN_WIN_FORM, f)
+        _lib.flash_attn_win(q, k, vt, outs[w, f], L, H, D, 1 / math.sqrt(D), w, batch=B)
+        _lib.set_option(_lib.OPT_ATTN_WIN_FORM, 0)
+
+    work = {"dense": lambda: _lib.flash_attn(q, k, vt, out, L, L, H, D, 1 / math.sqrt(D), batch=B)}
+    for key in outs:
+        work[key] = (lambda key=key: win_launch(*key))
+    times = {name: [] for name in work}
+    for rnd in range(rounds + 1):
+        for name, fn in work.items():
+            fn(); torch.cuda.synchronize()
+            s.record()
+            for _ in range(n):
+                fn()
+            e.record(); torch.cuda.synchronize()
+            if rnd:
+                times[name].append(s.elapsed_time(e) / n * 1e3)
+    med = {name: statistics.median(t) for name, t in times.items()}
+    dense_tiles = B * H * ((L + 31) // 32) * ((L + 63) // 64)
+    print(f"dense B{B} L{L}: median {med['dense']:.1f} us (min {min(times['dense']):.1f} max {max(times['dense']):.1f}, {rounds} rounds of {n}); "
+          f"{dense_tiles} wave tiles, {med['dense'] * 1e3 / dense_tiles:.3f} ns per tile; kernel={_lib.attn_plan(L, L, D, B, H)['kernel']}")
+    assert all(torch.equal(outs[(-1, -1), f], out) for f in forms), "(-1, -1) through the win entry differs from the dense launch"
+    for w, f in outs:
+        assert torch.equal(outs[w, f], outs[w, 0]), "the form changes the bits"
+        t, tiles, key = times[w, f], wave_tiles(w), (w, f)
+        _lib.set_option(_lib.OPT_ATTN_WIN_FORM, f)
+        plan = _lib.attn_win_plan(L, D, B, H, w)
+        _lib.set_option(_lib.OPT_ATTN_WIN_FORM, 0)
+        print(f"window {w} form {('auto', '12-wave', '4-wave')[f]} B{B} L{L}: median {med[key]:.1f} us (min {min(t):.1f} max {max(t):.1f}); {med[key] / med['dense']:.4f} x dense, "
+              f"dense / window = {med['dense'] / med[key]:.3f}; {tiles} wave tiles ({tiles / dense_tiles:.4f} of dense), {med[key] * 1e3 / tiles:.3f} ns per tile "
+              f"({med[key] / tiles / (med['dense'] / dense_tiles):.3f} x the dense kernel's); plan={plan}")

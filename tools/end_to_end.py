@@ -9,6 +9,8 @@ f32-grade bf16x6 / f16x3 modes - at the bench size (49 frames of 704 x 1280) and
     --proj-precision bf16|mxfp8   the DiT's attention projections in the opt-in MXFP8 mode (WanModel.set_proj_precision)
     --proj-ab ROUNDS [--also-with-mx]   instead of the table: ms per denoise step with the attention projections in bf16 and mxfp8, alternating in one
                        process; --also-with-mx repeats the comparison beside ffn_precision mxfp8 + attn_precision mxfp8_qk_pv in the same process
+    --attn-window L,R   the DiT's self-attention under flash-attn's window_size = (L, R) tokens (WanModel.set_attn_window; -1 = unbounded)
+    --window-ab ROUNDS   instead of the table: ms per denoise step with global attention and with --attn-window, alternating in one process
     --attn-ab ROUNDS   instead of the table: ms per denoise step with the self-attention in bf16, mxfp8_qk and mxfp8_qk_pv, alternating in one process"""
 import os, sys, time, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -64,7 +66,10 @@ attn_precision = sys.argv[sys.argv.index("--attn-precision") + 1] if "--attn-pre
 m.set_attn_precision(attn_precision)
 proj_precision = sys.argv[sys.argv.index("--proj-precision") + 1] if "--proj-precision" in sys.argv else "bf16"
 m.set_proj_precision(proj_precision)
-print(f"ffn_precision {ffn_precision} attn_precision {attn_precision} proj_precision {proj_precision}", flush=True)
+attn_window = tuple(int(v) for v in sys.argv[sys.argv.index("--attn-window") + 1].split(",")) if "--attn-window" in sys.argv else None
+if "--window-ab" not in sys.argv:
+    m.set_attn_window(attn_window)
+print(f"ffn_precision {ffn_precision} attn_precision {attn_precision} proj_precision {proj_precision} attn_window {attn_window}", flush=True)
 m.prepare()
 g = torch.Generator(device=dev).manual_seed(1)
 pe = [torch.randn(40, 4096, device=dev, generator=g) * 0.1]
@@ -73,6 +78,32 @@ ne = [torch.randn(9, 4096, device=dev, generator=g) * 0.1]
 
 frames = [int(f) for f in os.environ.get("FRAMES", "49,121").split(",")]
 precs = os.environ.get("PRECS", "fp32,bf16x6,f16x3").split(",")
+if "--window-ab" in sys.argv:
+    # --window-ab ROUNDS: the denoise loop alone (t2v, decode=False) at the first FRAMES entry with global attention and with --attn-window,
+    # alternating round by round in THIS process (each switch re-captures: its warm-up generation is not timed), the first round dropped;
+    # medians and the spread of the rounds. The precision options apply to both sides.
+    import statistics
+    assert attn_window is not None, "--window-ab needs --attn-window L,R"
+    rounds, F = int(sys.argv[sys.argv.index("--window-ab") + 1]), frames[0]
+    pipe = WanTI2V(model=m, vae=Wan2_2_VAE(device=dev, seed=0, precision="f16x3"), device=dev)
+    ms = {None: [], attn_window: []}
+    for rnd in range(rounds + 1):
+        for win in ms:
+            m.set_attn_window(win)
+            with torch.no_grad():
+                pipe.t2v("", size=(1280, 704), frame_num=F, sampling_steps=2, seed=7, prompt_embeds=pe, negative_prompt_embeds=ne, decode=False)
+                lat, t = clock(lambda: pipe.t2v("", size=(1280, 704), frame_num=F, sampling_steps=steps, seed=7, prompt_embeds=pe,
+                                                negative_prompt_embeds=ne, decode=False))
+            assert bool(torch.isfinite(lat).all())
+            if rnd:
+                ms[win].append(t / steps * 1e3)
+    med = {k: statistics.median(v) for k, v in ms.items()}
+    for k, v in ms.items():
+        print(f"{F} frames, ffn {ffn_precision}, attn {attn_precision}, window {k}: median {med[k]:.2f} ms/step (min {min(v):.2f} max {max(v):.2f}, {len(v)} rounds of "
+              f"{steps} steps)", flush=True)
+    print(f"window / global = {med[attn_window] / med[None]:.4f}, gain {med[None] - med[attn_window]:.2f} ms/step (global spread "
+          f"{max(ms[None]) - min(ms[None]):.2f} ms)", flush=True)
+    sys.exit(0)
 if "--attn-ab" in sys.argv:
     # --attn-ab ROUNDS: the denoise loop alone (t2v, decode=False) at the first FRAMES entry with the self-attention in "bf16", "mxfp8_qk" and "mxfp8_qk_pv",
     # alternating round by round in THIS process (each switch re-prepares and re-captures: its warm-up generation is not timed), the first

@@ -47,6 +47,8 @@ SIGNATURES = {
     "uv_flash_attn_bf16_qnorm": [_P, _L, _P, _L, _P, _L, _P, _L, _I, _I, _I, _I, _I, _F, _P, _P, _P],
     "uv_flash_attn_bf16": [_P, _L, _P, _L, _P, _L, _P, _L, _I, _I, _I, _I, _I, _F, _P],
     "uv_flash_attn_f16": [_P, _L, _P, _L, _P, _L, _P, _L, _I, _I, _I, _I, _I, _F, _P],
+    "uv_flash_attn_win_bf16": [_P, _L, _P, _L, _P, _L, _P, _L, _I, _I, _I, _I, _F, _I, _I, _P],
+    "uv_flash_attn_win_plan": [_I, _I, _I, _I, _I, _I, _c.c_char_p, _I, _c.POINTER(_I), _c.POINTER(_I), _c.POINTER(_I)],
     "uv_flash_attn_mxqk": [_P, _L, _P, _L, _P, _L, _P, _L, _P, _L, _P, _L, _I, _I, _I, _I, _I, _F, _P],
     "uv_flash_attn_mxqk_plan": [_I, _I, _I, _I, _I, _c.c_char_p, _I, _c.POINTER(_I), _c.POINTER(_I), _c.POINTER(_I)],
     "uv_vt_mx_quant": [_P, _L, _P, _L, _P, _L, _I, _I, _I, _I, _P],
@@ -108,7 +110,7 @@ SIGNATURES = {
 }
 _RESTYPE = {"uv_last_error": _c.c_char_p, "uv_build_id": _c.c_char_p, "uv_gemm_splitk_ws_bytes": _L}
 
-OPT_CONV_HALO, OPT_GEMM_GM, OPT_ATTN_CUT = range(3)      # include/univid_hip.h: UV_OPT_*
+OPT_CONV_HALO, OPT_GEMM_GM, OPT_ATTN_CUT, OPT_ATTN_WIN_FORM = range(4)      # include/univid_hip.h: UV_OPT_*
 EPI_BF16, EPI_GELU_BF16, EPI_F32_FROM_BF16, EPI_RESID_F32, EPI_GATE_RESID_F32, EPI_BF16_T = range(6)
 
 _lib = None
@@ -560,6 +562,30 @@ def attn_plan(Lq, Lk, D, batch=1, H=1, f16=False, ldk=None, ldvt=None):
     ldvt = vt_cols(batch, Lk) if ldvt is None else ldvt
     lib = load()
     if lib.uv_flash_attn_plan(batch, Lq, Lk, H, D, int(ldk), int(ldvt), int(f16), buf, 96, ctypes.byref(qb), ctypes.byref(n12), ctypes.byref(grid)) != 0:
+        raise UnividHipError(lib.uv_last_error().decode())
+    return dict(kernel=buf.value.decode(), q_blocks=qb.value, n12=n12.value, grid=grid.value)
+
+
+def flash_attn_win(q, k, vt, out, L, H, D, scale, window, batch=1):
+    """`flash_attn` for Lq == Lk == L under flash-attn's window_size = (left, right): query i attends keys max(0, i - left) ..
+    min(L - 1, i + right) of its sample, -1 = unbounded on that side (causal = right 0). bf16, head_dim 128 only; (-1, -1) visits every key
+    and equals `flash_attn` bit for bit."""
+    C = H * D
+    left, right = (int(w) for w in window)
+    _check("flash_attn_win", (q, "q", BF16, C, batch * L), (k, "k", BF16, C, batch * L), (vt, "vt", BF16, vt_cols(batch, L), C),
+           (out, "out", BF16, C, batch * L))
+    call("uv_flash_attn_win_bf16", ptr(q), q.stride(-2), ptr(k), k.stride(-2), ptr(vt), vt.stride(-2), ptr(out), out.stride(-2), batch, L, H, D,
+         float(scale), left, right, stream_ptr(), flops=4 * batch * L * L * H * D)
+    return out
+
+
+def attn_win_plan(L, D=128, batch=1, H=1, window=(-1, -1)):
+    """Launch plan of `flash_attn_win` for this geometry and window, as `attn_plan` reports `flash_attn`'s."""
+    buf = ctypes.create_string_buffer(96)
+    qb, n12, grid = _I(0), _I(0), _I(0)
+    lib = load()
+    if lib.uv_flash_attn_win_plan(batch, L, H, D, int(window[0]), int(window[1]), buf, 96, ctypes.byref(qb), ctypes.byref(n12),
+                                  ctypes.byref(grid)) != 0:
         raise UnividHipError(lib.uv_last_error().decode())
     return dict(kernel=buf.value.decode(), q_blocks=qb.value, n12=n12.value, grid=grid.value)
 

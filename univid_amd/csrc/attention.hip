@@ -47,8 +47,6 @@ __device__ unsigned long long* uv_attn_tl;
 #define UV_TL_HW(id) do {} while (0)
 #endif
 
-typedef __attribute__((address_space(3))) void lds_void_a;
-
 // D = head_dim (128 for TI2V-5B; 64 for the reference's CPU-runnable tiny config and the SigLIP2 ranker).
 // 4 waves x 32 queries per workgroup, 2 workgroups per CU: the two waves that share a SIMD then belong to DIFFERENT workgroups, are
 // not re-aligned by a common barrier every tile, and drift into complementary phases - one in its MFMA cluster while the other
@@ -338,19 +336,7 @@ __global__ __launch_bounds__(256, 2) void flash_attn_fwd_kernel(AttnArgs p) {
 // A lone wave needs ~3 440 cycles per tile of which 1 024 are MFMA issue; two waves per SIMD overlap almost perfectly
 // (3 500 cycles per PAIR of tiles), i.e. the chain is latency- not throughput-bound and a third wave has room.
 // ------------------------------------------------------------------------------------------------------------------------
-// One LDS-DMA piece with a UNIFORM base pointer (SGPR pair) and a 32-bit lane offset: "global_load_lds_dwordx4 voff, s[base]".
-// hipcc selects only the 64-bit-VGPR-address form for the builtin (one v_lshl_add_u64 and a live register pair per piece).
-// M0 = wave-uniform LDS byte address of the piece; saved and restored around the statement (the compiler owns M0).
-__device__ __forceinline__ void glds16_sbase(const char* sbase, unsigned voff, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(voff), "s"(sbase), "s"(lds_dst)
-                 : "memory");
-}
-
-constexpr int UV_ATT_AHEAD = 3;      // fwd3 / fwd12: fragment reads in flight ahead of their MFMA (2 .. 5 measured: all within 0.5 %)
-
+// glds16_sbase (one LDS-DMA piece from a uniform base pointer) and UV_ATT_AHEAD: attn_args.h, shared with attention_win.hip
 template <int QN = 0>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void flash_attn_fwd3_kernel(AttnArgs p) {
     constexpr int D = 128, NW = 4, KROW = 256, NKK = 8, ND = 4;

@@ -27,10 +27,17 @@ struct AttnArgs {
     const float* q_w;
 };
 
-enum AttnKernel { ATT_FWD12 = 0, ATT_FWD3 = 1, ATT_FWD_D128 = 2, ATT_FWD_D64 = 3, ATT_MXQK12 = 4, ATT_MXQK4 = 5, ATT_MXPV12 = 6, ATT_MXPV4 = 7 };
+// attention_win.hip: AttnArgs (Lq == Lk, q_rs / q_w unused) plus the window, every bound already resolved: 0 <= left, right <= L
+struct AttnWinArgs : AttnArgs {
+    int left, right;
+};
+
+enum AttnKernel { ATT_FWD12 = 0, ATT_FWD3 = 1, ATT_FWD_D128 = 2, ATT_FWD_D64 = 3, ATT_MXQK12 = 4, ATT_MXQK4 = 5, ATT_MXPV12 = 6, ATT_MXPV4 = 7,
+                  ATT_WIN12 = 8, ATT_WIN4 = 9 };
 static const char* const kAttnKernelName[] = {"flash_attn_fwd12_kernel", "flash_attn_fwd3_kernel", "flash_attn_fwd_kernel<128>",
                                               "flash_attn_fwd_kernel<64>", "flash_attn_mxqk12_kernel", "flash_attn_mxqk4_kernel",
-                                              "flash_attn_mxpv12_kernel", "flash_attn_mxpv4_kernel"};
+                                              "flash_attn_mxpv12_kernel", "flash_attn_mxpv4_kernel",
+                                              "flash_attn_win12_kernel", "flash_attn_win4_kernel"};
 struct AttnPlan {
     int kernel;            // AttnKernel
     int q_blocks, n12;     // query blocks per (sample, head); of them the 12-unit ones (flash_attn_fwd12_kernel only, else 0)
@@ -115,7 +122,37 @@ static inline AttnPlan plan_attn_mxpv(int batch, int Lq, int Lk, int H, int ncus
     return plan;
 }
 
+// The sliding-window / causal kernels (attention_win.hip; self-attention, Lq == Lk == L, head_dim 128, bf16): query i attends keys
+// max(0, i - left) .. min(L - 1, i + right), -1 = unbounded on that side. plan_attn's decision for the dense problem whose key count is the
+// span of keys ONE workgroup streams, min(L, 384 + left + right) with an unbounded side counted as L: the dense plan's Lk >= 2048 threshold
+// applied to what a 12-wave workgroup of 384 queries actually stages (carried over from the dense plan; profiles/attn_window_bench.md
+// holds what was measured around it). The cut and the grid are the dense plan's for (batch, L, H). Workgroups of a causal or one-sided
+// launch stream unequal key counts; the makespan model assumes equal ones (known, unmeasured).
+static inline AttnPlan plan_attn_win(int batch, int L, int H, int left, int right, int ncus, int force_cut, int force_form = 0) {
+    long span = 384L + (left < 0 ? L : left) + (right < 0 ? L : right);
+    if (span > L) span = L;
+    if (force_form) span = force_form == 1 ? 2048 : 1;       // UV_OPT_ATTN_WIN_FORM (A/B tools): the form whatever the span; a query's bits do not depend on it
+    AttnPlan plan = plan_attn(batch, L, (int)span, H, 128, 8, 8, false, ncus, force_cut);
+    plan.kernel = plan.kernel == ATT_FWD12 ? ATT_WIN12 : ATT_WIN4;
+    return plan;
+}
+
 // ---- device code the kernels share
+typedef __attribute__((address_space(3))) void lds_void_a;
+
+// One LDS-DMA piece with a UNIFORM base pointer (SGPR pair) and a 32-bit lane offset: "global_load_lds_dwordx4 voff, s[base]".
+// hipcc selects only the 64-bit-VGPR-address form for the builtin (one v_lshl_add_u64 and a live register pair per piece).
+// M0 = wave-uniform LDS byte address of the piece; saved and restored around the statement (the compiler owns M0).
+__device__ __forceinline__ void glds16_sbase(const char* sbase, unsigned voff, unsigned lds_dst) {
+    unsigned keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep)
+                 : "v"(voff), "s"(sbase), "s"(lds_dst)
+                 : "memory");
+}
+
+constexpr int UV_ATT_AHEAD = 3;      // fwd3 / fwd12: fragment reads in flight ahead of their MFMA (2 .. 5 measured: all within 0.5 %)
+
 // Independent samples are stacked along the token axis: rows of q / k / out, COLUMNS of V^T. Moves the argument block to sample b.
 template <int QN>
 __device__ __forceinline__ void attn_sample_offset(AttnArgs& p, long b) {
@@ -201,4 +238,34 @@ __device__ __forceinline__ void attn_frag_addrs(unsigned smem_a, unsigned v_off,
     for (int T = 0; T < 2; ++T)
 #pragma unroll
         for (int s2 = 0; s2 < 2; ++s2) vaddr[T][s2] = smem_a + v_off + r * 128 + (((4 * T + 2 * s2 + h) ^ v_key) << 4);
+}
+
+// O rows of one wave through a wave-private LDS image (flash_attn_fwd12_kernel's epilogue, for kernels written after it): 32 rows x (128 + 16)
+// bytes at img, two passes of two d-blocks; every store instruction writes 8 whole 128-byte lines. ldo % 8 == 0. The caller owns the LDS
+// (every reader of what it held has passed a barrier).
+__device__ __forceinline__ void attn_store_lds(char* img, bf16_t* out0, long ldo, int rows, int lane, const f32x16 (&oacc)[4], float inv) {
+    constexpr int RS = 144;
+    const int r = lane & 31, h = lane >> 5, srow = lane >> 3, chunk = lane & 7;
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+#pragma unroll
+        for (int dd = 0; dd < 2; ++dd)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const int d = 2 * half + dd;
+                u32x2 o = {pack16_2<false>(oacc[d][4 * g + 0] * inv, oacc[d][4 * g + 1] * inv),
+                           pack16_2<false>(oacc[d][4 * g + 2] * inv, oacc[d][4 * g + 3] * inv)};
+                *(u32x2*)(img + r * RS + 64 * dd + 16 * g + 8 * h) = o;
+            }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // wave-private image: no barrier
+        u32x4 v[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) v[i] = *(const u32x4*)(img + (8 * i + srow) * RS + chunk * 16);
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the second pass overwrites the image
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int row = 8 * i + srow;
+            if (row < rows) *(u32x4*)(out0 + (long)row * ldo + 64 * half + chunk * 8) = v[i];
+        }
+    }
 }

@@ -133,7 +133,8 @@ __device__ __forceinline__ float silu_f32(float x) { return x / (1.0f + expf(-x)
 #define UV_OPT_CONV_HALO 0     // -1 automatic (default), 0 never the LDS-halo convolution kernel, 1 whenever the geometry fits
 #define UV_OPT_GEMM_GM 1       // 0 automatic (default), > 0: tile-walk group height of the persistent GEMM
 #define UV_OPT_ATTN_CUT 2      // 0 automatic (default); v > 0: flash_attn_fwd12_kernel cuts every head with n8 = v - 1 eight-unit blocks (A/B tools)
-#define UV_OPT_COUNT 3
+#define UV_OPT_ATTN_WIN_FORM 3 // 0 automatic (default: plan_attn_win's span rule); 1 / 2: uv_flash_attn_win_bf16 on its 12-wave / 4-wave form (A/B tools)
+#define UV_OPT_COUNT 4
 int uv_option(int key);
 
 // error plumbing shared by the extern "C" entry points

@@ -57,6 +57,7 @@ class CrossAttentionConfig:
     proj_precision: str = "bf16"  # "mxfp8": the DiT's self-attention q / k / v / o and cross-attention q / o projections on MXFP8 operands (WanModel.set_proj_precision), an opt-in experimental mode
     vae_precision: Optional[str] = None   # "f16": the VAE's opt-in narrow arithmetic (WanVAE_.prepare; one fp16 pass where f16x3 takes three); None keeps the VAE's own mode ("f16x3")
     attn_precision: str = "bf16"  # "mxfp8_qk" / "mxfp8_qk_pv": the DiT's self-attention q / k (and P.V) as MXFP8 (WanModel.set_attn_precision), opt-in experimental modes
+    attn_window: Optional[Tuple[int, int]] = None  # (left, right) tokens as flash-attn's window_size: sliding-window / causal DiT self-attention (WanModel.set_attn_window), opt-in, changes the model's function; None = what the checkpoint says (global)
     guidance_strength: float = 1.0
     bagel_cross_attn_layers: List[int] = None
     freeze_bagel: bool = True
@@ -386,6 +387,9 @@ class CrossAttentionFusionPipeline:
         attn_precision = getattr(config, "attn_precision", "bf16")
         if attn_precision != "bf16" and hasattr(self.dit_model, "set_attn_precision") and attn_precision != self.dit_model.attn_precision:
             self.dit_model.set_attn_precision(attn_precision)
+        attn_window = getattr(config, "attn_window", None)
+        if attn_window is not None and hasattr(self.dit_model, "set_attn_window") and tuple(attn_window) != tuple(self.dit_model.window_size):
+            self.dit_model.set_attn_window(attn_window)
         proj_precision = getattr(config, "proj_precision", "bf16")
         if proj_precision != "bf16" and hasattr(self.dit_model, "set_proj_precision") and proj_precision != self.dit_model.proj_precision:
             self.dit_model.set_proj_precision(proj_precision)
@@ -420,7 +424,7 @@ class CrossAttentionFusionPipeline:
                            use_sp=False, ffn_precision=getattr(self.config, "ffn_precision", "bf16"),
                            attn_precision=getattr(self.config, "attn_precision", "bf16"),
                            proj_precision=getattr(self.config, "proj_precision", "bf16"),
-                           vae_precision=getattr(self.config, "vae_precision", None))
+                           vae_precision=getattr(self.config, "vae_precision", None), attn_window=getattr(self.config, "attn_window", None))
         except Exception as e:
             raise RuntimeError(f"Wan2.2 initialization failed: {e}") from e
 

@@ -7,13 +7,19 @@ model.py:175 cross-attention, distributed/ulysses.py:37) can import this module 
     q [B, Lq, N, C], k [B, Lk, N, C], v [B, Lk, N, C] in any float dtype -> [B, Lq, N, C] in q's dtype;
     operands that are not fp16/bf16 are cast to `dtype` first (:59-83); sample b attends keys [0, k_lens[b]).
 
-The core is `uv_flash_attn_bf16` / `uv_flash_attn_f16` (csrc/attention.hip); this file only arranges memory for it: casts
+The core is `uv_flash_attn_bf16` / `uv_flash_attn_f16` (csrc/attention.hip) and, under `causal` / `window_size`,
+`uv_flash_attn_win_bf16` (csrc/attention_win.hip); this file only arranges memory for it: casts
 (`uv_cast_f32_to16`), the V^T operand (`uv_transpose_16`, zero-filled to the 64-key tile), the widening of the result
 (`uv_cast_16_to_f32`). The fused DiT path (`univid_amd/wan/model.py`) does not come through here - there V^T is written by
 the V projection's GEMM epilogue - so this is the path for code that calls the operator directly.
 
+`causal` / `window_size=(left, right)` (attention.py:113-127, flash-attn's meaning: query i attends keys max(0, i - left) ..
+min(Lk - 1, i + right), -1 = unbounded, causal forces right = 0) are built for SELF-attention as `WanModel.forward` runs it:
+Lq == Lk, every sample attending all Lk keys (`k_lens` None or all Lk), head size 128, bf16 operands after the cast. Bottom-right
+alignment for Lq != Lk, ragged `k_lens`, fp16 tensors and head size 64 under a window raise NotImplementedError naming the limit.
+
 What the reference function accepts but UniVid never uses is rejected loudly instead of being computed wrongly:
-causal / sliding-window masks, dropout, `q_scale`, grouped K/V heads, head sizes other than 64 / 128, and `q_lens` that
+dropout, `q_scale`, grouped K/V heads, head sizes other than 64 / 128, and `q_lens` that
 differ from Lq (the reference itself cannot return those: its `.unflatten(0, (b, lq))` needs every q_len == Lq).
 There is no eager fallback: without the HIP extension or a gfx950 device the call raises.
 """
@@ -55,9 +61,15 @@ def flash_attention(q, k, v, q_lens=None, k_lens=None, dropout_p=0., softmax_sca
     assert dtype in _HALF
     if q.device.type != "cuda":
         raise _lib.UnividHipError(f"flash_attention: tensors must live on the GPU (got {q.device}); univid_amd has no CPU path")
-    if causal or tuple(window_size) != (-1, -1):
-        raise NotImplementedError("flash_attention: causal / sliding-window attention is not built (UniVid's DiT uses global "
-                                  "attention, window_size=(-1, -1): configs/wan_ti2v_5B.py)")
+    try:
+        window = tuple(int(w) for w in window_size)
+    except (TypeError, ValueError):
+        window = ()
+    if len(window) != 2 or min(window) < -1:
+        raise ValueError(f"flash_attention: window_size {window_size!r} must be (left, right), each >= 0 or -1 for unbounded")
+    if causal:
+        window = (window[0], 0)      # flash-attn: causal forces right = 0, whatever window_size[1] says
+    windowed = window != (-1, -1)
     if dropout_p:
         raise NotImplementedError("flash_attention: dropout_p > 0 is a training option; the inference kernels have no dropout")
     if q_scale is not None:
@@ -71,6 +83,11 @@ def flash_attention(q, k, v, q_lens=None, k_lens=None, dropout_p=0., softmax_sca
                                   f"C2 != C1 are not built); got k {tuple(k.shape)}, v {tuple(v.shape)}")
     if c not in (64, 128):
         raise NotImplementedError(f"flash_attention: head size {c} (the kernels are built for 64 and 128)")
+    if windowed and c != 128:
+        raise NotImplementedError(f"flash_attention: causal / window_size with head size {c} is not built (the windowed kernels are head size 128)")
+    if windowed and lq != lk:
+        raise NotImplementedError(f"flash_attention: causal / window_size with Lq != Lk ({lq} vs {lk}: flash-attn's bottom-right alignment) "
+                                  f"is not built, self-attention only")
     out_dtype = q.dtype
     if any(ql != lq for ql in _lens(q_lens, b, lq, "q_lens")):
         raise ValueError("flash_attention: q_lens other than Lq cannot be returned as [B, Lq, N, C] (attention.py:107,127)")
@@ -79,6 +96,11 @@ def flash_attention(q, k, v, q_lens=None, k_lens=None, dropout_p=0., softmax_sca
     qh, kh, vh = _half(q, dtype), _half(k, dtype), _half(v, dtype)
     if not (qh.dtype == kh.dtype == vh.dtype):          # attention.py:82-83 casts q and k to v's dtype
         raise NotImplementedError("flash_attention: q, k, v of different half dtypes; pass one dtype")
+    if windowed and any(kl != lk for kl in kls):
+        raise NotImplementedError(f"flash_attention: causal / window_size with ragged k_lens {kls} (Lk = {lk}) is not built: strip the padding "
+                                  f"first, as WanModel.forward does")
+    if windowed and vh.dtype != torch.bfloat16:
+        raise NotImplementedError("flash_attention: causal / window_size with fp16 tensors is not built (the windowed kernels are bf16)")
     C = n * c
     dev = q.device
     scale = float(softmax_scale) if softmax_scale is not None else c ** -0.5
@@ -94,13 +116,19 @@ def flash_attention(q, k, v, q_lens=None, k_lens=None, dropout_p=0., softmax_sca
         vt = torch.empty(C, _lib.vt_cols(b, lk), dtype=vh.dtype, device=dev)
         for s in range(b):      # later samples overwrite the previous sample's zero padding, the last one keeps it
             vt_of(v2[s * lk:(s + 1) * lk], lk, vt, s * lk)
-        _lib.flash_attn(q2, k2, vt, out.view(b * lq, C), lq, lk, n, c, scale, batch=b)
+        if windowed:
+            _lib.flash_attn_win(q2, k2, vt, out.view(b * lq, C), lq, n, c, scale, window, batch=b)
+        else:
+            _lib.flash_attn(q2, k2, vt, out.view(b * lq, C), lq, lk, n, c, scale, batch=b)
     else:
         for s in range(b):      # ragged key lengths: one launch per sample on its first k_lens[s] keys
             L = kls[s]
             vt = torch.empty(C, _lib.vt_cols(1, L), dtype=vh.dtype, device=dev)
             vt_of(v2[s * lk:s * lk + L], L, vt, 0)
-            _lib.flash_attn(q2[s * lq:(s + 1) * lq], k2[s * lk:s * lk + L], vt, out[s], lq, L, n, c, scale)
+            if windowed:        # (every k_len == Lk here: Lk % 8 != 0 at batch > 1)
+                _lib.flash_attn_win(q2[s * lq:(s + 1) * lq], k2[s * lk:s * lk + L], vt, out[s], lq, n, c, scale, window)
+            else:
+                _lib.flash_attn(q2[s * lq:(s + 1) * lq], k2[s * lk:s * lk + L], vt, out[s], lq, L, n, c, scale)
     out = out.view(b, lq, n, c)
     if out_dtype == out.dtype:
         return out

@@ -96,6 +96,28 @@ def _check_attn_precision(mode, head_dim):
                          f"block-scaled matrix instruction); this model has head_dim {head_dim}")
 
 
+def _check_attn_window(window, head_dim=128, attn_precision="bf16"):
+    """set_attn_window's guards, on one self-attention's geometry: raises before any state changes. Returns the window as the kernels take
+    it - (left, right), each >= 0 or -1 = unbounded (flash-attn's window_size) - or None for global attention (None or (-1, -1))."""
+    if window is None:
+        return None
+    try:
+        ok = len(window) == 2 and all(int(w) == w and not isinstance(w, bool) for w in window)
+    except (TypeError, ValueError):
+        ok = False
+    if not ok or min(int(w) for w in window) < -1:
+        raise ValueError(f"window_size {window!r}: (left, right), two integers, each >= 0 or -1 for unbounded")
+    window = (int(window[0]), int(window[1]))
+    if window == (-1, -1):
+        return None
+    if head_dim != 128:
+        raise NotImplementedError(f"window_size {window}: the windowed attention kernels are built for head_dim 128 (this model has {head_dim})")
+    if attn_precision != "bf16":
+        raise NotImplementedError(f"window_size {window} with attn_precision {attn_precision!r}: the windowed attention kernels are bf16 only "
+                                  f"- set_attn_precision('bf16') or set_attn_window(None) first")
+    return window
+
+
 def _check_ffn_precision(mode, dim, ffn_dim, ffn):
     """Everything that can refuse a mode, before any state changes."""
     if mode not in FFN_PRECISIONS:
@@ -254,9 +276,12 @@ class WanSelfAttention(nn.Module):
         assert dim % num_heads == 0
         super().__init__()
         self.dim, self.num_heads, self.head_dim = dim, num_heads, dim // num_heads
-        self.window_size, self.qk_norm, self.eps = window_size, qk_norm, eps
-        if tuple(window_size) != (-1, -1) or not qk_norm:
-            raise NotImplementedError("only the TI2V-5B setting (global attention, qk_norm) is built")
+        self.qk_norm, self.eps = qk_norm, eps
+        if not qk_norm:
+            raise NotImplementedError("only the TI2V-5B setting (qk_norm) is built")
+        # (left, right) of flash-attn's window_size, or None = global attention (WanModel.set_attn_window): instance state
+        self.attn_window = _check_attn_window(window_size, self.head_dim)
+        self.window_size = self.attn_window or (-1, -1)
         self.q = nn.Linear(dim, dim)
         self.k = nn.Linear(dim, dim)
         self.v = nn.Linear(dim, dim)
@@ -318,6 +343,14 @@ class WanSelfAttention(nn.Module):
         vt = _vt_scratch("vt", C, batch, L, dev)
         ql, kl = self._qkv(h, M, L, s0, vt)
         att = _act_buf(M, C, (self._slots["o"],), dev)
+        if self.attn_window is not None:
+            # the window counts tokens of the UNPADDED sequence (set_attn_window keeps attn_precision at "bf16")
+            if Lk != L:
+                raise NotImplementedError(f"window_size {self.attn_window} with padded samples (seq_len {Lk} < {L}) is not built: "
+                                          f"call WanModel.forward, which strips the padding")
+            _lib.rmsnorm_rope_qk(ql, kl, self.norm_q.weight, self.norm_k.weight, M, L, C, D, self.eps, freqs, grid)
+            _lib.flash_attn_win(ql, kl, vt, att, L, H, D, 1.0 / math.sqrt(D), self.attn_window, batch=batch)
+            return _slotted(att, C, self._slots["o"], M, L, s0)
         if self.attn_precision != "bf16":
             # q and k leave the norm + RoPE pass as MXFP8 codes + scales (fresh buffers: no in-place form), S = K Q^T on the block-scaled
             # matrix instruction; "mxfp8_qk": V^T, P.V and the output stay bf16
@@ -365,6 +398,9 @@ class WanSelfAttention(nn.Module):
         """Ulysses form (distributed/sequence_parallel.py:147-176, ulysses.py:9-47): projections, RMSNorm and RoPE on the
         rank's n tokens of each sample; q/k/V^T exchanged to [all tokens, heads/p]; attention over the whole sequence for
         the rank's heads; output exchanged back; o-projection + gated residual on the rank's tokens."""
+        if self.attn_window is not None:
+            raise NotImplementedError(f"window_size {self.attn_window} is not built for the sequence-parallel forward (the Ulysses attention "
+                                      f"runs the dense kernel): set_attn_window(None) or run without sequence parallelism")
         if self.attn_precision != "bf16":
             raise NotImplementedError(f"attn_precision {self.attn_precision!r} is not built for the sequence-parallel forward (the Ulysses "
                                       f"exchange carries bf16 q / k): set_attn_precision('bf16') or run without sequence parallelism")
@@ -405,10 +441,13 @@ class WanSelfAttention(nn.Module):
     def forward(self, x, seq_lens, grid_sizes, freqs):
         """Reference signature (model.py:126-155): x [B, L, C] -> [B, L, C] bf16. Keys >= seq_lens[b] are masked,
         which here means: only the first seq_lens[b] tokens are attended (the rest of L is padding)."""
+        L = x.size(1)
+        if self.attn_window is not None and any(int(s) < L for s in seq_lens):
+            raise NotImplementedError(f"window_size {self.attn_window} with padded samples (seq_lens {[int(s) for s in seq_lens]} < {L}) is "
+                                      f"not built: call WanModel.forward, which strips the padding")
         _ensure_prepared(self)
         outs = []
         fr = _freqs_device(freqs, x.device)
-        L = x.size(1)
         for b in range(x.size(0)):      # (sample b of the batch takes its own row of per-sample adapter weights)
             xb = x[b].to(BF16).contiguous()
             if self.proj_precision == "mxfp8":
@@ -525,9 +564,10 @@ class WanAttentionBlock(nn.Module):
     def __init__(self, dim, ffn_dim, num_heads, window_size=(-1, -1), qk_norm=True, cross_attn_norm=False, eps=1e-6):
         super().__init__()
         self.dim, self.ffn_dim, self.num_heads, self.eps = dim, ffn_dim, num_heads, eps
-        self.window_size, self.qk_norm, self.cross_attn_norm = window_size, qk_norm, cross_attn_norm
+        self.qk_norm, self.cross_attn_norm = qk_norm, cross_attn_norm
         self.norm1 = WanLayerNorm(dim, eps)
         self.self_attn = WanSelfAttention(dim, num_heads, window_size, qk_norm, eps)
+        self.window_size = self.self_attn.window_size
         self.norm3 = WanLayerNorm(dim, eps, elementwise_affine=True) if cross_attn_norm else nn.Identity()
         self.cross_attn = WanCrossAttention(dim, num_heads, (-1, -1), qk_norm, eps)
         self.norm2 = WanLayerNorm(dim, eps)
@@ -554,7 +594,15 @@ class WanAttentionBlock(nn.Module):
         """"bf16" (default), "mxfp8_qk": this block's self-attention with MXFP8 q / k, or "mxfp8_qk_pv": with an MXFP8 P.V as well
         (WanModel.set_attn_precision states the modes). No prepared weight depends on it."""
         _check_attn_precision(mode, self.self_attn.head_dim)
+        _check_attn_window(self.self_attn.attn_window, self.self_attn.head_dim, mode)
         self.self_attn.attn_precision = mode
+
+    def set_attn_window(self, window_size):
+        """(left, right) as flash-attn's window_size, or None / (-1, -1) for global attention: this block's self-attention
+        (WanModel.set_attn_window states the mode). No prepared weight depends on it."""
+        w = _check_attn_window(window_size, self.self_attn.head_dim, self.self_attn.attn_precision)
+        self.self_attn.attn_window = w
+        self.self_attn.window_size = self.window_size = w or (-1, -1)
 
     def set_proj_precision(self, mode):
         """"bf16" (default: the reference's arithmetic) or "mxfp8": this block's self-attention q / k / v / o and cross-attention q / o on
@@ -844,6 +892,8 @@ class WanModel(nn.Module):
         self.text_len, self.in_dim, self.dim, self.ffn_dim = text_len, in_dim, dim, ffn_dim
         self.freq_dim, self.text_dim, self.out_dim = freq_dim, text_dim, out_dim
         self.num_heads, self.num_layers = num_heads, num_layers
+        self.attn_window = _check_attn_window(window_size, dim // num_heads)      # None = global attention; set_attn_window
+        window_size = self.attn_window or (-1, -1)
         self.window_size, self.qk_norm, self.cross_attn_norm, self.eps = window_size, qk_norm, cross_attn_norm, eps
         self.config = dict(model_type=model_type, patch_size=self.patch_size, text_len=text_len, in_dim=in_dim, dim=dim,
                            ffn_dim=ffn_dim, freq_dim=freq_dim, text_dim=text_dim, out_dim=out_dim, num_heads=num_heads,
@@ -962,11 +1012,32 @@ class WanModel(nn.Module):
         Needs head_dim 128 (ValueError otherwise, before any state changes). Independent of set_ffn_precision; the two combine.
         Calls invalidate(): the prepared-weights generation moves on, so captured HIP graphs (WanTI2V) re-capture."""
         _check_attn_precision(mode, self.blocks[0].self_attn.head_dim if len(self.blocks) else 128)
+        _check_attn_window(self.attn_window, attn_precision=mode)
         for b in self.blocks:
             _check_attn_precision(mode, b.self_attn.head_dim)
+            _check_attn_window(b.self_attn.attn_window, b.self_attn.head_dim, mode)
         self.attn_precision = mode
         for b in self.blocks:
             b.set_attn_precision(mode)
+        self.invalidate()
+
+    def set_attn_window(self, window_size):
+        """Sliding-window / causal SELF-attention in every block: window_size = (left, right) as flash-attn's (the reference's
+        WanModel(window_size=...), a key of every checkpoint's config.json) - token i of a sample attends tokens max(0, i - left) ..
+        min(L - 1, i + right) of the flattened (frame, row, column) sequence, -1 = unbounded on that side, (-1, 0) = causal; None or
+        (-1, -1) = global attention (default, UniVid's configuration). Opt-in: it CHANGES the model's function (exactly - the same softmax
+        over fewer keys, uv_flash_attn_win_bf16), it is not an approximation of global attention (README). Cross-attention is untouched.
+        Needs head_dim 128 and attn_precision "bf16" (NotImplementedError otherwise; set_attn_precision refuses an MXFP8 mode while a
+        window is set); the sequence-parallel forward and the reference-signature WanSelfAttention.forward on padded samples raise
+        NotImplementedError while a window is set. Independent of ffn_precision / proj_precision and of un-merged LoRA. Every guard runs
+        before any state changes. Calls invalidate(): the prepared-weights generation moves on, so captured HIP graphs (WanTI2V) re-capture."""
+        w = _check_attn_window(window_size, self.dim // self.num_heads, self.attn_precision)
+        for b in self.blocks:
+            _check_attn_window(window_size, b.self_attn.head_dim, b.self_attn.attn_precision)
+        self.attn_window = w
+        self.window_size = self.config["window_size"] = w or (-1, -1)
+        for b in self.blocks:
+            b.set_attn_window(w)
         self.invalidate()
 
     def set_proj_precision(self, mode):
