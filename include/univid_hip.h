@@ -242,6 +242,25 @@ int uv_flash_attn_win_bf16(const void* q, long ldq, const void* k, long ldk, con
 int uv_flash_attn_win_plan(int batch, int L, int H, int head_dim, int win_left, int win_right, char* kernel, int len, int* q_blocks, int* n12,
                            int* grid);
 
+/* ---- DiT: block-sparse self-attention from a key-tile mask (opt-in; WanModel.set_attn_block_mask) -----------------------------------
+ * uv_flash_attn_bf16 for Lq == Lk == L under a block mask of 128-query x 64-key tiles (no counterpart in the reference, whose attention.py
+ * knows global, causal and sliding-window attention): with nqb = ceil(L / 128), nkb = ceil(L / 64), query i of head h attends key j iff
+ * mask[h][i / 128][j / 64] and j < L. The mask arrives as a schedule prepared once per mask: tile_idx int32 [mask_heads, nqb, nkb] holds
+ * each (mask head, query block)'s visible key tiles in ascending order (the entries behind the count are never used), tile_cnt int32
+ * [mask_heads, nqb] how many; mask_heads = 1 (one mask for all heads) or H; both on the device, shared by the samples of a stacked launch.
+ * Every count should be >= 1 (univid_amd._lib.prepare_block_mask refuses a mask with an empty row); a block whose count is <= 0 gets zero
+ * rows. The kernel clamps what it reads - the count into [0, nkb], an entry into [0, nkb - 1], an entry that is not its list's last into
+ * the full tiles - so no list content reads outside k / vt; an unsorted or repeating list is computed as listed. Exact - the same softmax
+ * over fewer keys: unlisted tiles are neither staged nor visited, the all-ones mask reproduces uv_flash_attn_bf16 bit for bit, and a
+ * query's bits depend on its 32-query unit and on its block's list only. q / k / vt / out / ld* / batch / H / softmax_scale:
+ * uv_flash_attn_win_bf16's meaning and checks. head_dim 128 only. Anything else is rejected and nothing is written. */
+int uv_flash_attn_bs_bf16(const void* q, long ldq, const void* k, long ldk, const void* vt, long ldvt, void* out, long ldo, int batch, int L,
+                          int H, int head_dim, float softmax_scale, const int* tile_idx, const int* tile_cnt, int mask_heads, void* stream);
+
+/* The launch plan of uv_flash_attn_bs_bf16: flash_attn_bs4_kernel on blocks of 128 queries, *q_blocks = ceil(L / 128), *grid = *q_blocks * H *
+ * batch - whatever the mask holds. Host-only. */
+int uv_flash_attn_bs_plan(int batch, int L, int H, int head_dim, char* kernel, int len, int* q_blocks, int* grid);
+
 /* ---- DiT: self-attention with MXFP8 q / k (opt-in mode; WanModel.set_attn_precision("mxfp8_qk")) ------------------------------
  * uv_flash_attn_bf16 with q and k in the MXFP8 format stated above (e4m3fn codes, one e8m0 byte per 32 consecutive elements of a row, e =
  * clamp(exp(amax) - 8, 0, 254), clamp to +-448 then RNE, never a NaN code): replaces attention.py:24-130 as called at model.py:145-150 with

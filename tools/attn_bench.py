@@ -2,7 +2,11 @@
     --qk mxfp8          bf16 against the MXFP8 q / k and q / k + P.V modes, launches and producers alternating in one process
     --window L,R[:L,R...]   the dense launch against uv_flash_attn_win_bf16 under each window (-1 = unbounded; -1,0 = causal), and against (-1,-1)
                         through the same entry - which visits every tile: what the classification costs -, all alternating in one process;
-                        --forms: every window also on the 12-wave and on the 4-wave form (OPT_ATTN_WIN_FORM), whatever the plan's rule says"""
+                        --forms: every window also on the 12-wave and on the 4-wave form (OPT_ATTN_WIN_FORM), whatever the plan's rule says
+    --block-mask F,H,W  (F H W == L: the patch grid) the dense launch against uv_flash_attn_bs_bf16 under the all-ones mask (what a listed tile
+                        costs), video_block_mask of +-2 frames - beside window_size = 2 frames each way through uv_flash_attn_win_bf16 -, of
+                        +-1 frame x +-8 rows (no window expresses it) and a per-head mix (spatial heads: the own frame; temporal heads: every
+                        frame, +-2 rows x +-4 columns), all alternating in one process"""
 import math, os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from univid_amd import _lib
@@ -137,3 +141,55 @@ if "--window" in sys.argv:
         print(f"window {w} form {('auto', '12-wave', '4-wave')[f]} B{B} L{L}: median {med[key]:.1f} us (min {min(t):.1f} max {max(t):.1f}); {med[key] / med['dense']:.4f} x dense, "
               f"dense / window = {med['dense'] / med[key]:.3f}; {tiles} wave tiles ({tiles / dense_tiles:.4f} of dense), {med[key] * 1e3 / tiles:.3f} ns per tile "
               f"({med[key] / tiles / (med['dense'] / dense_tiles):.3f} x the dense kernel's); plan={plan}")
+
+
+if "--block-mask" in sys.argv:
+    # Dense, windowed and block-sparse launches on the same random operands, alternating round by round in ONE process, the first round
+    # dropped; medians and the spread (min .. max) of the ROUNDS rounds. Per launch the 128-query x 64-key tiles its workgroups visit (the
+    # lists' lengths; dense and windowed: host arithmetic), the density and the time per visited tile next to the dense kernel's.
+    import statistics
+    from univid_amd.wan.attention import video_block_mask
+    assert L == Lk, "block masks are built for self-attention (Lq == Lk)"
+    rounds = int(os.environ.get("ROUNDS", 7))
+    grid = tuple(int(x) for x in sys.argv[sys.argv.index("--block-mask") + 1].split(","))
+    assert len(grid) == 3 and grid[0] * grid[1] * grid[2] == L, f"--block-mask F,H,W must multiply to L = {L}"
+    frame = grid[1] * grid[2]
+    nqb, nkb = (L + 127) // 128, (L + 63) // 64
+    spatial, temporal = video_block_mask(grid, frames=(0, 0)), video_block_mask(grid, frames=(-1, -1), rows=2, cols=4)
+    masks = {"ones": torch.ones(nqb, nkb, dtype=torch.bool),
+             "frames+-2": video_block_mask(grid, frames=(2, 2)),
+             "frames+-1 x rows+-8": video_block_mask(grid, frames=(1, 1), rows=8),
+             "per-head mix (spatial | temporal)": torch.stack([spatial if hd % 2 == 0 else temporal for hd in range(H)])}
+    bms = {name: _lib.prepare_block_mask(m, L, dev) for name, m in masks.items()}
+    win = (2 * frame, 2 * frame)
+    outs = {name: torch.empty_like(out) for name in list(masks) + ["window"]}
+    work = {"dense": lambda: _lib.flash_attn(q, k, vt, out, L, L, H, D, 1 / math.sqrt(D), batch=B),
+            "window": lambda: _lib.flash_attn_win(q, k, vt, outs["window"], L, H, D, 1 / math.sqrt(D), win, batch=B)}
+    for name in masks:
+        work[name] = (lambda name=name: _lib.flash_attn_bs(q, k, vt, outs[name], L, H, D, 1 / math.sqrt(D), bms[name], batch=B))
+    times = {name: [] for name in work}
+    for rnd in range(rounds + 1):
+        for name, fn in work.items():
+            fn(); torch.cuda.synchronize()
+            s.record()
+            for _ in range(n):
+                fn()
+            e.record(); torch.cuda.synchronize()
+            if rnd:
+                times[name].append(s.elapsed_time(e) / n * 1e3)
+    med = {name: statistics.median(t) for name, t in times.items()}
+    dense_tiles = B * H * nqb * nkb
+    per_dense = med["dense"] * 1e3 / dense_tiles
+    print(f"dense B{B} L{L} grid {grid}: median {med['dense']:.1f} us (min {min(times['dense']):.1f} max {max(times['dense']):.1f}, {rounds} rounds of {n}); "
+          f"{dense_tiles} 128 x 64 tiles, {per_dense:.2f} ns per tile; kernel={_lib.attn_plan(L, L, D, B, H)['kernel']}")
+    assert torch.equal(outs["ones"], out), "the all-ones mask differs from the dense launch"
+    win_tiles = B * H * sum(min(L - 1, min(b * 128 + 127, L - 1) + win[1]) // 64 - max(0, b * 128 - win[0]) // 64 + 1 for b in range(nqb))
+    t = times["window"]
+    print(f"window {win} B{B} L{L}: median {med['window']:.1f} us (min {min(t):.1f} max {max(t):.1f}); dense / window = {med['dense'] / med['window']:.3f}; "
+          f"{win_tiles} tiles staged per 128 queries ({win_tiles / dense_tiles:.4f} of dense), {med['window'] * 1e3 / win_tiles:.2f} ns per tile "
+          f"({med['window'] * 1e3 / win_tiles / per_dense:.3f} x the dense kernel's); plan={_lib.attn_win_plan(L, D, B, H, win)}")
+    for name, bm in bms.items():
+        t, tiles = times[name], B * (H // bm.heads) * int(bm.tile_cnt.sum())
+        print(f"block mask {name} B{B} L{L}: median {med[name]:.1f} us (min {min(t):.1f} max {max(t):.1f}); dense / masked = {med['dense'] / med[name]:.3f}; "
+              f"density {bm.density:.4f}, {tiles} tiles visited, {med[name] * 1e3 / tiles:.2f} ns per tile ({med[name] * 1e3 / tiles / per_dense:.3f} x the dense "
+              f"kernel's); grid order: XCD-contiguous block ids (flash_attn_fwd3_kernel's); plan={_lib.attn_bs_plan(L, D, B, H)}")

@@ -11,6 +11,8 @@ f32-grade bf16x6 / f16x3 modes - at the bench size (49 frames of 704 x 1280) and
                        process; --also-with-mx repeats the comparison beside ffn_precision mxfp8 + attn_precision mxfp8_qk_pv in the same process
     --attn-window L,R   the DiT's self-attention under flash-attn's window_size = (L, R) tokens (WanModel.set_attn_window; -1 = unbounded)
     --window-ab ROUNDS   instead of the table: ms per denoise step with global attention and with --attn-window, alternating in one process
+    --attn-block-mask B,A,R,C   with --window-ab: a third side, the self-attention under video_block_mask(frames=(B, A), rows=R, cols=C) of the
+                         latent's patch grid (WanModel.set_attn_block_mask; -1 = unbounded); --attn-window may then be left out
     --attn-ab ROUNDS   instead of the table: ms per denoise step with the self-attention in bf16, mxfp8_qk and mxfp8_qk_pv, alternating in one process"""
 import os, sys, time, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -83,13 +85,22 @@ if "--window-ab" in sys.argv:
     # alternating round by round in THIS process (each switch re-captures: its warm-up generation is not timed), the first round dropped;
     # medians and the spread of the rounds. The precision options apply to both sides.
     import statistics
-    assert attn_window is not None, "--window-ab needs --attn-window L,R"
+    from univid_amd.wan.attention import video_block_mask
+    vm = tuple(int(v) for v in sys.argv[sys.argv.index("--attn-block-mask") + 1].split(",")) if "--attn-block-mask" in sys.argv else None
+    assert attn_window is not None or vm is not None, "--window-ab needs --attn-window L,R or --attn-block-mask B,A,R,C"
     rounds, F = int(sys.argv[sys.argv.index("--window-ab") + 1]), frames[0]
     pipe = WanTI2V(model=m, vae=Wan2_2_VAE(device=dev, seed=0, precision="f16x3"), device=dev)
-    ms = {None: [], attn_window: []}
+    ms = {None: []}
+    if attn_window is not None:
+        ms[attn_window] = []
+    if vm is not None:
+        ms[f"video_block_mask{vm}"] = []
+    spec = None if vm is None else (lambda Fg, Hg, Wg, nh: video_block_mask((Fg, Hg, Wg), frames=vm[:2], rows=vm[2], cols=vm[3]))
     for rnd in range(rounds + 1):
         for win in ms:
-            m.set_attn_window(win)
+            m.set_attn_block_mask(None)
+            m.set_attn_window(None if isinstance(win, str) else win)
+            m.set_attn_block_mask(spec if isinstance(win, str) else None)
             with torch.no_grad():
                 pipe.t2v("", size=(1280, 704), frame_num=F, sampling_steps=2, seed=7, prompt_embeds=pe, negative_prompt_embeds=ne, decode=False)
                 lat, t = clock(lambda: pipe.t2v("", size=(1280, 704), frame_num=F, sampling_steps=steps, seed=7, prompt_embeds=pe,
@@ -101,8 +112,11 @@ if "--window-ab" in sys.argv:
     for k, v in ms.items():
         print(f"{F} frames, ffn {ffn_precision}, attn {attn_precision}, window {k}: median {med[k]:.2f} ms/step (min {min(v):.2f} max {max(v):.2f}, {len(v)} rounds of "
               f"{steps} steps)", flush=True)
-    print(f"window / global = {med[attn_window] / med[None]:.4f}, gain {med[None] - med[attn_window]:.2f} ms/step (global spread "
-          f"{max(ms[None]) - min(ms[None]):.2f} ms)", flush=True)
+    for k in ms:
+        if k is not None:
+            print(f"{k} / global = {med[k] / med[None]:.4f}, gain {med[None] - med[k]:.2f} ms/step (global spread {max(ms[None]) - min(ms[None]):.2f} ms)"
+                  + ("" if spec is None or not isinstance(k, str) else f"; densities {[round(b.density, 4) for b in m.attn_block_mask.prepared().values()] if m.attn_block_mask else '-'}"),
+                  flush=True)
     sys.exit(0)
 if "--attn-ab" in sys.argv:
     # --attn-ab ROUNDS: the denoise loop alone (t2v, decode=False) at the first FRAMES entry with the self-attention in "bf16", "mxfp8_qk" and "mxfp8_qk_pv",

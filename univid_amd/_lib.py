@@ -49,6 +49,8 @@ SIGNATURES = {
     "uv_flash_attn_f16": [_P, _L, _P, _L, _P, _L, _P, _L, _I, _I, _I, _I, _I, _F, _P],
     "uv_flash_attn_win_bf16": [_P, _L, _P, _L, _P, _L, _P, _L, _I, _I, _I, _I, _F, _I, _I, _P],
     "uv_flash_attn_win_plan": [_I, _I, _I, _I, _I, _I, _c.c_char_p, _I, _c.POINTER(_I), _c.POINTER(_I), _c.POINTER(_I)],
+    "uv_flash_attn_bs_bf16": [_P, _L, _P, _L, _P, _L, _P, _L, _I, _I, _I, _I, _F, _P, _P, _I, _P],
+    "uv_flash_attn_bs_plan": [_I, _I, _I, _I, _c.c_char_p, _I, _c.POINTER(_I), _c.POINTER(_I)],
     "uv_flash_attn_mxqk": [_P, _L, _P, _L, _P, _L, _P, _L, _P, _L, _P, _L, _I, _I, _I, _I, _I, _F, _P],
     "uv_flash_attn_mxqk_plan": [_I, _I, _I, _I, _I, _c.c_char_p, _I, _c.POINTER(_I), _c.POINTER(_I), _c.POINTER(_I)],
     "uv_vt_mx_quant": [_P, _L, _P, _L, _P, _L, _I, _I, _I, _I, _P],
@@ -588,6 +590,107 @@ def attn_win_plan(L, D=128, batch=1, H=1, window=(-1, -1)):
                                   ctypes.byref(grid)) != 0:
         raise UnividHipError(lib.uv_last_error().decode())
     return dict(kernel=buf.value.decode(), q_blocks=qb.value, n12=n12.value, grid=grid.value)
+
+
+class PreparedBlockMask:
+    """A block mask as `flash_attn_bs` takes it: the key-tile schedule of one sequence length on one device. Immutable; built only by
+    `prepare_block_mask`. L: the sequence length; heads: 1 (one mask for all heads) or H; tile_idx int32 [heads, nqb, nkb] (each row's
+    visible 64-key tiles ascending, the rest of the row -1, never read) and tile_cnt int32 [heads, nqb] on `device`; mask: the expanded
+    bool mask [heads, nqb, nkb] on the CPU; density: the fraction of set tiles."""
+    __slots__ = ("L", "heads", "tile_idx", "tile_cnt", "mask", "density")
+
+    def __init__(self, L, heads, tile_idx, tile_cnt, mask, density, _token=None):
+        if _token is not _PBM_TOKEN:
+            raise TypeError("PreparedBlockMask is built by prepare_block_mask(mask, L, device)")
+        for name, v in (("L", L), ("heads", heads), ("tile_idx", tile_idx), ("tile_cnt", tile_cnt), ("mask", mask), ("density", density)):
+            object.__setattr__(self, name, v)
+
+    def __setattr__(self, name, value):
+        raise AttributeError("PreparedBlockMask is immutable: prepare a new mask")
+
+    def __delattr__(self, name):
+        raise AttributeError("PreparedBlockMask is immutable: prepare a new mask")
+
+    @property
+    def device(self):
+        return self.tile_idx.device
+
+    def __repr__(self):
+        return f"PreparedBlockMask(L={self.L}, heads={self.heads}, density={self.density:.4f}, device={self.tile_idx.device})"
+
+
+_PBM_TOKEN = object()
+BS_Q_BLOCK, BS_K_BLOCK = 128, 64      # the kernel's tile: 4 x UV_ATT_QW queries, UV_ATT_KV keys
+
+
+def prepare_block_mask(mask, L, device, q_block=BS_Q_BLOCK, k_block=BS_K_BLOCK):
+    """The schedule of a block mask for `flash_attn_bs` at sequence length L. mask: a bool tensor [ceil(L / q_block), ceil(L / k_block)]
+    (all heads) or [H, ...] (per head); query i of head h attends key j iff mask[h][i // q_block][j // k_block] and j < L. q_block any
+    multiple of 128, k_block any multiple of 64 (128 x 128: FlexAttention's default block): coarser masks are expanded exactly to the
+    kernel's 128 x 64 tiles. Every query block of every head needs at least one set tile (ValueError otherwise: no empty softmax rows
+    exist). The lists are built with CPU ops and uploaded: call it once per mask, outside any graph capture."""
+    if not isinstance(mask, torch.Tensor) or mask.dtype != torch.bool:
+        raise TypeError(f"prepare_block_mask: the mask must be a torch.bool tensor, got "
+                        f"{mask.dtype if isinstance(mask, torch.Tensor) else type(mask).__name__}")
+    L, q_block, k_block = int(L), int(q_block), int(k_block)
+    if L <= 0:
+        raise ValueError(f"prepare_block_mask: L = {L} must be positive")
+    if q_block <= 0 or q_block % BS_Q_BLOCK or k_block <= 0 or k_block % BS_K_BLOCK:
+        raise ValueError(f"prepare_block_mask: q_block {q_block} must be a multiple of {BS_Q_BLOCK} and k_block {k_block} a multiple of "
+                         f"{BS_K_BLOCK} (the kernel's tile is {BS_Q_BLOCK} queries x {BS_K_BLOCK} keys)")
+    if mask.dim() not in (2, 3):
+        raise ValueError(f"prepare_block_mask: the mask must be [nqb, nkb] or [H, nqb, nkb], got shape {tuple(mask.shape)}")
+    want = (-(-L // q_block), -(-L // k_block))
+    if tuple(mask.shape[-2:]) != want:
+        raise ValueError(f"prepare_block_mask: mask shape {tuple(mask.shape)} does not belong to L = {L}: {q_block} x {k_block} blocks "
+                         f"need [..., {want[0]}, {want[1]}]")
+    if mask.dim() == 3 and mask.shape[0] < 1:
+        raise ValueError("prepare_block_mask: a per-head mask needs at least one head")
+    m = mask.detach().to("cpu")
+    m = m[None] if m.dim() == 2 else m
+    nqb, nkb = -(-L // BS_Q_BLOCK), -(-L // BS_K_BLOCK)
+    m = m.repeat_interleave(q_block // BS_Q_BLOCK, dim=1)[:, :nqb].repeat_interleave(k_block // BS_K_BLOCK, dim=2)[:, :, :nkb].contiguous()
+    cnt = m.sum(dim=2, dtype=torch.int32)
+    if bool((cnt == 0).any()):
+        hh, qq = (int(v) for v in (cnt == 0).nonzero()[0])
+        raise ValueError(f"prepare_block_mask: query block {qq} of mask head {hh} (queries {qq * BS_Q_BLOCK}..) has no key tile: every "
+                         f"{BS_Q_BLOCK}-query block of every head must see at least one tile (an empty softmax row has no value)")
+    # each row's set tiles first, ascending (a stable sort of "unset" keeps the column order), the rest -1
+    order = torch.sort((~m).to(torch.uint8), dim=2, stable=True).indices.to(torch.int32)
+    idx = torch.where(torch.arange(nkb, dtype=torch.int32)[None, None, :] < cnt[:, :, None], order, torch.full_like(order, -1)).contiguous()
+    dev = torch.device(device)
+    return PreparedBlockMask(L, int(m.shape[0]), idx.to(dev), cnt.contiguous().to(dev), m, float(m.double().mean()), _token=_PBM_TOKEN)
+
+
+def flash_attn_bs(q, k, vt, out, L, H, D, scale, bm, batch=1):
+    """`flash_attn` for Lq == Lk == L under the block mask `bm` (a PreparedBlockMask: `prepare_block_mask`): query i of head h attends key j
+    iff bm.mask[h or 0][i // 128][j // 64] and j < L; the samples of a stacked launch share the mask. bf16, head_dim 128 only; the all-ones
+    mask equals `flash_attn` bit for bit."""
+    C = H * D
+    if not isinstance(bm, PreparedBlockMask):
+        raise UnividHipError(f"flash_attn_bs.bm: a PreparedBlockMask is required (prepare_block_mask), got {type(bm).__name__}")
+    if bm.L != L:
+        raise UnividHipError(f"flash_attn_bs.bm: the mask was prepared for L = {bm.L}, the launch has L = {L}")
+    if bm.heads not in (1, H):
+        raise UnividHipError(f"flash_attn_bs.bm: the mask has {bm.heads} heads, the launch {H} (1 = shared by all heads, or H)")
+    if bm.tile_idx.device != q.device:
+        raise UnividHipError(f"flash_attn_bs.bm: the mask lives on {bm.tile_idx.device}, the tensors on {q.device}")
+    nqb, nkb = -(-L // BS_Q_BLOCK), -(-L // BS_K_BLOCK)
+    _check("flash_attn_bs", (q, "q", BF16, C, batch * L), (k, "k", BF16, C, batch * L), (vt, "vt", BF16, vt_cols(batch, L), C),
+           (out, "out", BF16, C, batch * L), (bm.tile_idx, "bm.tile_idx", I32, bm.heads * nqb * nkb), (bm.tile_cnt, "bm.tile_cnt", I32, bm.heads * nqb))
+    call("uv_flash_attn_bs_bf16", ptr(q), q.stride(-2), ptr(k), k.stride(-2), ptr(vt), vt.stride(-2), ptr(out), out.stride(-2), batch, L, H, D,
+         float(scale), ptr(bm.tile_idx), ptr(bm.tile_cnt), bm.heads, stream_ptr(), flops=int(4 * batch * L * L * H * D * bm.density))
+    return out
+
+
+def attn_bs_plan(L, D=128, batch=1, H=1):
+    """Launch plan of `flash_attn_bs` for this geometry (the mask does not change it), as `attn_plan` reports `flash_attn`'s."""
+    buf = ctypes.create_string_buffer(96)
+    qb, grid = _I(0), _I(0)
+    lib = load()
+    if lib.uv_flash_attn_bs_plan(batch, L, H, D, buf, 96, ctypes.byref(qb), ctypes.byref(grid)) != 0:
+        raise UnividHipError(lib.uv_last_error().decode())
+    return dict(kernel=buf.value.decode(), q_blocks=qb.value, grid=grid.value)
 
 
 def flash_attn_mxqk(q_codes, q_scales, k_codes, k_scales, vt, out, Lq, Lk, H, D, scale, batch=1):

@@ -32,12 +32,20 @@ struct AttnWinArgs : AttnArgs {
     int left, right;
 };
 
+// attention_bs.hip: AttnArgs (Lq == Lk, q_rs / q_w unused) plus the key-tile schedule of a block mask: per (mask head, 128-query block) the
+// ascending list of visible 64-key tiles and its length. mask_heads = 1 (one mask for all heads) or H.
+struct AttnBsArgs : AttnArgs {
+    const int* tile_idx;   // [mask_heads, q_blocks, nkb]  the first tile_cnt entries of a row are read, nothing else
+    const int* tile_cnt;   // [mask_heads, q_blocks]
+    int mask_heads, nkb;   // nkb = ceil(L / 64)
+};
+
 enum AttnKernel { ATT_FWD12 = 0, ATT_FWD3 = 1, ATT_FWD_D128 = 2, ATT_FWD_D64 = 3, ATT_MXQK12 = 4, ATT_MXQK4 = 5, ATT_MXPV12 = 6, ATT_MXPV4 = 7,
-                  ATT_WIN12 = 8, ATT_WIN4 = 9 };
+                  ATT_WIN12 = 8, ATT_WIN4 = 9, ATT_BS4 = 10 };
 static const char* const kAttnKernelName[] = {"flash_attn_fwd12_kernel", "flash_attn_fwd3_kernel", "flash_attn_fwd_kernel<128>",
                                               "flash_attn_fwd_kernel<64>", "flash_attn_mxqk12_kernel", "flash_attn_mxqk4_kernel",
                                               "flash_attn_mxpv12_kernel", "flash_attn_mxpv4_kernel",
-                                              "flash_attn_win12_kernel", "flash_attn_win4_kernel"};
+                                              "flash_attn_win12_kernel", "flash_attn_win4_kernel", "flash_attn_bs4_kernel"};
 struct AttnPlan {
     int kernel;            // AttnKernel
     int q_blocks, n12;     // query blocks per (sample, head); of them the 12-unit ones (flash_attn_fwd12_kernel only, else 0)
@@ -135,6 +143,14 @@ static inline AttnPlan plan_attn_win(int batch, int L, int H, int left, int righ
     AttnPlan plan = plan_attn(batch, L, (int)span, H, 128, 8, 8, false, ncus, force_cut);
     plan.kernel = plan.kernel == ATT_FWD12 ? ATT_WIN12 : ATT_WIN4;
     return plan;
+}
+
+// The block-sparse kernel (attention_bs.hip; self-attention, Lq == Lk == L, head_dim 128, bf16): one 4-wave workgroup per (sample, head,
+// 128-query block), whatever the mask holds - the key count a workgroup streams is its list's, not the problem's. Grid ids map to blocks in
+// flash_attn_fwd3_kernel's XCD-contiguous order.
+static inline AttnPlan plan_attn_bs(int batch, int L, int H) {
+    const int qb = (L + 4 * UV_ATT_QW - 1) / (4 * UV_ATT_QW);
+    return AttnPlan{ATT_BS4, qb, 0, qb * H * batch, 256};
 }
 
 // ---- device code the kernels share

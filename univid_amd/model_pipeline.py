@@ -24,7 +24,7 @@ import os
 import time
 from dataclasses import dataclass, field
 from pathlib import Path
-from typing import Callable, List, Optional, Tuple
+from typing import Any, Callable, List, Optional, Tuple
 
 import torch
 
@@ -58,6 +58,7 @@ class CrossAttentionConfig:
     vae_precision: Optional[str] = None   # "f16": the VAE's opt-in narrow arithmetic (WanVAE_.prepare; one fp16 pass where f16x3 takes three); None keeps the VAE's own mode ("f16x3")
     attn_precision: str = "bf16"  # "mxfp8_qk" / "mxfp8_qk_pv": the DiT's self-attention q / k (and P.V) as MXFP8 (WanModel.set_attn_precision), opt-in experimental modes
     attn_window: Optional[Tuple[int, int]] = None  # (left, right) tokens as flash-attn's window_size: sliding-window / causal DiT self-attention (WanModel.set_attn_window), opt-in, changes the model's function; None = what the checkpoint says (global)
+    attn_block_mask: Any = None  # a bool block mask / PreparedBlockMask / callable f(F, H, W, num_heads): block-sparse DiT self-attention (WanModel.set_attn_block_mask), opt-in, changes the model's function; None = global
     guidance_strength: float = 1.0
     bagel_cross_attn_layers: List[int] = None
     freeze_bagel: bool = True
@@ -390,6 +391,9 @@ class CrossAttentionFusionPipeline:
         attn_window = getattr(config, "attn_window", None)
         if attn_window is not None and hasattr(self.dit_model, "set_attn_window") and tuple(attn_window) != tuple(self.dit_model.window_size):
             self.dit_model.set_attn_window(attn_window)
+        attn_block_mask = getattr(config, "attn_block_mask", None)
+        if attn_block_mask is not None and hasattr(self.dit_model, "set_attn_block_mask"):
+            self.dit_model.set_attn_block_mask(attn_block_mask)
         proj_precision = getattr(config, "proj_precision", "bf16")
         if proj_precision != "bf16" and hasattr(self.dit_model, "set_proj_precision") and proj_precision != self.dit_model.proj_precision:
             self.dit_model.set_proj_precision(proj_precision)
@@ -424,7 +428,8 @@ class CrossAttentionFusionPipeline:
                            use_sp=False, ffn_precision=getattr(self.config, "ffn_precision", "bf16"),
                            attn_precision=getattr(self.config, "attn_precision", "bf16"),
                            proj_precision=getattr(self.config, "proj_precision", "bf16"),
-                           vae_precision=getattr(self.config, "vae_precision", None), attn_window=getattr(self.config, "attn_window", None))
+                           vae_precision=getattr(self.config, "vae_precision", None), attn_window=getattr(self.config, "attn_window", None),
+                           attn_block_mask=getattr(self.config, "attn_block_mask", None))
         except Exception as e:
             raise RuntimeError(f"Wan2.2 initialization failed: {e}") from e
 

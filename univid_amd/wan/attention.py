@@ -18,6 +18,12 @@ min(Lk - 1, i + right), -1 = unbounded, causal forces right = 0) are built for S
 Lq == Lk, every sample attending all Lk keys (`k_lens` None or all Lk), head size 128, bf16 operands after the cast. Bottom-right
 alignment for Lq != Lk, ragged `k_lens`, fp16 tensors and head size 64 under a window raise NotImplementedError naming the limit.
 
+`block_mask=` (a trailing keyword of this port; the reference signature is unchanged without it) runs block-sparse SELF-attention
+(`uv_flash_attn_bs_bf16`, csrc/attention_bs.hip): a `_lib.PreparedBlockMask` or a bool tensor [ceil(L / 128), ceil(L / 64)] / [N, ...]
+(prepared per call), query i of head h attending key j iff mask[h][i // 128][j // 64]. The window's restrictions apply, each refused with
+a message naming the limit: Lq == Lk, full `k_lens`, head size 128, bf16, and not beside `causal` / `window_size`. `video_block_mask`
+builds such a mask from a 3-D (frame, row, column) neighbourhood.
+
 What the reference function accepts but UniVid never uses is rejected loudly instead of being computed wrongly:
 dropout, `q_scale`, grouped K/V heads, head sizes other than 64 / 128, and `q_lens` that
 differ from Lq (the reference itself cannot return those: its `.unflatten(0, (b, lq))` needs every q_len == Lq).
@@ -27,7 +33,7 @@ import torch
 
 from .. import _lib
 
-__all__ = ["flash_attention", "attention"]
+__all__ = ["flash_attention", "attention", "video_block_mask"]
 
 _HALF = (torch.float16, torch.bfloat16)
 
@@ -55,9 +61,9 @@ def _lens(lens, b, full, name):
 
 
 def flash_attention(q, k, v, q_lens=None, k_lens=None, dropout_p=0., softmax_scale=None, q_scale=None, causal=False,
-                    window_size=(-1, -1), deterministic=False, dtype=torch.bfloat16, version=None):
+                    window_size=(-1, -1), deterministic=False, dtype=torch.bfloat16, version=None, *, block_mask=None):
     """Reference signature (attention.py:24-38). `deterministic` and `version` select nothing here: the kernel is always
-    deterministic (no atomics, fixed reduction order) and there is one implementation."""
+    deterministic (no atomics, fixed reduction order) and there is one implementation. `block_mask`: see the module's docstring."""
     assert dtype in _HALF
     if q.device.type != "cuda":
         raise _lib.UnividHipError(f"flash_attention: tensors must live on the GPU (got {q.device}); univid_amd has no CPU path")
@@ -70,6 +76,12 @@ def flash_attention(q, k, v, q_lens=None, k_lens=None, dropout_p=0., softmax_sca
     if causal:
         window = (window[0], 0)      # flash-attn: causal forces right = 0, whatever window_size[1] says
     windowed = window != (-1, -1)
+    masked = block_mask is not None
+    if masked and windowed:
+        raise NotImplementedError("flash_attention: block_mask combined with causal / window_size is not built: fold the window into the mask")
+    if masked and not isinstance(block_mask, _lib.PreparedBlockMask) and not (torch.is_tensor(block_mask) and block_mask.dtype == torch.bool):
+        raise TypeError(f"flash_attention: block_mask must be a PreparedBlockMask or a torch.bool tensor, got "
+                        f"{block_mask.dtype if torch.is_tensor(block_mask) else type(block_mask).__name__}")
     if dropout_p:
         raise NotImplementedError("flash_attention: dropout_p > 0 is a training option; the inference kernels have no dropout")
     if q_scale is not None:
@@ -88,6 +100,10 @@ def flash_attention(q, k, v, q_lens=None, k_lens=None, dropout_p=0., softmax_sca
     if windowed and lq != lk:
         raise NotImplementedError(f"flash_attention: causal / window_size with Lq != Lk ({lq} vs {lk}: flash-attn's bottom-right alignment) "
                                   f"is not built, self-attention only")
+    if masked and c != 128:
+        raise NotImplementedError(f"flash_attention: block_mask with head size {c} is not built (the block-sparse kernel is head size 128)")
+    if masked and lq != lk:
+        raise NotImplementedError(f"flash_attention: block_mask with Lq != Lk ({lq} vs {lk}) is not built, self-attention only")
     out_dtype = q.dtype
     if any(ql != lq for ql in _lens(q_lens, b, lq, "q_lens")):
         raise ValueError("flash_attention: q_lens other than Lq cannot be returned as [B, Lq, N, C] (attention.py:107,127)")
@@ -101,6 +117,16 @@ def flash_attention(q, k, v, q_lens=None, k_lens=None, dropout_p=0., softmax_sca
                                   f"first, as WanModel.forward does")
     if windowed and vh.dtype != torch.bfloat16:
         raise NotImplementedError("flash_attention: causal / window_size with fp16 tensors is not built (the windowed kernels are bf16)")
+    if masked and any(kl != lk for kl in kls):
+        raise NotImplementedError(f"flash_attention: block_mask with ragged k_lens {kls} (Lk = {lk}) is not built: strip the padding first, "
+                                  f"as WanModel.forward does")
+    if masked and vh.dtype != torch.bfloat16:
+        raise NotImplementedError("flash_attention: block_mask with fp16 tensors is not built (the block-sparse kernel is bf16)")
+    if masked:
+        bm = block_mask if isinstance(block_mask, _lib.PreparedBlockMask) else _lib.prepare_block_mask(block_mask, lk, q.device)
+        if bm.L != lk or bm.heads not in (1, n):
+            raise ValueError(f"flash_attention: block_mask was prepared for L = {bm.L} and {bm.heads} head(s); this call has L = {lk} and "
+                             f"{n} heads (1 = shared by all heads)")
     C = n * c
     dev = q.device
     scale = float(softmax_scale) if softmax_scale is not None else c ** -0.5
@@ -118,6 +144,8 @@ def flash_attention(q, k, v, q_lens=None, k_lens=None, dropout_p=0., softmax_sca
             vt_of(v2[s * lk:(s + 1) * lk], lk, vt, s * lk)
         if windowed:
             _lib.flash_attn_win(q2, k2, vt, out.view(b * lq, C), lq, n, c, scale, window, batch=b)
+        elif masked:
+            _lib.flash_attn_bs(q2, k2, vt, out.view(b * lq, C), lq, n, c, scale, bm, batch=b)
         else:
             _lib.flash_attn(q2, k2, vt, out.view(b * lq, C), lq, lk, n, c, scale, batch=b)
     else:
@@ -127,6 +155,8 @@ def flash_attention(q, k, v, q_lens=None, k_lens=None, dropout_p=0., softmax_sca
             vt_of(v2[s * lk:s * lk + L], L, vt, 0)
             if windowed:        # (every k_len == Lk here: Lk % 8 != 0 at batch > 1)
                 _lib.flash_attn_win(q2[s * lq:(s + 1) * lq], k2[s * lk:s * lk + L], vt, out[s], lq, n, c, scale, window)
+            elif masked:
+                _lib.flash_attn_bs(q2[s * lq:(s + 1) * lq], k2[s * lk:s * lk + L], vt, out[s], lq, n, c, scale, bm)
             else:
                 _lib.flash_attn(q2[s * lq:(s + 1) * lq], k2[s * lk:s * lk + L], vt, out[s], lq, L, n, c, scale)
     out = out.view(b, lq, n, c)
@@ -139,9 +169,46 @@ def flash_attention(q, k, v, q_lens=None, k_lens=None, dropout_p=0., softmax_sca
 
 
 def attention(q, k, v, q_lens=None, k_lens=None, dropout_p=0., softmax_scale=None, q_scale=None, causal=False,
-              window_size=(-1, -1), deterministic=False, dtype=torch.bfloat16, fa_version=None):
+              window_size=(-1, -1), deterministic=False, dtype=torch.bfloat16, fa_version=None, *, block_mask=None):
     """attention.py:133-179. The reference falls back to `scaled_dot_product_attention` WITHOUT the padding mask when no
     flash-attn wheel is installed; here the kernel is always present, so this is `flash_attention` (mask included)."""
     return flash_attention(q=q, k=k, v=v, q_lens=q_lens, k_lens=k_lens, dropout_p=dropout_p, softmax_scale=softmax_scale,
                            q_scale=q_scale, causal=causal, window_size=window_size, deterministic=deterministic, dtype=dtype,
-                           version=fa_version)
+                           version=fa_version, block_mask=block_mask)
+
+
+def video_block_mask(grid, frames=(-1, -1), rows=-1, cols=-1, num_heads=None, q_block=128, k_block=64):
+    """A block mask [ceil(L / q_block), ceil(L / k_block)] (bool, CPU; [num_heads, ...] with the same mask per head when num_heads is
+    given) for a video of grid = (F, H, W) patches flattened as i = (f * H + h) * W + w, L = F H W: block (qb, kb) is set iff SOME query
+    token in qb and SOME key token in kb have -before <= f_k - f_q <= after, |h_k - h_q| <= rows and |w_k - w_q| <= cols, with frames =
+    (before, after); -1 = unbounded on that axis.
+
+    The result is the BLOCK COVER of that 3-D neighbourhood: attention under it (`flash_attention(block_mask=)`,
+    `WanModel.set_attn_block_mask`) computes the function the MASK defines - every query of a block sees every key of each set tile -
+    not the element-exact neighbourhood, which it contains. Every query block sees at least its own tokens, so no row is empty."""
+    F, H, W = (int(g) for g in grid)
+    before, after = (int(f) for f in frames)
+    rows, cols = int(rows), int(cols)
+    if min(F, H, W) < 1 or min(before, after, rows, cols) < -1:
+        raise ValueError(f"video_block_mask: grid {grid!r} must be positive, frames {frames!r} / rows {rows} / cols {cols} >= 0 or -1 = unbounded")
+    L = F * H * W
+    nqb, nkb = -(-L // q_block), -(-L // k_block)
+    i = torch.arange(L)
+    f, h, w = i // (H * W), (i // W) % H, i % W
+
+    def near(lo, hi, size):
+        """[size, size] bool: lo <= c_k - c_q <= hi, -1 = unbounded."""
+        d = torch.arange(size)[None, :] - torch.arange(size)[:, None]
+        return ((d >= -lo) if lo >= 0 else torch.ones_like(d, dtype=torch.bool)) & ((d <= hi) if hi >= 0 else torch.ones_like(d, dtype=torch.bool))
+
+    # ONE token pair must meet all three conditions, so the axes cannot be covered separately: per query block, the keys within reach of
+    # SOME of its tokens (q_block x L pair tests), then the tiles those keys lie in
+    qcell = i // q_block
+    kcell = i // k_block
+    nf, nh, nw = near(before, after, F), near(rows, rows, H), near(cols, cols, W)
+    mask = torch.zeros(nqb, nkb, dtype=torch.bool)
+    for qb in range(nqb):
+        sel = qcell == qb
+        ok = (nf[f[sel]][:, f] & nh[h[sel]][:, h] & nw[w[sel]][:, w]).any(dim=0)       # [L] keys
+        mask[qb, kcell[ok].unique()] = True
+    return mask if num_heads is None else mask[None].expand(int(num_heads), nqb, nkb).clone()

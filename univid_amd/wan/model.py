@@ -118,6 +118,78 @@ def _check_attn_window(window, head_dim=128, attn_precision="bf16"):
     return window
 
 
+class AttnBlockMask:
+    """set_attn_block_mask's spec as the self-attention launches resolve it: the PreparedBlockMask of a forward's patch grid. spec: a
+    PreparedBlockMask or a bool tensor (one fixed L: a forward at another L raises), or a callable f(F, H, W, num_heads) -> bool mask
+    [ceil(L / 128), ceil(L / 64)] or [num_heads, ...] with L = F H W, evaluated and prepared ONCE per distinct (grid, device) and cached.
+    Preparing builds lists on the CPU and uploads them, which a HIP-graph capture cannot hold: a forward inside a capture whose grid was
+    not prepared raises (WanTI2V's eager warm-up forward prepares it before it captures; `prepare(grid, device)` does so by hand)."""
+
+    def __init__(self, spec, num_heads):
+        self.spec, self.num_heads, self._cache = spec, int(num_heads), {}
+
+    def prepared(self):
+        """{(grid or L, device): PreparedBlockMask} of what was prepared so far (tools report the densities)."""
+        return dict(self._cache)
+
+    def prepare(self, grid, device):
+        return self.resolve(tuple(int(g) for g in grid), math.prod(int(g) for g in grid), torch.device(device))
+
+    def resolve(self, grid, L, device):
+        spec = self.spec
+        if isinstance(spec, _lib.PreparedBlockMask):
+            if spec.L != L:
+                raise ValueError(f"attn_block_mask was prepared for L = {spec.L}; this forward has L = {L} (patch grid {tuple(grid)})")
+            if spec.device != device:
+                raise ValueError(f"attn_block_mask lives on {spec.device}; this forward runs on {device}")
+            return spec
+        key = (L, device) if torch.is_tensor(spec) else (tuple(grid), device)
+        bm = self._cache.get(key)
+        if bm is None:
+            if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+                raise RuntimeError(f"attn_block_mask: patch grid {tuple(grid)} (L = {L}) was not prepared before this HIP-graph capture - "
+                                   f"run one eager forward at this grid, or AttnBlockMask.prepare(grid, device), first")
+            mask = spec if torch.is_tensor(spec) else spec(int(grid[0]), int(grid[1]), int(grid[2]), self.num_heads)
+            bm = _lib.prepare_block_mask(mask, L, device)      # (a tensor of another L's shape is refused here, naming the shape)
+            if bm.heads not in (1, self.num_heads):
+                raise ValueError(f"attn_block_mask: a per-head mask needs {self.num_heads} heads, got {bm.heads}")
+            self._cache[key] = bm
+        return bm
+
+
+def _check_attn_block_mask(spec, head_dim=128, attn_precision="bf16", attn_window=None, num_heads=None):
+    """set_attn_block_mask's guards, on one self-attention's geometry: raises before any state changes. Returns None (global attention) or
+    the AttnBlockMask that resolves the spec."""
+    if spec is None:
+        return None
+    if isinstance(spec, AttnBlockMask):
+        resolver, spec = spec, spec.spec
+    else:
+        resolver = None
+    if torch.is_tensor(spec):
+        if spec.dtype != torch.bool or spec.dim() not in (2, 3):
+            raise TypeError(f"attn_block_mask: a tensor spec must be torch.bool [nqb, nkb] or [num_heads, nqb, nkb], got {spec.dtype} "
+                            f"{tuple(spec.shape)}")
+        heads = spec.shape[0] if spec.dim() == 3 else 1
+    elif isinstance(spec, _lib.PreparedBlockMask):
+        heads = spec.heads
+    elif callable(spec):
+        heads = 1
+    else:
+        raise TypeError(f"attn_block_mask: None, a bool tensor, a PreparedBlockMask or a callable f(F, H, W, num_heads), got {type(spec).__name__}")
+    if num_heads is not None and heads not in (1, num_heads):
+        raise ValueError(f"attn_block_mask: a per-head mask needs {num_heads} heads (or one mask for all), got {heads}")
+    if head_dim != 128:
+        raise NotImplementedError(f"attn_block_mask: the block-sparse attention kernel is built for head_dim 128 (this model has {head_dim})")
+    if attn_precision != "bf16":
+        raise NotImplementedError(f"attn_block_mask with attn_precision {attn_precision!r}: the block-sparse attention kernel is bf16 only "
+                                  f"- set_attn_precision('bf16') or set_attn_block_mask(None) first")
+    if attn_window is not None:
+        raise NotImplementedError(f"attn_block_mask with window_size {tuple(attn_window)}: one or the other - set_attn_window(None) first, "
+                                  f"or fold the window into the mask")
+    return resolver if resolver is not None else AttnBlockMask(spec, num_heads if num_heads is not None else heads)
+
+
 def _check_ffn_precision(mode, dim, ffn_dim, ffn):
     """Everything that can refuse a mode, before any state changes."""
     if mode not in FFN_PRECISIONS:
@@ -282,6 +354,7 @@ class WanSelfAttention(nn.Module):
         # (left, right) of flash-attn's window_size, or None = global attention (WanModel.set_attn_window): instance state
         self.attn_window = _check_attn_window(window_size, self.head_dim)
         self.window_size = self.attn_window or (-1, -1)
+        self.attn_block_mask = None      # an AttnBlockMask, or None = global attention (WanModel.set_attn_block_mask): instance state
         self.q = nn.Linear(dim, dim)
         self.k = nn.Linear(dim, dim)
         self.v = nn.Linear(dim, dim)
@@ -340,6 +413,14 @@ class WanSelfAttention(nn.Module):
         C, H, D = self.dim, self.num_heads, self.head_dim
         M = batch * L
         dev = h[0].device if isinstance(h, tuple) else h.device
+        bm = None
+        if self.attn_block_mask is not None:
+            # the mask counts tokens of the UNPADDED sequence (set_attn_block_mask keeps attn_precision at "bf16" and no window beside it);
+            # resolved before the first launch: a refused mask leaves nothing half-computed
+            if Lk != L:
+                raise NotImplementedError(f"attn_block_mask with padded samples (seq_len {Lk} < {L}) is not built: call WanModel.forward, "
+                                          f"which strips the padding")
+            bm = self.attn_block_mask.resolve(grid, L, dev)
         vt = _vt_scratch("vt", C, batch, L, dev)
         ql, kl = self._qkv(h, M, L, s0, vt)
         att = _act_buf(M, C, (self._slots["o"],), dev)
@@ -350,6 +431,10 @@ class WanSelfAttention(nn.Module):
                                           f"call WanModel.forward, which strips the padding")
             _lib.rmsnorm_rope_qk(ql, kl, self.norm_q.weight, self.norm_k.weight, M, L, C, D, self.eps, freqs, grid)
             _lib.flash_attn_win(ql, kl, vt, att, L, H, D, 1.0 / math.sqrt(D), self.attn_window, batch=batch)
+            return _slotted(att, C, self._slots["o"], M, L, s0)
+        if bm is not None:
+            _lib.rmsnorm_rope_qk(ql, kl, self.norm_q.weight, self.norm_k.weight, M, L, C, D, self.eps, freqs, grid)
+            _lib.flash_attn_bs(ql, kl, vt, att, L, H, D, 1.0 / math.sqrt(D), bm, batch=batch)
             return _slotted(att, C, self._slots["o"], M, L, s0)
         if self.attn_precision != "bf16":
             # q and k leave the norm + RoPE pass as MXFP8 codes + scales (fresh buffers: no in-place form), S = K Q^T on the block-scaled
@@ -401,6 +486,9 @@ class WanSelfAttention(nn.Module):
         if self.attn_window is not None:
             raise NotImplementedError(f"window_size {self.attn_window} is not built for the sequence-parallel forward (the Ulysses attention "
                                       f"runs the dense kernel): set_attn_window(None) or run without sequence parallelism")
+        if self.attn_block_mask is not None:
+            raise NotImplementedError("attn_block_mask is not built for the sequence-parallel forward (the Ulysses attention runs the dense "
+                                      "kernel): set_attn_block_mask(None) or run without sequence parallelism")
         if self.attn_precision != "bf16":
             raise NotImplementedError(f"attn_precision {self.attn_precision!r} is not built for the sequence-parallel forward (the Ulysses "
                                       f"exchange carries bf16 q / k): set_attn_precision('bf16') or run without sequence parallelism")
@@ -445,6 +533,9 @@ class WanSelfAttention(nn.Module):
         if self.attn_window is not None and any(int(s) < L for s in seq_lens):
             raise NotImplementedError(f"window_size {self.attn_window} with padded samples (seq_lens {[int(s) for s in seq_lens]} < {L}) is "
                                       f"not built: call WanModel.forward, which strips the padding")
+        if self.attn_block_mask is not None and any(int(s) < L for s in seq_lens):
+            raise NotImplementedError(f"attn_block_mask with padded samples (seq_lens {[int(s) for s in seq_lens]} < {L}) is not built: "
+                                      f"call WanModel.forward, which strips the padding")
         _ensure_prepared(self)
         outs = []
         fr = _freqs_device(freqs, x.device)
@@ -595,14 +686,23 @@ class WanAttentionBlock(nn.Module):
         (WanModel.set_attn_precision states the modes). No prepared weight depends on it."""
         _check_attn_precision(mode, self.self_attn.head_dim)
         _check_attn_window(self.self_attn.attn_window, self.self_attn.head_dim, mode)
+        _check_attn_block_mask(self.self_attn.attn_block_mask, self.self_attn.head_dim, mode)
         self.self_attn.attn_precision = mode
 
     def set_attn_window(self, window_size):
         """(left, right) as flash-attn's window_size, or None / (-1, -1) for global attention: this block's self-attention
         (WanModel.set_attn_window states the mode). No prepared weight depends on it."""
         w = _check_attn_window(window_size, self.self_attn.head_dim, self.self_attn.attn_precision)
+        _check_attn_block_mask(self.self_attn.attn_block_mask, attn_window=w)
         self.self_attn.attn_window = w
         self.self_attn.window_size = self.window_size = w or (-1, -1)
+
+    def set_attn_block_mask(self, spec):
+        """None (global attention), a bool tensor / PreparedBlockMask of one fixed L, a callable f(F, H, W, num_heads) -> bool mask, or an
+        AttnBlockMask that resolves one of them: this block's self-attention (WanModel.set_attn_block_mask states the mode). No prepared
+        weight depends on it."""
+        a = self.self_attn
+        a.attn_block_mask = _check_attn_block_mask(spec, a.head_dim, a.attn_precision, a.attn_window, a.num_heads)
 
     def set_proj_precision(self, mode):
         """"bf16" (default: the reference's arithmetic) or "mxfp8": this block's self-attention q / k / v / o and cross-attention q / o on
@@ -938,6 +1038,7 @@ class WanModel(nn.Module):
         self._text_weight = None  # (per-sample weights, rows, layers | None): set_text_weight
         self.ffn_precision = "bf16"  # set_ffn_precision
         self.attn_precision = "bf16"  # set_attn_precision
+        self.attn_block_mask = None   # set_attn_block_mask: an AttnBlockMask, or None = global attention
         self.proj_precision = "bf16"  # set_proj_precision
         self.dedup_twins = True   # block 0's self-attention half once for samples that enter with identical rows (the CFG pair); A/B switch
         self.register_load_state_dict_post_hook(lambda m, _k: m.invalidate())
@@ -1013,9 +1114,11 @@ class WanModel(nn.Module):
         Calls invalidate(): the prepared-weights generation moves on, so captured HIP graphs (WanTI2V) re-capture."""
         _check_attn_precision(mode, self.blocks[0].self_attn.head_dim if len(self.blocks) else 128)
         _check_attn_window(self.attn_window, attn_precision=mode)
+        _check_attn_block_mask(self.attn_block_mask, attn_precision=mode)
         for b in self.blocks:
             _check_attn_precision(mode, b.self_attn.head_dim)
             _check_attn_window(b.self_attn.attn_window, b.self_attn.head_dim, mode)
+            _check_attn_block_mask(b.self_attn.attn_block_mask, b.self_attn.head_dim, mode)
         self.attn_precision = mode
         for b in self.blocks:
             b.set_attn_precision(mode)
@@ -1032,12 +1135,37 @@ class WanModel(nn.Module):
         NotImplementedError while a window is set. Independent of ffn_precision / proj_precision and of un-merged LoRA. Every guard runs
         before any state changes. Calls invalidate(): the prepared-weights generation moves on, so captured HIP graphs (WanTI2V) re-capture."""
         w = _check_attn_window(window_size, self.dim // self.num_heads, self.attn_precision)
+        _check_attn_block_mask(self.attn_block_mask, attn_window=w)
         for b in self.blocks:
             _check_attn_window(window_size, b.self_attn.head_dim, b.self_attn.attn_precision)
+            _check_attn_block_mask(b.self_attn.attn_block_mask, attn_window=w)
         self.attn_window = w
         self.window_size = self.config["window_size"] = w or (-1, -1)
         for b in self.blocks:
             b.set_attn_window(w)
+        self.invalidate()
+
+    def set_attn_block_mask(self, spec):
+        """Block-sparse SELF-attention in every block (uv_flash_attn_bs_bf16): token i of head h attends token j of its sample iff
+        mask[h][i // 128][j // 64], on the flattened (frame, row, column) sequence - the masks of the training-free sparse-attention
+        schemes for video DiTs (univid_amd.wan.attention.video_block_mask builds the block cover of a 3-D neighbourhood). spec: None =
+        global attention (default); a bool tensor [ceil(L / 128), ceil(L / 64)] or [num_heads, ...] or a _lib.PreparedBlockMask, for ONE
+        sequence length (a forward at another L raises); or a callable f(F, H, W, num_heads) -> such a bool mask for the patch grid
+        (F, H, W), evaluated and prepared once per distinct grid and cached - in an eager forward: a forward inside a HIP-graph capture
+        at a grid that was not prepared raises (WanTI2V's warm-up forward prepares it). Opt-in: it CHANGES the model's function (exactly -
+        the same softmax over fewer keys), it is not an approximation of global attention (README). Cross-attention is untouched.
+        Needs head_dim 128, attn_precision "bf16" and no window_size (NotImplementedError otherwise; set_attn_precision refuses an MXFP8
+        mode and set_attn_window a window while a mask is set); the sequence-parallel forward and the reference-signature
+        WanSelfAttention.forward on padded samples raise NotImplementedError while a mask is set. Independent of ffn_precision /
+        proj_precision and of un-merged and per-sample LoRA. Every guard runs before any state changes. Calls invalidate(): the
+        prepared-weights generation moves on, so captured HIP graphs (WanTI2V) re-capture."""
+        r = _check_attn_block_mask(spec, self.dim // self.num_heads, self.attn_precision, self.attn_window, self.num_heads)
+        for b in self.blocks:
+            a = b.self_attn
+            _check_attn_block_mask(r, a.head_dim, a.attn_precision, a.attn_window, a.num_heads)
+        self.attn_block_mask = r
+        for b in self.blocks:
+            b.set_attn_block_mask(r)      # one resolver: every block shares its cache
         self.invalidate()
 
     def set_proj_precision(self, mode):

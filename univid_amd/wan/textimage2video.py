@@ -235,7 +235,7 @@ class WanTI2V:
     def __init__(self, config=TI2VConfig, checkpoint_dir=None, device_id=0, rank=0, t5_fsdp=False, dit_fsdp=False,
                  use_sp=False, t5_cpu=False, init_on_cpu=True, convert_model_dtype=False, *, model: WanModel = None,
                  vae=None, text_encoder: Optional[Callable] = None, device=None, ffn_precision=None, attn_precision=None, proj_precision=None,
-                 vae_precision=None, attn_window=None):
+                 vae_precision=None, attn_window=None, attn_block_mask=None):
         if t5_fsdp or dit_fsdp:
             raise NotImplementedError("FSDP is not part of this build (UniVid passes False, models/model_pipeline.py:2205-2207; "
                                       "the fp32 masters + bf16 operands of the 5B DiT are 30 GB of a 288 GB GPU)")
@@ -281,6 +281,10 @@ class WanTI2V:
             # (left, right) as flash-attn's window_size (WanModel.set_attn_window): opt-in sliding-window / causal self-attention, passed on like
             # attn_precision; None keeps what the model came with (its checkpoint's config.json, global attention unless it says otherwise)
             self.model.set_attn_window(attn_window)
+        if attn_block_mask is not None:
+            # a bool mask / PreparedBlockMask / callable f(F, H, W, num_heads) (WanModel.set_attn_block_mask): opt-in block-sparse self-attention,
+            # passed on like attn_window; None keeps the model as it came (global attention)
+            self.model.set_attn_block_mask(attn_block_mask)
         if proj_precision is not None and proj_precision != self.model.proj_precision:
             # "bf16" | "mxfp8" (WanModel.set_proj_precision): the opt-in MXFP8 mode of the attention projections, passed on like ffn_precision
             self.model.set_proj_precision(proj_precision)
