@@ -261,6 +261,39 @@ int uv_flash_attn_bs_bf16(const void* q, long ldq, const void* k, long ldk, cons
  * batch - whatever the mask holds. Host-only. */
 int uv_flash_attn_bs_plan(int batch, int L, int H, int head_dim, char* kernel, int len, int* q_blocks, int* grid);
 
+/* ---- DiT: data-dependent block-sparse self-attention - top-k key tiles chosen on the device (opt-in; TopKBlockMask) -------------------
+ * No counterpart in the reference. uv_flash_attn_bs_bf16's domain (Lq == Lk == L, head_dim 128, bf16, nqb = ceil(L / 128), nkb =
+ * ceil(L / 64)) with lists that a kernel builds per forward, sample, head and query block from pooled q.k scores. Three launches on one
+ * stream: uv_attn_pool_qk, uv_attn_bs_select, uv_flash_attn_bs_lists_bf16. Deterministic: no atomics, fixed summation order.
+ *
+ * uv_attn_pool_qk: q, k bf16 [batch * L, >= H * 128] (row stride ldq / ldk elements, multiples of 8, head h at column 128 h; sample b = rows
+ * [b L, (b + 1) L)) -> qbar fp32 [batch, H, nqb, 128] = the mean of the q rows of each 128-query block and kbar fp32 [batch, H, nkb, 128] =
+ * the mean of the k rows of each 64-key tile: the fp32 sum of the block's VALID rows (a ragged last block / tile holds L % 128 / L % 64 of
+ * them) divided by their count. Both contiguous. q and k are read once. Pointers 16-byte aligned; head_dim 128 only; batch > 1 needs
+ * L % 8 == 0 (uv_flash_attn_bs_bf16's rule). Anything else is rejected and nothing is written. */
+int uv_attn_pool_qk(const void* q, long ldq, const void* k, long ldk, void* qbar, void* kbar, int batch, int L, int H, int head_dim, void* stream);
+
+/* uv_attn_bs_select: the lists of (sample b, head h, query block i) from qbar / kbar as uv_attn_pool_qk writes them. s[j] = sum_d
+ * qbar[b][h][i][d] kbar[b][h][j][d] in fp32 (no softmax, no scale). keep: uint8 [keep_heads, nqb, nkb] (non-zero = the tile is always
+ * listed), keep_heads = 1 (one keep mask for all heads) or H, shared by the samples; null = nothing is kept (keep_heads is still checked).
+ * Among the tiles of the row that are NOT kept, the top_k best under the total order (score descending, tile index ascending) are listed as
+ * well; fewer than top_k candidates: all of them. Scores are compared through an order-preserving unsigned image of their bits (-0 taken as
+ * +0; NaNs sort at the two ends), so the choice is deterministic and, whatever the scores hold, the list is valid: tile_cnt[b][h][i] =
+ * keepcount + min(top_k, nkb - keepcount) in [1, nkb], the first tile_cnt entries of tile_idx[b][h][i][:] strictly ascending in
+ * [0, nkb - 1] (the ragged tile nkb - 1 can only be last). Entries behind the count are left as they were. tile_idx int32 [batch, H, nqb,
+ * nkb], tile_cnt int32 [batch, H, nqb]: uv_flash_attn_bs_lists_bf16's format with mask_heads = H, mask_samples = batch. top_k >= 1; nkb <=
+ * 4096 (the row is sorted in LDS); qbar / kbar 16-byte aligned. Anything else is rejected and nothing is written. */
+int uv_attn_bs_select(const void* qbar, const void* kbar, const void* keep, int keep_heads, int top_k, int* tile_idx, int* tile_cnt, int batch,
+                      int L, int H, void* stream);
+
+/* uv_flash_attn_bs_bf16 under lists with a leading sample axis: tile_idx int32 [mask_samples, mask_heads, nqb, nkb], tile_cnt int32
+ * [mask_samples, mask_heads, nqb]; mask_samples = 1 (the samples share the lists: uv_flash_attn_bs_bf16 exactly, bit for bit) or batch
+ * (sample b walks its own lists). The same kernel, checks and guarantees; the lists may have been written by a kernel launched before on the
+ * same stream (uv_attn_bs_select). */
+int uv_flash_attn_bs_lists_bf16(const void* q, long ldq, const void* k, long ldk, const void* vt, long ldvt, void* out, long ldo, int batch,
+                                int L, int H, int head_dim, float softmax_scale, const int* tile_idx, const int* tile_cnt, int mask_heads,
+                                int mask_samples, void* stream);
+
 /* ---- DiT: self-attention with MXFP8 q / k (opt-in mode; WanModel.set_attn_precision("mxfp8_qk")) ------------------------------
  * uv_flash_attn_bf16 with q and k in the MXFP8 format stated above (e4m3fn codes, one e8m0 byte per 32 consecutive elements of a row, e =
  * clamp(exp(amax) - 8, 0, 254), clamp to +-448 then RNE, never a NaN code): replaces attention.py:24-130 as called at model.py:145-150 with

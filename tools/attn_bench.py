@@ -6,7 +6,11 @@
     --block-mask F,H,W  (F H W == L: the patch grid) the dense launch against uv_flash_attn_bs_bf16 under the all-ones mask (what a listed tile
                         costs), video_block_mask of +-2 frames - beside window_size = 2 frames each way through uv_flash_attn_win_bf16 -, of
                         +-1 frame x +-8 rows (no window expresses it) and a per-head mix (spatial heads: the own frame; temporal heads: every
-                        frame, +-2 rows x +-4 columns), all alternating in one process"""
+                        frame, +-2 rows x +-4 columns), all alternating in one process
+    --attn-topk K[,B,A,R,C]  with --block-mask F,H,W: also the data-dependent lists of TopKBlockMask(K, keep) - K an int or a fraction of the key
+                        tiles, keep = video_block_mask(frames=(B, A), rows=R, cols=C) when given: uv_attn_pool_qk, uv_attn_bs_select and
+                        uv_flash_attn_bs_lists_bf16 each on its own, beside uv_flash_attn_bs_bf16 under a STATIC mask of the same lists'
+                        density (the keep tiles plus the K nearest others), and pooling against its traffic bound (one read of q and k)"""
 import math, os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from univid_amd import _lib
@@ -193,3 +197,47 @@ if "--block-mask" in sys.argv:
         print(f"block mask {name} B{B} L{L}: median {med[name]:.1f} us (min {min(t):.1f} max {max(t):.1f}); dense / masked = {med['dense'] / med[name]:.3f}; "
               f"density {bm.density:.4f}, {tiles} tiles visited, {med[name] * 1e3 / tiles:.2f} ns per tile ({med[name] * 1e3 / tiles / per_dense:.3f} x the dense "
               f"kernel's); grid order: XCD-contiguous block ids (flash_attn_fwd3_kernel's); plan={_lib.attn_bs_plan(L, D, B, H)}")
+
+    if "--attn-topk" in sys.argv:
+        # The three launches of a TopKBlockMask on the same operands, in the same alternation: pooling, selection, and the attention under the
+        # device-built lists - beside the static-mask launch of EQUAL density (every row lists the keep tiles plus the top_k non-kept tiles
+        # nearest to its diagonal). Random q / k give scattered lists; real activations are not measured here.
+        from univid_amd.wan.attention import TopKBlockMask
+        arg = sys.argv[sys.argv.index("--attn-topk") + 1].split(",")
+        keep_mask = video_block_mask(grid, frames=(int(arg[1]), int(arg[2])), rows=int(arg[3]), cols=int(arg[4])) if len(arg) == 5 else None
+        top_k = TopKBlockMask(float(arg[0]) if "." in arg[0] else int(arg[0])).count(L)
+        keep = None if keep_mask is None else _lib.prepare_keep_mask(keep_mask, L, dev)[0]
+        kb = torch.zeros(nqb, nkb, dtype=torch.bool) if keep_mask is None else keep_mask
+        dist = (torch.arange(nkb)[None, :] - 2 * torch.arange(nqb)[:, None]).abs().double().masked_fill(kb, float("inf"))
+        near = torch.zeros_like(kb)
+        near.scatter_(1, dist.argsort(dim=1, stable=True)[:, :top_k], True)
+        static = _lib.prepare_block_mask(kb | (near & ~kb), L, dev)
+        qbar, kbar = torch.empty(B, H, nqb, D, device=dev), torch.empty(B, H, nkb, D, device=dev)
+        idx, cnt = torch.empty(B, H, nqb, nkb, dtype=torch.int32, device=dev), torch.empty(B, H, nqb, dtype=torch.int32, device=dev)
+        o_topk, o_static = torch.empty_like(out), torch.empty_like(out)
+        work = {"dense": work["dense"],
+                "static mask": lambda: _lib.flash_attn_bs(q, k, vt, o_static, L, H, D, 1 / math.sqrt(D), static, batch=B),
+                "pool": lambda: _lib.attn_pool_qk(q, k, qbar, kbar, L, H, D, batch=B),
+                "select": lambda: _lib.attn_bs_select(qbar, kbar, keep, top_k, idx, cnt, L, H, batch=B),
+                "top-k lists": lambda: _lib.flash_attn_bs_lists(q, k, vt, o_topk, L, H, D, 1 / math.sqrt(D), idx, cnt, H, B, batch=B)}
+        times = {name: [] for name in work}
+        for rnd in range(rounds + 1):
+            for name, fn in work.items():
+                fn(); torch.cuda.synchronize()
+                s.record()
+                for _ in range(n):
+                    fn()
+                e.record(); torch.cuda.synchronize()
+                if rnd:
+                    times[name].append(s.elapsed_time(e) / n * 1e3)
+        med = {name: statistics.median(t) for name, t in times.items()}
+        tiles_topk, tiles_static = int(cnt.sum()), B * H * int(static.tile_cnt.sum())
+        assert tiles_topk == tiles_static or keep_mask is not None, "the static mask of equal density lists another number of tiles"
+        gb = (q.numel() + k.numel()) * 2 / 1e9
+        for name, t in times.items():
+            print(f"top-k {name} B{B} L{L} top_k {top_k} keep {arg[1:] or None}: median {med[name]:.1f} us (min {min(t):.1f} max {max(t):.1f}, {len(t)} rounds of {n})")
+        print(f"pool: {gb / med['pool'] * 1e3:.2f} TB/s over one read of q and k ({gb * 1e3:.1f} MB); pool + select = {med['pool'] + med['select']:.1f} us = "
+              f"{(med['pool'] + med['select']) / med['top-k lists']:.3f} of the launch under its lists; top-k lists / static mask = "
+              f"{med['top-k lists'] / med['static mask']:.3f} at {tiles_topk} vs {tiles_static} tiles ({tiles_topk / dense_tiles:.4f} of dense); "
+              f"per listed tile {med['top-k lists'] * 1e3 / tiles_topk:.2f} ns ({med['top-k lists'] * 1e3 / tiles_topk / per_dense:.3f} x the dense kernel's); "
+              f"dense / (pool + select + launch) = {med['dense'] / (med['pool'] + med['select'] + med['top-k lists']):.3f}")

@@ -13,6 +13,9 @@ f32-grade bf16x6 / f16x3 modes - at the bench size (49 frames of 704 x 1280) and
     --window-ab ROUNDS   instead of the table: ms per denoise step with global attention and with --attn-window, alternating in one process
     --attn-block-mask B,A,R,C   with --window-ab: a third side, the self-attention under video_block_mask(frames=(B, A), rows=R, cols=C) of the
                          latent's patch grid (WanModel.set_attn_block_mask; -1 = unbounded); --attn-window may then be left out
+    --attn-topk K[,B,A,R,C]   with --window-ab: one more side, the self-attention under TopKBlockMask(K, keep) - K an int or a fraction of the
+                         key tiles, keep = video_block_mask(frames=(B, A), rows=R, cols=C) when given - with lists built on the device per
+                         forward, sample and head; the other sides may then be left out
     --attn-ab ROUNDS   instead of the table: ms per denoise step with the self-attention in bf16, mxfp8_qk and mxfp8_qk_pv, alternating in one process"""
 import os, sys, time, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -87,7 +90,8 @@ if "--window-ab" in sys.argv:
     import statistics
     from univid_amd.wan.attention import video_block_mask
     vm = tuple(int(v) for v in sys.argv[sys.argv.index("--attn-block-mask") + 1].split(",")) if "--attn-block-mask" in sys.argv else None
-    assert attn_window is not None or vm is not None, "--window-ab needs --attn-window L,R or --attn-block-mask B,A,R,C"
+    tk = sys.argv[sys.argv.index("--attn-topk") + 1].split(",") if "--attn-topk" in sys.argv else None
+    assert attn_window is not None or vm is not None or tk is not None, "--window-ab needs --attn-window L,R, --attn-block-mask B,A,R,C or --attn-topk K[,B,A,R,C]"
     rounds, F = int(sys.argv[sys.argv.index("--window-ab") + 1]), frames[0]
     pipe = WanTI2V(model=m, vae=Wan2_2_VAE(device=dev, seed=0, precision="f16x3"), device=dev)
     ms = {None: []}
@@ -96,11 +100,21 @@ if "--window-ab" in sys.argv:
     if vm is not None:
         ms[f"video_block_mask{vm}"] = []
     spec = None if vm is None else (lambda Fg, Hg, Wg, nh: video_block_mask((Fg, Hg, Wg), frames=vm[:2], rows=vm[2], cols=vm[3]))
+    specs = {f"video_block_mask{vm}": spec}
+    if tk is not None:
+        from univid_amd.wan.attention import TopKBlockMask
+        kv = tuple(int(v) for v in tk[1:])
+        assert len(kv) in (0, 4), "--attn-topk K or K,B,A,R,C"
+        ms[f"top_k{tuple(tk)}"] = []
+        specs[f"top_k{tuple(tk)}"] = TopKBlockMask(float(tk[0]) if "." in tk[0] else int(tk[0]),
+                                                   (lambda Fg, Hg, Wg, nh: video_block_mask((Fg, Hg, Wg), frames=kv[:2], rows=kv[2], cols=kv[3])) if kv else None)
+    resolvers = {}
     for rnd in range(rounds + 1):
         for win in ms:
             m.set_attn_block_mask(None)
             m.set_attn_window(None if isinstance(win, str) else win)
-            m.set_attn_block_mask(spec if isinstance(win, str) else None)
+            m.set_attn_block_mask(specs[win] if isinstance(win, str) else None)
+            resolvers[win] = m.attn_block_mask
             with torch.no_grad():
                 pipe.t2v("", size=(1280, 704), frame_num=F, sampling_steps=2, seed=7, prompt_embeds=pe, negative_prompt_embeds=ne, decode=False)
                 lat, t = clock(lambda: pipe.t2v("", size=(1280, 704), frame_num=F, sampling_steps=steps, seed=7, prompt_embeds=pe,
@@ -115,7 +129,7 @@ if "--window-ab" in sys.argv:
     for k in ms:
         if k is not None:
             print(f"{k} / global = {med[k] / med[None]:.4f}, gain {med[None] - med[k]:.2f} ms/step (global spread {max(ms[None]) - min(ms[None]):.2f} ms)"
-                  + ("" if spec is None or not isinstance(k, str) else f"; densities {[round(b.density, 4) for b in m.attn_block_mask.prepared().values()] if m.attn_block_mask else '-'}"),
+                  + ("" if spec is None or k != f"video_block_mask{vm}" else f"; densities {[round(b.density, 4) for b in resolvers[k].prepared().values()]}"),
                   flush=True)
     sys.exit(0)
 if "--attn-ab" in sys.argv:

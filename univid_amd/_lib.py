@@ -51,6 +51,9 @@ SIGNATURES = {
     "uv_flash_attn_win_plan": [_I, _I, _I, _I, _I, _I, _c.c_char_p, _I, _c.POINTER(_I), _c.POINTER(_I), _c.POINTER(_I)],
     "uv_flash_attn_bs_bf16": [_P, _L, _P, _L, _P, _L, _P, _L, _I, _I, _I, _I, _F, _P, _P, _I, _P],
     "uv_flash_attn_bs_plan": [_I, _I, _I, _I, _c.c_char_p, _I, _c.POINTER(_I), _c.POINTER(_I)],
+    "uv_attn_pool_qk": [_P, _L, _P, _L, _P, _P, _I, _I, _I, _I, _P],
+    "uv_attn_bs_select": [_P, _P, _P, _I, _I, _P, _P, _I, _I, _I, _P],
+    "uv_flash_attn_bs_lists_bf16": [_P, _L, _P, _L, _P, _L, _P, _L, _I, _I, _I, _I, _F, _P, _P, _I, _I, _P],
     "uv_flash_attn_mxqk": [_P, _L, _P, _L, _P, _L, _P, _L, _P, _L, _P, _L, _I, _I, _I, _I, _I, _F, _P],
     "uv_flash_attn_mxqk_plan": [_I, _I, _I, _I, _I, _c.c_char_p, _I, _c.POINTER(_I), _c.POINTER(_I), _c.POINTER(_I)],
     "uv_vt_mx_quant": [_P, _L, _P, _L, _P, _L, _I, _I, _I, _I, _P],
@@ -623,33 +626,41 @@ _PBM_TOKEN = object()
 BS_Q_BLOCK, BS_K_BLOCK = 128, 64      # the kernel's tile: 4 x UV_ATT_QW queries, UV_ATT_KV keys
 
 
+def _expand_block_mask(fn, mask, L, q_block, k_block):
+    """A block mask [nqb', nkb'] / [H, nqb', nkb'] of q_block x k_block blocks, checked against L and expanded exactly to the kernel's
+    128 x 64 tiles: (bool [heads, nqb, nkb] on the CPU, L). `fn` names the caller in the messages."""
+    if not isinstance(mask, torch.Tensor) or mask.dtype != torch.bool:
+        raise TypeError(f"{fn}: the mask must be a torch.bool tensor, got "
+                        f"{mask.dtype if isinstance(mask, torch.Tensor) else type(mask).__name__}")
+    L, q_block, k_block = int(L), int(q_block), int(k_block)
+    if L <= 0:
+        raise ValueError(f"{fn}: L = {L} must be positive")
+    if q_block <= 0 or q_block % BS_Q_BLOCK or k_block <= 0 or k_block % BS_K_BLOCK:
+        raise ValueError(f"{fn}: q_block {q_block} must be a multiple of {BS_Q_BLOCK} and k_block {k_block} a multiple of "
+                         f"{BS_K_BLOCK} (the kernel's tile is {BS_Q_BLOCK} queries x {BS_K_BLOCK} keys)")
+    if mask.dim() not in (2, 3):
+        raise ValueError(f"{fn}: the mask must be [nqb, nkb] or [H, nqb, nkb], got shape {tuple(mask.shape)}")
+    want = (-(-L // q_block), -(-L // k_block))
+    if tuple(mask.shape[-2:]) != want:
+        raise ValueError(f"{fn}: mask shape {tuple(mask.shape)} does not belong to L = {L}: {q_block} x {k_block} blocks "
+                         f"need [..., {want[0]}, {want[1]}]")
+    if mask.dim() == 3 and mask.shape[0] < 1:
+        raise ValueError(f"{fn}: a per-head mask needs at least one head")
+    m = mask.detach().to("cpu")
+    m = m[None] if m.dim() == 2 else m
+    nqb, nkb = -(-L // BS_Q_BLOCK), -(-L // BS_K_BLOCK)
+    m = m.repeat_interleave(q_block // BS_Q_BLOCK, dim=1)[:, :nqb].repeat_interleave(k_block // BS_K_BLOCK, dim=2)[:, :, :nkb].contiguous()
+    return m, L
+
+
 def prepare_block_mask(mask, L, device, q_block=BS_Q_BLOCK, k_block=BS_K_BLOCK):
     """The schedule of a block mask for `flash_attn_bs` at sequence length L. mask: a bool tensor [ceil(L / q_block), ceil(L / k_block)]
     (all heads) or [H, ...] (per head); query i of head h attends key j iff mask[h][i // q_block][j // k_block] and j < L. q_block any
     multiple of 128, k_block any multiple of 64 (128 x 128: FlexAttention's default block): coarser masks are expanded exactly to the
     kernel's 128 x 64 tiles. Every query block of every head needs at least one set tile (ValueError otherwise: no empty softmax rows
     exist). The lists are built with CPU ops and uploaded: call it once per mask, outside any graph capture."""
-    if not isinstance(mask, torch.Tensor) or mask.dtype != torch.bool:
-        raise TypeError(f"prepare_block_mask: the mask must be a torch.bool tensor, got "
-                        f"{mask.dtype if isinstance(mask, torch.Tensor) else type(mask).__name__}")
-    L, q_block, k_block = int(L), int(q_block), int(k_block)
-    if L <= 0:
-        raise ValueError(f"prepare_block_mask: L = {L} must be positive")
-    if q_block <= 0 or q_block % BS_Q_BLOCK or k_block <= 0 or k_block % BS_K_BLOCK:
-        raise ValueError(f"prepare_block_mask: q_block {q_block} must be a multiple of {BS_Q_BLOCK} and k_block {k_block} a multiple of "
-                         f"{BS_K_BLOCK} (the kernel's tile is {BS_Q_BLOCK} queries x {BS_K_BLOCK} keys)")
-    if mask.dim() not in (2, 3):
-        raise ValueError(f"prepare_block_mask: the mask must be [nqb, nkb] or [H, nqb, nkb], got shape {tuple(mask.shape)}")
-    want = (-(-L // q_block), -(-L // k_block))
-    if tuple(mask.shape[-2:]) != want:
-        raise ValueError(f"prepare_block_mask: mask shape {tuple(mask.shape)} does not belong to L = {L}: {q_block} x {k_block} blocks "
-                         f"need [..., {want[0]}, {want[1]}]")
-    if mask.dim() == 3 and mask.shape[0] < 1:
-        raise ValueError("prepare_block_mask: a per-head mask needs at least one head")
-    m = mask.detach().to("cpu")
-    m = m[None] if m.dim() == 2 else m
+    m, L = _expand_block_mask("prepare_block_mask", mask, L, q_block, k_block)
     nqb, nkb = -(-L // BS_Q_BLOCK), -(-L // BS_K_BLOCK)
-    m = m.repeat_interleave(q_block // BS_Q_BLOCK, dim=1)[:, :nqb].repeat_interleave(k_block // BS_K_BLOCK, dim=2)[:, :, :nkb].contiguous()
     cnt = m.sum(dim=2, dtype=torch.int32)
     if bool((cnt == 0).any()):
         hh, qq = (int(v) for v in (cnt == 0).nonzero()[0])
@@ -691,6 +702,61 @@ def attn_bs_plan(L, D=128, batch=1, H=1):
     if lib.uv_flash_attn_bs_plan(batch, L, H, D, buf, 96, ctypes.byref(qb), ctypes.byref(grid)) != 0:
         raise UnividHipError(lib.uv_last_error().decode())
     return dict(kernel=buf.value.decode(), q_blocks=qb.value, grid=grid.value)
+
+
+def prepare_keep_mask(mask, L, device, q_block=BS_Q_BLOCK, k_block=BS_K_BLOCK):
+    """The static keep mask of `attn_bs_select` at sequence length L: `prepare_block_mask`'s shapes and block expansion, but rows may be
+    empty (the selection adds its top-k tiles to every row). Returns (uint8 [heads, nqb, nkb] on `device`, the expanded bool mask on the
+    CPU). Built with CPU ops and uploaded: once per mask, outside any graph capture."""
+    m, _ = _expand_block_mask("prepare_keep_mask", mask, L, q_block, k_block)
+    return m.to(torch.uint8).to(torch.device(device)), m
+
+
+BS_SELECT_MAX_TILES = 4096      # uv_attn_bs_select sorts a row's key tiles in LDS
+
+
+def attn_pool_qk(q, k, qbar, kbar, L, H, D, batch=1):
+    """The pooled operands of the top-k tile selection: q, k bf16 [batch*L, >= H*D] (after RMSNorm + RoPE, as the attention kernel reads them)
+    -> qbar fp32 [batch, H, ceil(L / 128), D] and kbar fp32 [batch, H, ceil(L / 64), D], the fp32 mean of each 128-query block's / 64-key
+    tile's valid rows. head_dim 128 only."""
+    C = H * D
+    nqb, nkb = -(-L // BS_Q_BLOCK), -(-L // BS_K_BLOCK)
+    _check("attn_pool_qk", (q, "q", BF16, C, batch * L), (k, "k", BF16, C, batch * L), (qbar, "qbar", F32, batch * H * nqb * D),
+           (kbar, "kbar", F32, batch * H * nkb * D))
+    call("uv_attn_pool_qk", ptr(q), q.stride(-2), ptr(k), k.stride(-2), ptr(qbar), ptr(kbar), batch, L, H, D, stream_ptr())
+    return qbar, kbar
+
+
+def attn_bs_select(qbar, kbar, keep, top_k, tile_idx, tile_cnt, L, H, batch=1):
+    """The key-tile lists of `flash_attn_bs_lists` from pooled scores: per (sample, head, 128-query block) the tiles `keep` marks (uint8
+    [1 or H, nqb, nkb] on the device, or None) plus the `top_k` best of the others by s = qbar . kbar (score descending, tile index
+    ascending), written ascending into tile_idx int32 [batch, H, nqb, nkb] with their number in tile_cnt int32 [batch, H, nqb]. At most
+    BS_SELECT_MAX_TILES key tiles."""
+    nqb, nkb = -(-L // BS_Q_BLOCK), -(-L // BS_K_BLOCK)
+    keep_heads = 1
+    if keep is not None:
+        if keep.dim() != 3 or tuple(keep.shape[1:]) != (nqb, nkb):
+            raise UnividHipError(f"attn_bs_select.keep: expected uint8 [1 or {H}, {nqb}, {nkb}], got shape {tuple(keep.shape)}")
+        keep_heads = int(keep.shape[0])
+    _check("attn_bs_select", (qbar, "qbar", F32, batch * H * nqb * 128), (kbar, "kbar", F32, batch * H * nkb * 128),
+           (keep, "keep", U8, keep_heads * nqb * nkb, None, True), (tile_idx, "tile_idx", I32, batch * H * nqb * nkb),
+           (tile_cnt, "tile_cnt", I32, batch * H * nqb))
+    call("uv_attn_bs_select", ptr(qbar), ptr(kbar), ptr(keep), keep_heads, int(top_k), ptr(tile_idx), ptr(tile_cnt), batch, L, H, stream_ptr())
+    return tile_idx, tile_cnt
+
+
+def flash_attn_bs_lists(q, k, vt, out, L, H, D, scale, tile_idx, tile_cnt, mask_heads, mask_samples, batch=1):
+    """`flash_attn_bs` under raw lists on the device with a leading sample axis: tile_idx int32 [mask_samples, mask_heads, nqb, nkb],
+    tile_cnt int32 [mask_samples, mask_heads, nqb] (`prepare_block_mask`'s format; `attn_bs_select` writes them); mask_samples 1 (shared
+    by the samples, `flash_attn_bs` exactly) or batch, mask_heads 1 or H."""
+    C = H * D
+    nqb, nkb = -(-L // BS_Q_BLOCK), -(-L // BS_K_BLOCK)
+    rows = max(int(mask_samples), 0) * max(int(mask_heads), 0) * nqb
+    _check("flash_attn_bs_lists", (q, "q", BF16, C, batch * L), (k, "k", BF16, C, batch * L), (vt, "vt", BF16, vt_cols(batch, L), C),
+           (out, "out", BF16, C, batch * L), (tile_idx, "tile_idx", I32, rows * nkb), (tile_cnt, "tile_cnt", I32, rows))
+    call("uv_flash_attn_bs_lists_bf16", ptr(q), q.stride(-2), ptr(k), k.stride(-2), ptr(vt), vt.stride(-2), ptr(out), out.stride(-2), batch, L,
+         H, D, float(scale), ptr(tile_idx), ptr(tile_cnt), int(mask_heads), int(mask_samples), stream_ptr())
+    return out
 
 
 def flash_attn_mxqk(q_codes, q_scales, k_codes, k_scales, vt, out, Lq, Lk, H, D, scale, batch=1):

@@ -8,7 +8,8 @@
 //
 // Query i of head h attends key j iff mask[h][i / 128][j / 64] and j < L. Exact: the same softmax over fewer keys. The mask arrives as a tile
 // SCHEDULE prepared once per mask (univid_amd/_lib.py: prepare_block_mask): tile_idx [Hm, nqb, nkb] holds each (mask head, query block)'s visible
-// 64-key tiles in ascending order, tile_cnt [Hm, nqb] how many, Hm = 1 (shared by the heads) or H; the samples of a stacked launch share it.
+// 64-key tiles in ascending order, tile_cnt [Hm, nqb] how many, Hm = 1 (shared by the heads) or H; the samples of a stacked launch share it
+// (uv_flash_attn_bs_bf16) or bring one set of lists each, a leading sample axis (uv_flash_attn_bs_lists_bf16: attention_sel.hip builds them).
 //
 // One 4-wave workgroup per (sample, head, 128-query block) in flash_attn_fwd3_kernel's XCD-contiguous id order, flash_attn_win4_kernel's
 // staging (K and V^T both double-buffered, 64 KiB, one barrier per tile, uniform-base LDS-DMA pieces). It walks its LIST: the index of tile
@@ -60,15 +61,22 @@ __global__ __launch_bounds__(256, 2) void flash_attn_bs4_kernel(AttnBsArgs p) {
     const int bh = vb / p.q_blocks;
     const int qblk = vb - bh * p.q_blocks;
     const int head = bh % p.H;
-    attn_sample_offset<0>(p, bh / p.H);
+    const int sample = bh / p.H;
+    attn_sample_offset<0>(p, sample);
     const int q0w = (qblk * 4 + wave_u) * UV_ATT_QW;
     const long hcol = (long)head * D;
 
     // ---- this block's schedule: its row of the list, the clamped count
     const int nkb = p.nkb, nt_full = L / UV_ATT_KV;
-    const int row = (p.mask_heads == 1 ? 0 : head) * p.q_blocks + qblk;
+    const int row = ((p.mask_samples == 1 ? 0 : sample) * p.mask_heads + (p.mask_heads == 1 ? 0 : head)) * p.q_blocks + qblk;
     // the list and the counts are read through the constant address space: nothing writes them while the kernel runs, and a uniform read of
-    // it is a scalar load - which neither waits for the LDS-DMA pieces in flight (a vector load's vmcnt would) nor occupies a lane register
+    // it is a scalar load - which neither waits for the LDS-DMA pieces in flight (a vector load's vmcnt would) nor occupies a lane register.
+    // uv_flash_attn_bs_lists_bf16: ANOTHER KERNEL on the same stream (uv_attn_bs_select) wrote them just before. What the read rests on: that
+    // kernel has completed before this one's first wave starts (stream order: the dispatch packet's barrier bit), its plain vector stores
+    // were written back to the L2 at its end (the packet's release fence), and this kernel's dispatch starts with the packet's acquire
+    // fence, which invalidates the scalar data cache together with the vector L1 - HSA's kernel-boundary rule (LLVM's AMDGPU memory model:
+    // "kernel dispatch acquire"), the same one that makes any kernel's plain loads see its predecessor's stores; eager launches and HIP
+    // graph replays on one stream both keep it. Nothing inside a kernel would: a list written DURING this kernel could be read stale.
     typedef const __attribute__((address_space(4))) int* const_int_p;
     const const_int_p lst = (const_int_p)(p.tile_idx + (long)row * nkb);
     const int cnt = __builtin_amdgcn_readfirstlane(min(max(((const_int_p)p.tile_cnt)[row], 0), nkb));
@@ -309,10 +317,10 @@ extern "C" int uv_flash_attn_bs_plan(int batch, int L, int H, int head_dim, char
     return 0;
 }
 
-extern "C" int uv_flash_attn_bs_bf16(const void* q, long ldq, const void* k, long ldk, const void* vt, long ldvt, void* out, long ldo, int batch,
-                                     int L, int H, int head_dim, float softmax_scale, const int* tile_idx, const int* tile_cnt, int mask_heads,
-                                     void* stream) {
-    const char* name = "uv_flash_attn_bs_bf16";
+// Both entries: the checks, the argument block, the launch. mask_samples was checked by the caller.
+static int attn_bs_launch(const char* name, const void* q, long ldq, const void* k, long ldk, const void* vt, long ldvt, void* out, long ldo,
+                          int batch, int L, int H, int head_dim, float softmax_scale, const int* tile_idx, const int* tile_cnt, int mask_heads,
+                          int mask_samples, void* stream) {
     UV_CHECK_ARG(q && k && vt && out && tile_idx && tile_cnt, "%s: null pointer", name);
     UV_CHECK_ARG(head_dim == 128, "%s: head_dim %d unsupported (128 only)", name, head_dim);
     UV_CHECK_ARG(L > 0 && L <= (1 << 30) && H > 0 && batch > 0, "%s: bad shape B=%d L=%d H=%d", name, batch, L, H);
@@ -333,8 +341,25 @@ extern "C" int uv_flash_attn_bs_bf16(const void* q, long ldq, const void* k, lon
     a.scale_log2 = softmax_scale * 1.4426950408889634f;
     a.q_rs = nullptr; a.q_w = nullptr;
     a.q_blocks = plan.q_blocks; a.n12 = 0;
-    a.tile_idx = tile_idx; a.tile_cnt = tile_cnt; a.mask_heads = mask_heads; a.nkb = (L + UV_ATT_KV - 1) / UV_ATT_KV;
+    a.tile_idx = tile_idx; a.tile_cnt = tile_cnt; a.mask_heads = mask_heads; a.nkb = (L + UV_ATT_KV - 1) / UV_ATT_KV; a.mask_samples = mask_samples;
     hipLaunchKernelGGL(flash_attn_bs4_kernel, dim3(plan.grid), dim3(plan.block), 0, (hipStream_t)stream, a);
     UV_CHECK_LAUNCH(name);
     return 0;
+}
+
+extern "C" int uv_flash_attn_bs_bf16(const void* q, long ldq, const void* k, long ldk, const void* vt, long ldvt, void* out, long ldo, int batch,
+                                     int L, int H, int head_dim, float softmax_scale, const int* tile_idx, const int* tile_cnt, int mask_heads,
+                                     void* stream) {
+    return attn_bs_launch("uv_flash_attn_bs_bf16", q, ldq, k, ldk, vt, ldvt, out, ldo, batch, L, H, head_dim, softmax_scale, tile_idx, tile_cnt,
+                          mask_heads, 1, stream);
+}
+
+// The same kernel under lists with a leading sample axis (csrc/attention_sel.hip: uv_attn_bs_select writes them on the device).
+extern "C" int uv_flash_attn_bs_lists_bf16(const void* q, long ldq, const void* k, long ldk, const void* vt, long ldvt, void* out, long ldo,
+                                           int batch, int L, int H, int head_dim, float softmax_scale, const int* tile_idx, const int* tile_cnt,
+                                           int mask_heads, int mask_samples, void* stream) {
+    UV_CHECK_ARG(mask_samples == 1 || mask_samples == batch,
+                 "uv_flash_attn_bs_lists_bf16: mask_samples=%d must be 1 (the samples share the lists) or batch=%d", mask_samples, batch);
+    return attn_bs_launch("uv_flash_attn_bs_lists_bf16", q, ldq, k, ldk, vt, ldvt, out, ldo, batch, L, H, head_dim, softmax_scale, tile_idx,
+                          tile_cnt, mask_heads, mask_samples, stream);
 }

@@ -33,11 +33,13 @@ struct AttnWinArgs : AttnArgs {
 };
 
 // attention_bs.hip: AttnArgs (Lq == Lk, q_rs / q_w unused) plus the key-tile schedule of a block mask: per (mask head, 128-query block) the
-// ascending list of visible 64-key tiles and its length. mask_heads = 1 (one mask for all heads) or H.
+// ascending list of visible 64-key tiles and its length. mask_heads = 1 (one mask for all heads) or H; mask_samples = 1 (the samples of a
+// stacked launch share the lists: uv_flash_attn_bs_bf16) or batch (one set of lists per sample: uv_flash_attn_bs_lists_bf16).
 struct AttnBsArgs : AttnArgs {
-    const int* tile_idx;   // [mask_heads, q_blocks, nkb]  the first tile_cnt entries of a row are read, nothing else
-    const int* tile_cnt;   // [mask_heads, q_blocks]
+    const int* tile_idx;   // [mask_samples, mask_heads, q_blocks, nkb]  the first tile_cnt entries of a row are read, nothing else
+    const int* tile_cnt;   // [mask_samples, mask_heads, q_blocks]
     int mask_heads, nkb;   // nkb = ceil(L / 64)
+    int mask_samples;
 };
 
 enum AttnKernel { ATT_FWD12 = 0, ATT_FWD3 = 1, ATT_FWD_D128 = 2, ATT_FWD_D64 = 3, ATT_MXQK12 = 4, ATT_MXQK4 = 5, ATT_MXPV12 = 6, ATT_MXPV4 = 7,

@@ -58,7 +58,7 @@ class CrossAttentionConfig:
     vae_precision: Optional[str] = None   # "f16": the VAE's opt-in narrow arithmetic (WanVAE_.prepare; one fp16 pass where f16x3 takes three); None keeps the VAE's own mode ("f16x3")
     attn_precision: str = "bf16"  # "mxfp8_qk" / "mxfp8_qk_pv": the DiT's self-attention q / k (and P.V) as MXFP8 (WanModel.set_attn_precision), opt-in experimental modes
     attn_window: Optional[Tuple[int, int]] = None  # (left, right) tokens as flash-attn's window_size: sliding-window / causal DiT self-attention (WanModel.set_attn_window), opt-in, changes the model's function; None = what the checkpoint says (global)
-    attn_block_mask: Any = None  # a bool block mask / PreparedBlockMask / callable f(F, H, W, num_heads): block-sparse DiT self-attention (WanModel.set_attn_block_mask), opt-in, changes the model's function; None = global
+    attn_block_mask: Any = None  # a bool block mask / PreparedBlockMask / callable f(F, H, W, num_heads) / TopKBlockMask: block-sparse DiT self-attention (WanModel.set_attn_block_mask), opt-in, changes the model's function; None = global
     guidance_strength: float = 1.0
     bagel_cross_attn_layers: List[int] = None
     freeze_bagel: bool = True

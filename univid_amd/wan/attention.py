@@ -22,18 +22,23 @@ alignment for Lq != Lk, ragged `k_lens`, fp16 tensors and head size 64 under a w
 (`uv_flash_attn_bs_bf16`, csrc/attention_bs.hip): a `_lib.PreparedBlockMask` or a bool tensor [ceil(L / 128), ceil(L / 64)] / [N, ...]
 (prepared per call), query i of head h attending key j iff mask[h][i // 128][j // 64]. The window's restrictions apply, each refused with
 a message naming the limit: Lq == Lk, full `k_lens`, head size 128, bf16, and not beside `causal` / `window_size`. `video_block_mask`
-builds such a mask from a 3-D (frame, row, column) neighbourhood.
+builds such a mask from a 3-D (frame, row, column) neighbourhood. A `TopKBlockMask(top_k, keep=None)` in its place makes the lists
+DATA-DEPENDENT: per call, sample, head and 128-query block the `top_k` key tiles with the highest pooled q.k scores, beside the static
+`keep` tiles, are chosen on the device (`uv_attn_pool_qk`, `uv_attn_bs_select`, `uv_flash_attn_bs_lists_bf16`; csrc/attention_sel.hip) -
+the same restrictions, no host synchronisation.
 
 What the reference function accepts but UniVid never uses is rejected loudly instead of being computed wrongly:
 dropout, `q_scale`, grouped K/V heads, head sizes other than 64 / 128, and `q_lens` that
 differ from Lq (the reference itself cannot return those: its `.unflatten(0, (b, lq))` needs every q_len == Lq).
 There is no eager fallback: without the HIP extension or a gfx950 device the call raises.
 """
+import math
+
 import torch
 
 from .. import _lib
 
-__all__ = ["flash_attention", "attention", "video_block_mask"]
+__all__ = ["flash_attention", "attention", "video_block_mask", "TopKBlockMask"]
 
 _HALF = (torch.float16, torch.bfloat16)
 
@@ -60,6 +65,77 @@ def _lens(lens, b, full, name):
     return vals
 
 
+class TopKBlockMask:
+    """The spec of DATA-DEPENDENT block-sparse self-attention (the top-k tile selection of the training-free sparse-attention schemes for
+    video DiTs), accepted wherever a block mask is: per forward, sample, head and 128-query block i, the key tiles attended are the ones
+    `keep` marks plus the `top_k` best of the others by the pooled score s[i][j] = mean(q rows of block i) . mean(k rows of tile j) (fp32; q
+    and k after RMSNorm + RoPE; ties go to the lower tile index); fewer than `top_k` candidates: all of them. Chosen on the device, so it
+    runs inside a captured HIP graph and differs between the samples of a stacked forward.
+
+    top_k: an int >= 1, or a float in (0, 1] = that fraction of the sequence's ceil(L / 64) key tiles, rounded up. keep: None, a bool
+    tensor [ceil(L / q_block), ceil(L / k_block)] or [num_heads, ...] for ONE sequence length, or a callable f(F, H, W, num_heads) -> such
+    a mask for the patch grid (`video_block_mask` builds one); rows may be empty. Immutable."""
+    __slots__ = ("top_k", "keep", "q_block", "k_block")
+
+    def __init__(self, top_k, keep=None, *, q_block=128, k_block=64):
+        if isinstance(top_k, bool) or not isinstance(top_k, (int, float)):
+            raise TypeError(f"TopKBlockMask: top_k must be an int >= 1 or a float in (0, 1], got {type(top_k).__name__}")
+        if isinstance(top_k, int) and top_k < 1:
+            raise ValueError(f"TopKBlockMask: top_k = {top_k} must be >= 1")
+        if isinstance(top_k, float) and not 0.0 < top_k <= 1.0:
+            raise ValueError(f"TopKBlockMask: a float top_k is a fraction of the key tiles in (0, 1], got {top_k}")
+        if torch.is_tensor(keep):
+            if keep.dtype != torch.bool or keep.dim() not in (2, 3):
+                raise TypeError(f"TopKBlockMask: a tensor keep must be torch.bool [nqb, nkb] or [num_heads, nqb, nkb], got {keep.dtype} "
+                                f"{tuple(keep.shape)}")
+        elif keep is not None and not callable(keep):
+            raise TypeError(f"TopKBlockMask: keep must be None, a bool tensor or a callable f(F, H, W, num_heads), got {type(keep).__name__}")
+        q_block, k_block = int(q_block), int(k_block)
+        if q_block <= 0 or q_block % _lib.BS_Q_BLOCK or k_block <= 0 or k_block % _lib.BS_K_BLOCK:
+            raise ValueError(f"TopKBlockMask: q_block {q_block} must be a multiple of {_lib.BS_Q_BLOCK} and k_block {k_block} a multiple of "
+                             f"{_lib.BS_K_BLOCK}")
+        for name, v in (("top_k", top_k), ("keep", keep), ("q_block", q_block), ("k_block", k_block)):
+            object.__setattr__(self, name, v)
+
+    def __setattr__(self, name, value):
+        raise AttributeError("TopKBlockMask is immutable: build a new spec")
+
+    def __delattr__(self, name):
+        raise AttributeError("TopKBlockMask is immutable: build a new spec")
+
+    def count(self, L):
+        """The number of non-kept tiles listed per query block at sequence length L (before the cap at the candidates a row has)."""
+        nkb = -(-int(L) // _lib.BS_K_BLOCK)
+        if isinstance(self.top_k, int):
+            return self.top_k
+        return max(1, min(nkb, math.ceil(self.top_k * nkb)))
+
+    def __repr__(self):
+        keep = "None" if self.keep is None else (f"tensor{tuple(self.keep.shape)}" if torch.is_tensor(self.keep) else "callable")
+        return f"TopKBlockMask(top_k={self.top_k!r}, keep={keep})"
+
+
+def topk_attention(q, k, vt, out, L, H, D, scale, top_k, keep, batch, scratch=None):
+    """The three launches of self-attention under a TopKBlockMask on q / k as the attention kernel reads them (bf16 [batch*L, H*D]): pool,
+    select, attend. top_k: the resolved count; keep: uint8 [1 or H, nqb, nkb] on the device or None. scratch(tag, shape, dtype) supplies
+    qbar / kbar / the lists (the model: stable per-stream buffers, so a captured graph allocates nothing); default: fresh tensors."""
+    nqb, nkb = -(-L // _lib.BS_Q_BLOCK), -(-L // _lib.BS_K_BLOCK)
+    if nkb > _lib.BS_SELECT_MAX_TILES:
+        raise NotImplementedError(f"TopKBlockMask: L = {L} has {nkb} key tiles; the selection kernel sorts at most {_lib.BS_SELECT_MAX_TILES} "
+                                  f"(L <= {_lib.BS_SELECT_MAX_TILES * _lib.BS_K_BLOCK})")
+    if scratch is None:
+        def scratch(tag, shape, dtype):
+            return torch.empty(shape, dtype=dtype, device=q.device)
+    qbar = scratch("topk_qbar", (batch, H, nqb, D), torch.float32)
+    kbar = scratch("topk_kbar", (batch, H, nkb, D), torch.float32)
+    idx = scratch("topk_idx", (batch, H, nqb, nkb), torch.int32)
+    cnt = scratch("topk_cnt", (batch, H, nqb), torch.int32)
+    _lib.attn_pool_qk(q, k, qbar, kbar, L, H, D, batch=batch)
+    _lib.attn_bs_select(qbar, kbar, keep, top_k, idx, cnt, L, H, batch=batch)
+    _lib.flash_attn_bs_lists(q, k, vt, out, L, H, D, scale, idx, cnt, H, batch, batch=batch)
+    return idx, cnt
+
+
 def flash_attention(q, k, v, q_lens=None, k_lens=None, dropout_p=0., softmax_scale=None, q_scale=None, causal=False,
                     window_size=(-1, -1), deterministic=False, dtype=torch.bfloat16, version=None, *, block_mask=None):
     """Reference signature (attention.py:24-38). `deterministic` and `version` select nothing here: the kernel is always
@@ -79,7 +155,11 @@ def flash_attention(q, k, v, q_lens=None, k_lens=None, dropout_p=0., softmax_sca
     masked = block_mask is not None
     if masked and windowed:
         raise NotImplementedError("flash_attention: block_mask combined with causal / window_size is not built: fold the window into the mask")
-    if masked and not isinstance(block_mask, _lib.PreparedBlockMask) and not (torch.is_tensor(block_mask) and block_mask.dtype == torch.bool):
+    topk = isinstance(block_mask, TopKBlockMask)
+    if topk and callable(block_mask.keep):
+        raise TypeError("flash_attention: a TopKBlockMask whose keep is a callable needs a patch grid, which this call does not carry: pass "
+                        "keep as a bool tensor (video_block_mask builds it)")
+    if masked and not topk and not isinstance(block_mask, _lib.PreparedBlockMask) and not (torch.is_tensor(block_mask) and block_mask.dtype == torch.bool):
         raise TypeError(f"flash_attention: block_mask must be a PreparedBlockMask or a torch.bool tensor, got "
                         f"{block_mask.dtype if torch.is_tensor(block_mask) else type(block_mask).__name__}")
     if dropout_p:
@@ -122,7 +202,15 @@ def flash_attention(q, k, v, q_lens=None, k_lens=None, dropout_p=0., softmax_sca
                                   f"as WanModel.forward does")
     if masked and vh.dtype != torch.bfloat16:
         raise NotImplementedError("flash_attention: block_mask with fp16 tensors is not built (the block-sparse kernel is bf16)")
-    if masked:
+    if topk:
+        keep = None
+        if block_mask.keep is not None:
+            keep, keep_mask = _lib.prepare_keep_mask(block_mask.keep, lk, q.device, block_mask.q_block, block_mask.k_block)
+            if keep_mask.shape[0] not in (1, n):
+                raise ValueError(f"flash_attention: the TopKBlockMask's keep has {keep_mask.shape[0]} heads; this call has {n} (1 = shared "
+                                 f"by all heads)")
+        top_k = block_mask.count(lk)
+    elif masked:
         bm = block_mask if isinstance(block_mask, _lib.PreparedBlockMask) else _lib.prepare_block_mask(block_mask, lk, q.device)
         if bm.L != lk or bm.heads not in (1, n):
             raise ValueError(f"flash_attention: block_mask was prepared for L = {bm.L} and {bm.heads} head(s); this call has L = {lk} and "
@@ -144,6 +232,8 @@ def flash_attention(q, k, v, q_lens=None, k_lens=None, dropout_p=0., softmax_sca
             vt_of(v2[s * lk:(s + 1) * lk], lk, vt, s * lk)
         if windowed:
             _lib.flash_attn_win(q2, k2, vt, out.view(b * lq, C), lq, n, c, scale, window, batch=b)
+        elif topk:
+            topk_attention(q2, k2, vt, out.view(b * lq, C), lq, n, c, scale, top_k, keep, b)
         elif masked:
             _lib.flash_attn_bs(q2, k2, vt, out.view(b * lq, C), lq, n, c, scale, bm, batch=b)
         else:
@@ -155,6 +245,8 @@ def flash_attention(q, k, v, q_lens=None, k_lens=None, dropout_p=0., softmax_sca
             vt_of(v2[s * lk:s * lk + L], L, vt, 0)
             if windowed:        # (every k_len == Lk here: Lk % 8 != 0 at batch > 1)
                 _lib.flash_attn_win(q2[s * lq:(s + 1) * lq], k2[s * lk:s * lk + L], vt, out[s], lq, n, c, scale, window)
+            elif topk:
+                topk_attention(q2[s * lq:(s + 1) * lq], k2[s * lk:s * lk + L], vt, out[s], lq, n, c, scale, top_k, keep, 1)
             elif masked:
                 _lib.flash_attn_bs(q2[s * lq:(s + 1) * lq], k2[s * lk:s * lk + L], vt, out[s], lq, n, c, scale, bm)
             else:

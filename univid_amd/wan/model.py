@@ -27,6 +27,7 @@ import torch
 import torch.nn as nn
 
 from .. import _lib
+from .attention import TopKBlockMask, topk_attention
 from .._lib import (EPI_BF16, EPI_BF16_T, EPI_F32_FROM_BF16, EPI_GATE_RESID_F32, EPI_GELU_BF16, EPI_RESID_F32)
 
 __all__ = ["WanModel"]
@@ -157,16 +158,66 @@ class AttnBlockMask:
         return bm
 
 
+class AttnTopKMask:
+    """set_attn_block_mask's resolver of a TopKBlockMask (univid_amd.wan.attention): per patch grid the count of non-kept tiles a query
+    block lists and the static keep mask on the device. keep's tensor / callable forms resolve and cache exactly as AttnBlockMask's specs
+    do - a tensor belongs to one L, a callable is evaluated once per distinct (grid, device), and uploading inside a HIP-graph capture is
+    refused (WanTI2V's eager warm-up forward prepares it; `prepare(grid, device)` does so by hand). Without a keep mask nothing is
+    uploaded and every grid resolves anywhere. The lists themselves are built on the device in every forward."""
+
+    class Plan:
+        """One grid's resolved spec: top_k (int), keep (uint8 [1 or H, nqb, nkb] on the device, or None), mask (the expanded bool keep mask
+        on the CPU, or None), L."""
+        __slots__ = ("top_k", "keep", "mask", "L")
+
+        def __init__(self, top_k, keep, mask, L):
+            self.top_k, self.keep, self.mask, self.L = top_k, keep, mask, L
+
+    def __init__(self, spec, num_heads):
+        self.spec, self.num_heads, self._cache = spec, int(num_heads), {}
+
+    def prepared(self):
+        """{(grid or L, device): Plan} of what was resolved so far."""
+        return dict(self._cache)
+
+    def prepare(self, grid, device):
+        return self.resolve(tuple(int(g) for g in grid), math.prod(int(g) for g in grid), torch.device(device))
+
+    def resolve(self, grid, L, device):
+        spec = self.spec
+        key = (tuple(grid), device) if callable(spec.keep) else (L, device)
+        plan = self._cache.get(key)
+        if plan is None:
+            nkb = -(-L // _lib.BS_K_BLOCK)
+            if nkb > _lib.BS_SELECT_MAX_TILES:
+                raise NotImplementedError(f"attn_block_mask: L = {L} has {nkb} key tiles; the top-k selection kernel sorts at most "
+                                          f"{_lib.BS_SELECT_MAX_TILES} (L <= {_lib.BS_SELECT_MAX_TILES * _lib.BS_K_BLOCK})")
+            keep = mask = None
+            if spec.keep is not None:
+                if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+                    raise RuntimeError(f"attn_block_mask: the keep mask of patch grid {tuple(grid)} (L = {L}) was not prepared before this "
+                                       f"HIP-graph capture - run one eager forward at this grid, or AttnTopKMask.prepare(grid, device), first")
+                m = spec.keep if torch.is_tensor(spec.keep) else spec.keep(int(grid[0]), int(grid[1]), int(grid[2]), self.num_heads)
+                keep, mask = _lib.prepare_keep_mask(m, L, device, spec.q_block, spec.k_block)
+                if mask.shape[0] not in (1, self.num_heads):
+                    raise ValueError(f"attn_block_mask: a per-head keep mask needs {self.num_heads} heads, got {mask.shape[0]}")
+            plan = self._cache[key] = AttnTopKMask.Plan(spec.count(L), keep, mask, L)
+        return plan
+
+
 def _check_attn_block_mask(spec, head_dim=128, attn_precision="bf16", attn_window=None, num_heads=None):
     """set_attn_block_mask's guards, on one self-attention's geometry: raises before any state changes. Returns None (global attention) or
     the AttnBlockMask that resolves the spec."""
     if spec is None:
         return None
-    if isinstance(spec, AttnBlockMask):
+    if isinstance(spec, (AttnBlockMask, AttnTopKMask)):
         resolver, spec = spec, spec.spec
     else:
         resolver = None
-    if torch.is_tensor(spec):
+    topk = isinstance(spec, TopKBlockMask)
+    if topk:
+        heads = spec.keep.shape[0] if torch.is_tensor(spec.keep) and spec.keep.dim() == 3 else 1
+    elif torch.is_tensor(spec):
         if spec.dtype != torch.bool or spec.dim() not in (2, 3):
             raise TypeError(f"attn_block_mask: a tensor spec must be torch.bool [nqb, nkb] or [num_heads, nqb, nkb], got {spec.dtype} "
                             f"{tuple(spec.shape)}")
@@ -187,7 +238,9 @@ def _check_attn_block_mask(spec, head_dim=128, attn_precision="bf16", attn_windo
     if attn_window is not None:
         raise NotImplementedError(f"attn_block_mask with window_size {tuple(attn_window)}: one or the other - set_attn_window(None) first, "
                                   f"or fold the window into the mask")
-    return resolver if resolver is not None else AttnBlockMask(spec, num_heads if num_heads is not None else heads)
+    if resolver is not None:
+        return resolver
+    return (AttnTopKMask if topk else AttnBlockMask)(spec, num_heads if num_heads is not None else heads)
 
 
 def _check_ffn_precision(mode, dim, ffn_dim, ffn):
@@ -434,7 +487,13 @@ class WanSelfAttention(nn.Module):
             return _slotted(att, C, self._slots["o"], M, L, s0)
         if bm is not None:
             _lib.rmsnorm_rope_qk(ql, kl, self.norm_q.weight, self.norm_k.weight, M, L, C, D, self.eps, freqs, grid)
-            _lib.flash_attn_bs(ql, kl, vt, att, L, H, D, 1.0 / math.sqrt(D), bm, batch=batch)
+            if isinstance(bm, AttnTopKMask.Plan):
+                # the lists of THIS forward's q / k, per sample and head, built on the device into stable scratch: pool, select, attend -
+                # no host synchronisation, nothing allocated inside a captured forward
+                topk_attention(ql, kl, vt, att, L, H, D, 1.0 / math.sqrt(D), bm.top_k, bm.keep, batch,
+                               scratch=lambda tag, shape, dtype: _mx_scratch(tag, shape, dev, dtype))
+            else:
+                _lib.flash_attn_bs(ql, kl, vt, att, L, H, D, 1.0 / math.sqrt(D), bm, batch=batch)
             return _slotted(att, C, self._slots["o"], M, L, s0)
         if self.attn_precision != "bf16":
             # q and k leave the norm + RoPE pass as MXFP8 codes + scales (fresh buffers: no in-place form), S = K Q^T on the block-scaled
@@ -926,13 +985,14 @@ def _vt_scratch(tag, C, batch, L, device):
     return t
 
 
-def _mx_scratch(tag, shape, device):
+def _mx_scratch(tag, shape, device, dtype=torch.uint8):
     """uint8 scratch of the MXFP8 V^T (codes / scales of attn_precision "mxfp8_qk_pv"): stable per (tag, device, stream) like _vt_scratch, so
-    a captured graph keeps reading and writing the same memory; never zeroed (uv_vt_mx_quant writes every byte the attention reads)."""
+    a captured graph keeps reading and writing the same memory; never zeroed (uv_vt_mx_quant writes every byte the attention reads). Also
+    the pooled operands and lists of a TopKBlockMask (fp32 / int32; their kernels write everything the next one reads)."""
     key = (tag, device, torch.cuda.current_stream(device).cuda_stream)
     t, _ = _zero_cache.get(key, (None, None))
-    if t is None or tuple(t.shape) != tuple(shape) or (t.is_inference() and not torch.is_inference_mode_enabled()):
-        t = torch.empty(shape, dtype=torch.uint8, device=device)
+    if t is None or tuple(t.shape) != tuple(shape) or t.dtype != dtype or (t.is_inference() and not torch.is_inference_mode_enabled()):
+        t = torch.empty(shape, dtype=dtype, device=device)
     _zero_cache[key] = (t, None)
     return t
 
@@ -1152,7 +1212,10 @@ class WanModel(nn.Module):
         global attention (default); a bool tensor [ceil(L / 128), ceil(L / 64)] or [num_heads, ...] or a _lib.PreparedBlockMask, for ONE
         sequence length (a forward at another L raises); or a callable f(F, H, W, num_heads) -> such a bool mask for the patch grid
         (F, H, W), evaluated and prepared once per distinct grid and cached - in an eager forward: a forward inside a HIP-graph capture
-        at a grid that was not prepared raises (WanTI2V's warm-up forward prepares it). Opt-in: it CHANGES the model's function (exactly -
+        at a grid that was not prepared raises (WanTI2V's warm-up forward prepares it); or a univid_amd.wan.attention.TopKBlockMask(top_k,
+        keep=None): DATA-DEPENDENT lists - per forward, sample, head and 128-query block the top_k key tiles with the highest pooled q.k
+        scores, beside the static keep tiles, chosen on the device (uv_attn_pool_qk, uv_attn_bs_select, uv_flash_attn_bs_lists_bf16: no
+        host synchronisation, runs inside a captured HIP graph, differs between the cond and uncond samples). Opt-in: it CHANGES the model's function (exactly -
         the same softmax over fewer keys), it is not an approximation of global attention (README). Cross-attention is untouched.
         Needs head_dim 128, attn_precision "bf16" and no window_size (NotImplementedError otherwise; set_attn_precision refuses an MXFP8
         mode and set_attn_window a window while a mask is set); the sequence-parallel forward and the reference-signature

@@ -282,7 +282,7 @@ class WanTI2V:
             # attn_precision; None keeps what the model came with (its checkpoint's config.json, global attention unless it says otherwise)
             self.model.set_attn_window(attn_window)
         if attn_block_mask is not None:
-            # a bool mask / PreparedBlockMask / callable f(F, H, W, num_heads) (WanModel.set_attn_block_mask): opt-in block-sparse self-attention,
+            # a bool mask / PreparedBlockMask / callable f(F, H, W, num_heads) / TopKBlockMask (WanModel.set_attn_block_mask): opt-in block-sparse self-attention,
             # passed on like attn_window; None keeps the model as it came (global attention)
             self.model.set_attn_block_mask(attn_block_mask)
         if proj_precision is not None and proj_precision != self.model.proj_precision:
