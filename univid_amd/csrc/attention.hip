@@ -6,7 +6,8 @@
 //           q/k/v cast to bf16 :59-83, result cast back :130), called from
 //           WanSelfAttention.forward model.py:145-150 and WanCrossAttention.forward model.py:175.
 //
-// Three kernels share the operand layouts, LDS images and arithmetic below:
+// Three kernels share the operand layouts, LDS images and arithmetic below (fwd12 / fwd3: the per-wave pieces of attn_args.h, which the windowed,
+// block-sparse and MXFP8-q/k kernels call too):
 //   flash_attn_fwd12_kernel  head_dim 128, bf16, Lk >= 2048 (self-attention): one 12-wave workgroup per CU, up to 384 queries per K/V^T stream
 //   flash_attn_fwd3_kernel   head_dim 128, bf16, shorter Lk (cross-attention): three 4-wave workgroups per CU (48 KiB LDS, <= 168 registers)
 //   flash_attn_fwd_kernel    head_dim 64 / fp16 operands / very large leading dimensions: two 4-wave workgroups per CU (the first design)
@@ -336,7 +337,8 @@ __global__ __launch_bounds__(256, 2) void flash_attn_fwd_kernel(AttnArgs p) {
 // A lone wave needs ~3 440 cycles per tile of which 1 024 are MFMA issue; two waves per SIMD overlap almost perfectly
 // (3 500 cycles per PAIR of tiles), i.e. the chain is latency- not throughput-bound and a third wave has room.
 // ------------------------------------------------------------------------------------------------------------------------
-// glds16_sbase (one LDS-DMA piece from a uniform base pointer) and UV_ATT_AHEAD: attn_args.h, shared with attention_win.hip
+// The per-half pieces (attn_qk_half, attn_softmax_half, attn_pv_half, attn_mask_ragged) and glds16_sbase (one LDS-DMA piece from a uniform base
+// pointer): attn_args.h. This kernel keeps what is its own between them: the 48 KiB staging, the waits and the 272-byte O images.
 template <int QN = 0>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void flash_attn_fwd3_kernel(AttnArgs p) {
     constexpr int D = 128, NW = 4, KROW = 256, NKK = 8, ND = 4;
@@ -412,7 +414,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
     };
 
     // fragment read addresses (LDS byte offsets from smem; buffer / key-half / d-tile offsets are instruction immediates)
-    typedef const __attribute__((address_space(3))) bf16x8* lds_frag_p;
     const unsigned smem_a = (unsigned)(uintptr_t)(lds_void_a*)smem;
     unsigned kaddr[NKK];
     unsigned vaddr[2][2];
@@ -447,8 +448,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
     // PAR = -1: the GENERIC form of the tail tiles (parity, "is the next tile full" and "is this the ragged tile" decided at run time).
     // Until round 4 the tail was five compile-time instantiations behind an if / else chain; hipcc allocated registers across that chain
     // and SPILLED 380 of them to scratch (444 bytes per lane; none in the main loop) - and 2 of the cross-attention's 8 tiles ran there.
-    // One generic instantiation in a loop of its own keeps the tail at the main loop's register footprint (8 spilled registers, none
-    // in a loop): the cross-attention launch 193.9 -> 165.8 us (two builds of the library in one process, tools/attn_so_ab.py), bit-identical.
+    // One generic instantiation in a loop of its own keeps the tail at the main loop's register footprint (168 registers, no spilled
+    // one, no scratch): the cross-attention launch 193.9 -> 165.8 us (two builds of the library in one process, tools/attn_so_ab.py), bit-identical.
     auto tile = [&](int t, auto masked_tag, auto next_tag, auto par_tag) {
         constexpr bool DYN = decltype(par_tag)::value < 0;
         constexpr bool MASKED_C = decltype(masked_tag)::value;
@@ -462,22 +463,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
         bool k_pending = true;
 #pragma unroll
         for (int T = 0; T < 2; ++T) {
-            f32x16 sacc;
-#pragma unroll
-            for (int e = 0; e < 16; ++e) sacc[e] = 0.f;
-#pragma unroll
-            for (int kk = 0; kk < NKK; ++kk) {
-                const bf16x8 kf = *(lds_frag_p)(kaddr[kk] + PAR * K_BYTES + T * 32 * KROW);
-                sacc = mfma_32x32x16<false>(kf, qf[kk], sacc);
-            }
-            __builtin_amdgcn_sched_group_barrier(0x100, UV_ATT_AHEAD, 0);      // fragment reads UV_ATT_AHEAD ahead of their MFMAs
-#pragma unroll
-            for (int i_ = 0; i_ < 8 - UV_ATT_AHEAD; ++i_) {
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-            }
-            __builtin_amdgcn_sched_group_barrier(0x008, UV_ATT_AHEAD, 0);
-            __builtin_amdgcn_sched_barrier(0);
+            f32x16 sacc = attn_qk_half(kaddr, qf, PAR * K_BYTES + T * 32 * KROW);
             if (T == 0) {
                 // K(t+1) into the other K buffer (every wave left tile t-1, its last reader, before the barrier that opened tile t)
                 if constexpr (NEXT_FULL) {
@@ -488,66 +474,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
                     else k_pending = false;
                 }
             }
-            if (MASKED) {
-#pragma unroll
-                for (int e = 0; e < 16; ++e) {
-                    const int i = 32 * T + (e & 3) + 8 * (e >> 2) + 4 * h;
-                    if (kv0 + perm23(i) >= p.Lk) sacc[e] = -INFINITY;
-                }
-            }
-            float mt = sacc[0];
-#pragma unroll
-            for (int e = 1; e < 16; ++e) mt = fmaxf(mt, sacc[e]);
-            {
-                const unsigned u = __builtin_bit_cast(unsigned, mt);
-                const auto sw = __builtin_amdgcn_permlane32_swap(u, u, false, false);
-                mt = fmaxf(__builtin_bit_cast(float, (unsigned)sw[0]), __builtin_bit_cast(float, (unsigned)sw[1]));
-            }
-            const float grow = (mt - m_run) * p.scale_log2;
-            if (__any(grow > UV_ATT_DEFER)) {
-                const float m_new = fmaxf(m_run, mt);
-                const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * p.scale_log2);
-                l_run *= alpha;
-#pragma unroll
-                for (int d = 0; d < ND; ++d)
-#pragma unroll
-                    for (int e = 0; e < 16; ++e) oacc[d][e] *= alpha;
-                m_run = m_new;
-            }
-            const float mneg = -m_run * p.scale_log2;
-            float psum = 0.f;
+            if (MASKED) attn_mask_ragged(sacc, kv0, T, h, p.Lk);
             bf16x8 pf[2];
-#pragma unroll
-            for (int s2 = 0; s2 < 2; ++s2)
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const float pv = __builtin_amdgcn_exp2f(__builtin_fmaf(sacc[8 * s2 + j], p.scale_log2, mneg));
-                    psum += pv;
-                    pf[s2][j] = (__bf16)pv;
-                }
-            l_run += psum;
+            attn_softmax_half<false>(sacc, 0u, p.scale_log2, m_run, l_run, oacc, pf);
             if (T == 0) {
                 // V^T(t) of every wave has landed: the K(t+1) pieces were issued after it and may stay in flight
                 if (k_pending) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
                 else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 __builtin_amdgcn_s_barrier();
             }
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int d = 0; d < ND; ++d)
-#pragma unroll
-                for (int s2 = 0; s2 < 2; ++s2) {
-                    const bf16x8 vf = *(lds_frag_p)(vaddr[T][s2] + d * 32 * 128);
-                    oacc[d] = mfma_32x32x16<false>(vf, pf[s2], oacc[d]);
-                }
-            __builtin_amdgcn_sched_group_barrier(0x100, UV_ATT_AHEAD, 1);
-#pragma unroll
-            for (int i_ = 0; i_ < 8 - UV_ATT_AHEAD; ++i_) {
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 1);
-                __builtin_amdgcn_sched_group_barrier(0x100, 1, 1);
-            }
-            __builtin_amdgcn_sched_group_barrier(0x008, UV_ATT_AHEAD, 1);
-            __builtin_amdgcn_sched_barrier(0);
+            attn_pv_half(vaddr[T], 0, pf, oacc);
         }
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");          // this wave's share of K(t+1); own LDS reads retired
         __builtin_amdgcn_s_barrier();
@@ -665,49 +601,13 @@ __global__ __launch_bounds__(768) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
     AttnQNorm<NKK, QN> qnorm;
     attn_load_q<NKK, QN>(p, qf, qnorm, min(q0w + r, p.Lq - 1), hcol, h);
 
-    // The 32 pieces of a tile (K pieces 0..15 = 4 LDS rows each, V^T pieces 0..15 = 8 rows each) are dealt round-robin: wave w
-    // issues K piece w, K piece w + 12 (w < 4), V^T piece w - 4 (w >= 4) and V^T piece w + 8 (w < 8). Pieces 12 apart (K) / of equal
-    // parity (V^T) share the swizzle key and the row permutation bits, so one lane offset per operand serves both.
-    const int s4 = lane >> 4, s8 = lane >> 3;
-    unsigned koff, voff;
-    {
-        const int p3 = wave_u & 3;
-        const int c = (lane & 15) ^ ((4 * p3 + s4) & 15);
-        const int swap2 = ((p3 & 1) << 1) | (p3 >> 1);
-        koff = (unsigned)((s4 + 4 * swap2) * (int)p.ldk + c * 8) * 2u;
-        const int cv = (lane & 7) ^ ((4 * (wave_u & 1) + (s8 >> 1)) & 7);
-        voff = (unsigned)(s8 * (int)p.ldvt + cv * 8) * 2u;
-    }
+    // staging: AttnStage (attn_args.h) with running base pointers; the ragged last tile (or a lone short tile) clamps its K rows to Lk - 1
+    const unsigned smem_a = (unsigned)(uintptr_t)(lds_void_a*)smem;
+    AttnStage<NW> stage(smem_a, wave_u, lane, p.ldk, p.ldvt);
     const char* kbase = (const char*)(p.k + hcol);
     const char* vbase = (const char*)(p.vt + hcol * p.ldvt);
     const long kstep = (long)UV_ATT_KV * p.ldk * 2;
-    const long k16 = 16 * p.ldk * 2, v8 = 8 * p.ldvt * 2;
-    const unsigned smem_a = (unsigned)(uintptr_t)(lds_void_a*)smem;
-    const int kp0 = wave_u, kp1 = wave_u + 12;                // K pieces (kp1 only for wave < 4)
-    const int vq0 = wave_u - 4, vq1 = wave_u + 8;             // V^T pieces (vq0 for wave >= 4, vq1 for wave < 8)
-    auto fetch_full = [&](const char* kb_t, const char* vb_t, int buf) {
-        glds16_sbase(kb_t + (kp0 >> 2) * k16, koff, smem_a + buf * K_BYTES + kp0 * 1024);
-        if (wave_u < 4) glds16_sbase(kb_t + (kp1 >> 2) * k16, koff, smem_a + buf * K_BYTES + kp1 * 1024);
-        if (wave_u >= 4) glds16_sbase(vb_t + vq0 * v8, voff, smem_a + V_OFF + buf * V_BYTES + vq0 * 1024);
-        if (wave_u < 8) glds16_sbase(vb_t + vq1 * v8, voff, smem_a + V_OFF + buf * V_BYTES + vq1 * 1024);
-    };
-    auto fetch_clamped = [&](int kv0, const char* vb_t, int buf) {      // ragged last tile / lone short tile: clamped K rows
-#pragma unroll
-        for (int w = 0; w < 2; ++w) {
-            const int pc = w ? kp1 : kp0;
-            if (pc < 16) {
-                const int lrow = 4 * pc + s4;
-                const int c = (lane & 15) ^ (lrow & 15);
-                const int kr = min(kv0 + perm23(lrow), p.Lk - 1);
-                const bf16_t* src = p.k + hcol + (long)kr * p.ldk + c * 8;
-                __builtin_amdgcn_global_load_lds(src, (lds_void_a*)(smem + buf * K_BYTES + pc * 1024), 16, 0, 0);
-            }
-        }
-        if (wave_u >= 4) glds16_sbase(vb_t + vq0 * v8, voff, smem_a + V_OFF + buf * V_BYTES + vq0 * 1024);
-        if (wave_u < 8) glds16_sbase(vb_t + vq1 * v8, voff, smem_a + V_OFF + buf * V_BYTES + vq1 * 1024);
-    };
 
-    typedef const __attribute__((address_space(3))) bf16x8* lds_frag_p;
     unsigned kaddr[NKK];
     unsigned vaddr[2][2];
     attn_frag_addrs(smem_a, V_OFF, r, h, kaddr, vaddr);
@@ -721,15 +621,15 @@ __global__ __launch_bounds__(768) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
 
     const int nt = (p.Lk + UV_ATT_KV - 1) / UV_ATT_KV;
     const int nt_full = p.Lk / UV_ATT_KV;
-    if (nt_full > 0) fetch_full(kbase, vbase, 0);
-    else fetch_clamped(0, vbase, 0);
+    if (nt_full > 0) stage.full(kbase, vbase, 0);
+    else stage.clamped(kbase, vbase, p.Lk - 1, 0);
     attn_apply_qnorm<NKK, QN>(qf, qnorm);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #pragma unroll
     for (int kk = 0; kk < NKK; ++kk) asm volatile("" : "+v"(qf[kk]), "+v"(kaddr[kk]));
 #pragma unroll
     for (int i = 0; i < 4; ++i) asm volatile("" : "+v"(vaddr[i >> 1][i & 1]));
-    asm volatile("" : "+v"(koff), "+v"(voff));
+    asm volatile("" : "+v"(stage.koff), "+v"(stage.voff));
     __syncthreads();
     UV_TL(blockIdx.x, 1);
 
@@ -738,8 +638,8 @@ __global__ __launch_bounds__(768) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
         for (int t = 0; t < nt; ++t) {
             vbase += 2 * UV_ATT_KV;
             kbase += kstep;
-            if (t + 1 < nt_full) fetch_full(kbase, vbase, (t & 1) ^ 1);
-            else if (t + 1 < nt) fetch_clamped((t + 1) * UV_ATT_KV, vbase, (t & 1) ^ 1);
+            if (t + 1 < nt_full) stage.full(kbase, vbase, (t & 1) ^ 1);
+            else if (t + 1 < nt) stage.clamped(kbase, vbase, p.Lk - 1 - (t + 1) * UV_ATT_KV, (t & 1) ^ 1);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();
         }
@@ -749,7 +649,7 @@ __global__ __launch_bounds__(768) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
     // PAR = -1: the generic form of the tail tiles (see flash_attn_fwd3_kernel). Here the if / else chain of five instantiations spilled
     // 315 registers (408 bytes of scratch per lane) in the last two or three tiles of every workgroup: ~150 MB of scratch writes per
     // batch-2 launch at L = 11 440 - HALF of what rocprofv3's WRITE_SIZE reported for this kernel (287 640 KB against 137 280 KB of
-    // output; tools/diag/attn_write_probe.*). With the generic tail: 1 spilled register, the launch time unchanged (2.740 against 2.742 ms;
+    // output; tools/diag/attn_write_probe.*). With the generic tail: 166 registers, none spilled, the launch time unchanged (2.740 against 2.742 ms;
     // three tiles of 179 per workgroup), bit-identical.
     auto tile = [&](int t, auto masked_tag, auto next_tag, auto par_tag) {
         constexpr bool DYN = decltype(par_tag)::value < 0;
@@ -761,83 +661,18 @@ __global__ __launch_bounds__(768) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
         vbase += 2 * UV_ATT_KV;
         kbase += kstep;
         if constexpr (NEXT_FULL) {
-            fetch_full(kbase, vbase, PAR ^ 1);
+            stage.full(kbase, vbase, PAR ^ 1);
         } else {
-            if (t + 1 < nt_full) fetch_full(kbase, vbase, PAR ^ 1);
-            else if (t + 1 < nt) fetch_clamped(kv0 + UV_ATT_KV, vbase, PAR ^ 1);
+            if (t + 1 < nt_full) stage.full(kbase, vbase, PAR ^ 1);
+            else if (t + 1 < nt) stage.clamped(kbase, vbase, p.Lk - 1 - kv0 - UV_ATT_KV, PAR ^ 1);
         }
 #pragma unroll
         for (int T = 0; T < 2; ++T) {
-            f32x16 sacc;
-#pragma unroll
-            for (int e = 0; e < 16; ++e) sacc[e] = 0.f;
-#pragma unroll
-            for (int kk = 0; kk < NKK; ++kk) {
-                const bf16x8 kf = *(lds_frag_p)(kaddr[kk] + PAR * K_BYTES + T * 32 * KROW);
-                sacc = mfma_32x32x16<false>(kf, qf[kk], sacc);
-            }
-            __builtin_amdgcn_sched_group_barrier(0x100, UV_ATT_AHEAD, 0);
-#pragma unroll
-            for (int i_ = 0; i_ < 8 - UV_ATT_AHEAD; ++i_) {
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-            }
-            __builtin_amdgcn_sched_group_barrier(0x008, UV_ATT_AHEAD, 0);
-            __builtin_amdgcn_sched_barrier(0);
-            if (MASKED) {
-#pragma unroll
-                for (int e = 0; e < 16; ++e) {
-                    const int i = 32 * T + (e & 3) + 8 * (e >> 2) + 4 * h;
-                    if (kv0 + perm23(i) >= p.Lk) sacc[e] = -INFINITY;
-                }
-            }
-            float mt = sacc[0];
-#pragma unroll
-            for (int e = 1; e < 16; ++e) mt = fmaxf(mt, sacc[e]);
-            {
-                const unsigned u = __builtin_bit_cast(unsigned, mt);
-                const auto sw = __builtin_amdgcn_permlane32_swap(u, u, false, false);
-                mt = fmaxf(__builtin_bit_cast(float, (unsigned)sw[0]), __builtin_bit_cast(float, (unsigned)sw[1]));
-            }
-            const float grow = (mt - m_run) * p.scale_log2;
-            if (__any(grow > UV_ATT_DEFER)) {
-                const float m_new = fmaxf(m_run, mt);
-                const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * p.scale_log2);
-                l_run *= alpha;
-#pragma unroll
-                for (int d = 0; d < ND; ++d)
-#pragma unroll
-                    for (int e = 0; e < 16; ++e) oacc[d][e] *= alpha;
-                m_run = m_new;
-            }
-            const float mneg = -m_run * p.scale_log2;
-            float psum = 0.f;
+            f32x16 sacc = attn_qk_half(kaddr, qf, PAR * K_BYTES + T * 32 * KROW);
+            if (MASKED) attn_mask_ragged(sacc, kv0, T, h, p.Lk);
             bf16x8 pf[2];
-#pragma unroll
-            for (int s2 = 0; s2 < 2; ++s2)
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const float pv = __builtin_amdgcn_exp2f(__builtin_fmaf(sacc[8 * s2 + j], p.scale_log2, mneg));
-                    psum += pv;
-                    pf[s2][j] = (__bf16)pv;
-                }
-            l_run += psum;
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int d = 0; d < ND; ++d)
-#pragma unroll
-                for (int s2 = 0; s2 < 2; ++s2) {
-                    const bf16x8 vf = *(lds_frag_p)(vaddr[T][s2] + PAR * V_BYTES + d * 32 * 128);
-                    oacc[d] = mfma_32x32x16<false>(vf, pf[s2], oacc[d]);
-                }
-            __builtin_amdgcn_sched_group_barrier(0x100, UV_ATT_AHEAD, 1);
-#pragma unroll
-            for (int i_ = 0; i_ < 8 - UV_ATT_AHEAD; ++i_) {
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 1);
-                __builtin_amdgcn_sched_group_barrier(0x100, 1, 1);
-            }
-            __builtin_amdgcn_sched_group_barrier(0x008, UV_ATT_AHEAD, 1);
-            __builtin_amdgcn_sched_barrier(0);
+            attn_softmax_half<false>(sacc, 0u, p.scale_log2, m_run, l_run, oacc, pf);
+            attn_pv_half(vaddr[T], PAR * V_BYTES, pf, oacc);
         }
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
@@ -860,35 +695,9 @@ __global__ __launch_bounds__(768) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
     const float inv = 1.0f / l_tot;
     const int q = q0w + r;
     if ((p.ldo & 7) == 0) {
-        // O through LDS (as in flash_attn_fwd3_kernel), in two passes of two d-blocks each: twelve wave-private images of 32 rows x
-        // (128 + 16) bytes fit the 64 KiB that held K / V^T (free: the last tile ended on a barrier that the loader-only waves took too);
-        // every store instruction writes 8 whole 128-byte lines (self-attention at the DiT shape 2.724 -> 2.711 ms in a same-device A/B,
-        // bit-identical).
-        constexpr int RS = 144;
-        char* const img = smem + wave_u * (32 * RS);
-        const int srow = lane >> 3, chunk = lane & 7;
-#pragma unroll
-        for (int half = 0; half < 2; ++half) {
-#pragma unroll
-            for (int dd = 0; dd < 2; ++dd)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const int d = 2 * half + dd;
-                    u32x2 o = {pack16_2<false>(oacc[d][4 * g + 0] * inv, oacc[d][4 * g + 1] * inv),
-                               pack16_2<false>(oacc[d][4 * g + 2] * inv, oacc[d][4 * g + 3] * inv)};
-                    *(u32x2*)(img + r * RS + 64 * dd + 16 * g + 8 * h) = o;
-                }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // wave-private image: no barrier
-            u32x4 v[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) v[i] = *(const u32x4*)(img + (8 * i + srow) * RS + chunk * 16);
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the second pass overwrites the image
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int row = 8 * i + srow;
-                if (q0w + row < p.Lq) *(u32x4*)(p.out + (long)(q0w + row) * p.ldo + hcol + 64 * half + chunk * 8) = v[i];
-            }
-        }
+        // O through LDS: twelve wave-private images of 32 rows x (128 + 16) bytes fit the 64 KiB that held K / V^T (free: the last tile ended
+        // on a barrier that the loader-only waves took too)
+        attn_store_lds(smem + wave_u * (32 * 144), p.out + (long)q0w * p.ldo + hcol, p.ldo, p.Lq - q0w, lane, oacc, inv);
     } else if (q < p.Lq) {
         attn_store_direct<false, ND>(p.out + (long)q * p.ldo + hcol + 4 * h, oacc, inv);
     }

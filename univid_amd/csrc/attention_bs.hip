@@ -22,23 +22,13 @@
 // NO LIST CONTENT READS OUTSIDE k / V^T: the count is clamped into [0, nkb]; an entry that is not the list's last is clamped into the FULL
 // tiles [0, L / 64 - 1] (a valid list holds the ragged tile last or not at all), the last entry into [0, nkb - 1] and fetched by what it is.
 // A block whose clamped count is 0 (the host refuses such masks) leaves before its first fetch and before any barrier and writes zero rows.
-// Everything else is flash_attn_fwd12_kernel's arithmetic operation for operation (32-key halves, UV_ATT_DEFER, order within a tile, bf16
-// rounding of P, 1 / l, padded query rows as duplicates of row L - 1, O through LDS when ldo % 8 == 0): a query's bits depend on its 32-query
-// unit and on the ascending list of tiles it visits, on nothing else - the all-ones mask reproduces the dense launch bit for bit, and a block's
-// result is the dense kernels' on K / V gathered to its tiles.
+// The per-wave arithmetic of a half is the dense kernels' own code (attn_args.h: attn_qk_half, attn_softmax_half, attn_pv_half; the staging is
+// AttnStage<4>, the O stores attn_store_lds / attn_store_direct; padded query rows are duplicates of row L - 1): a query's bits depend on its
+// 32-query unit and on the ascending list of tiles it visits, on nothing else - the all-ones mask reproduces the dense launch bit for bit, and a
+// block's result is the dense kernels' on K / V gathered to its tiles.
 #include "attn_args.h"
 #include <stdio.h>
 #include <type_traits>
-
-#define UV_WIN_UNSET (-1.0e30f)      // attention_win.hip's finite "unset maximum" / masked score
-
-// The lane id, produced HERE (two VALU instructions, volatile: not hoisted): the rare branches and the epilogue derive their lane constants from
-// it instead of keeping them in registers across the tile loops (attention_win.hip: they were spilled there).
-__device__ __forceinline__ int bs_lane_here() {
-    int l;
-    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
-    return l;
-}
 
 constexpr int UV_BS_SMEM = 2 * UV_ATT_KV * 256 + 2 * 128 * 128;      // K and V^T double-buffered: 64 KiB (>= 4 O images of 32 x 144 B)
 
@@ -82,7 +72,7 @@ __global__ __launch_bounds__(256, 2) void flash_attn_bs4_kernel(AttnBsArgs p) {
     const int cnt = __builtin_amdgcn_readfirstlane(min(max(((const_int_p)p.tile_cnt)[row], 0), nkb));
     if (cnt == 0) {
         // nothing to attend (refused by the host; a corrupt count): zero rows, no fetch, no barrier
-        const int ln = bs_lane_here();
+        const int ln = attn_lane_here();
         const int qr = q0w + (ln & 31);
         if (qr < L) {
             bf16_t* op = p.out + (long)qr * p.ldo + hcol + 64 * (ln >> 5);
@@ -104,56 +94,18 @@ __global__ __launch_bounds__(256, 2) void flash_attn_bs4_kernel(AttnBsArgs p) {
     AttnQNorm<NKK, 0> qnorm;
     attn_load_q<NKK, 0>(p, qf, qnorm, qm, hcol, h);
 
-    // ---- staging (flash_attn_win4_kernel's): the 32 one-KiB pieces of a tile (K pieces 0..15 = 4 LDS rows each, V^T pieces 0..15 = 8 rows
-    // each) are dealt round-robin over the 4 waves: K and V^T pieces w, w + 4, w + 8, w + 12 share the swizzle key and the row permutation
-    // bits, so ONE lane offset per operand serves all of a wave's pieces; the piece's row / column step goes into the uniform base.
-    const int s4 = lane >> 4, s8 = lane >> 3;
-    unsigned koff, voff;
-    {
-        const int p3 = wave_u & 3;
-        const int c = (lane & 15) ^ ((4 * p3 + s4) & 15);
-        const int swap2 = ((p3 & 1) << 1) | (p3 >> 1);
-        koff = (unsigned)((s4 + 4 * swap2) * (int)p.ldk + c * 8) * 2u;
-        const int cv = (lane & 7) ^ ((4 * (wave_u & 1) + (s8 >> 1)) & 7);
-        voff = (unsigned)(s8 * (int)p.ldvt + cv * 8) * 2u;
-    }
+    // ---- staging: AttnStage (attn_args.h), the tile's base computed from its index; the ragged last tile clamps its K rows to L - 1
+    const unsigned smem_a = (unsigned)(uintptr_t)(lds_void_a*)smem;
+    AttnStage<4> stage(smem_a, wave_u, lane, p.ldk, p.ldvt);
     const long kstep = (long)UV_ATT_KV * p.ldk * 2;
-    const long k16 = 16 * p.ldk * 2, v8 = 8 * p.ldvt * 2;
     const char* khead = (const char*)(p.k + hcol);                     // tile t: + t kstep
     const char* vhead = (const char*)(p.vt + hcol * p.ldvt);           // tile t: + 128 t bytes
-    const unsigned smem_a = (unsigned)(uintptr_t)(lds_void_a*)smem;
-    auto fetch_v = [&](const char* vb_t, int buf) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) glds16_sbase(vb_t + (wave_u + 4 * i) * v8, voff, smem_a + V_OFF + buf * V_BYTES + (wave_u + 4 * i) * 1024);
-    };
-    auto fetch_full = [&](int t, int buf) {
-        const char* kb_t = khead + t * kstep;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) glds16_sbase(kb_t + i * k16, koff, smem_a + buf * K_BYTES + (wave_u + 4 * i) * 1024);
-        fetch_v(vhead + (long)t * 2 * UV_ATT_KV, buf);
-    };
-    // the ragged last tile: K rows clamped to L - 1 in the lane offset (the row inside the tile is 16 (pc >> 2) + the lane's row of its 16)
-    auto fetch_clamped = [&](int t, int buf) {
-        const char* kb_t = khead + t * kstep;
-        const int last = L - 1 - t * UV_ATT_KV;
-        const int p3 = wave_u & 3;
-        const int ln = bs_lane_here();
-        const int r4 = ln >> 4;
-        const int krl = r4 + 4 * (((p3 & 1) << 1) | (p3 >> 1));
-        const unsigned c16 = (unsigned)(((ln & 15) ^ ((4 * p3 + r4) & 15)) << 4);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int pc = wave_u + 4 * i;
-            glds16_sbase(kb_t, (unsigned)(min(16 * (pc >> 2) + krl, last) * (int)p.ldk) * 2u + c16, smem_a + buf * K_BYTES + pc * 1024);
-        }
-        fetch_v(vhead + (long)t * 2 * UV_ATT_KV, buf);
-    };
+    auto fetch_full = [&](int t, int buf) { stage.full(khead + t * kstep, vhead + (long)t * 2 * UV_ATT_KV, buf); };
     auto fetch_any = [&](int t, int buf) {
         if (t < nt_full) fetch_full(t, buf);
-        else fetch_clamped(t, buf);
+        else stage.clamped(khead + t * kstep, vhead + (long)t * 2 * UV_ATT_KV, L - 1 - t * UV_ATT_KV, buf);
     };
 
-    typedef const __attribute__((address_space(3))) bf16x8* lds_frag_p;
     unsigned kaddr[NKK];
     unsigned vaddr[2][2];
     attn_frag_addrs(smem_a, V_OFF, r, h, kaddr, vaddr);
@@ -172,7 +124,7 @@ __global__ __launch_bounds__(256, 2) void flash_attn_bs4_kernel(AttnBsArgs p) {
     for (int kk = 0; kk < NKK; ++kk) asm volatile("" : "+v"(qf[kk]), "+v"(kaddr[kk]));      // every prologue load has landed before the loops
 #pragma unroll
     for (int i = 0; i < 4; ++i) asm volatile("" : "+v"(vaddr[i >> 1][i & 1]));
-    asm volatile("" : "+v"(koff), "+v"(voff));
+    asm volatile("" : "+v"(stage.koff), "+v"(stage.voff));
     __syncthreads();
 
     // One staged tile: entry n of the list, tile t, its successor t_next. par_tag >= 0: a FULL tile in the buffer of that parity whose successor
@@ -190,22 +142,7 @@ __global__ __launch_bounds__(256, 2) void flash_attn_bs4_kernel(AttnBsArgs p) {
         const int kv0 = t * UV_ATT_KV;
 #pragma unroll
         for (int T = 0; T < 2; ++T) {
-            f32x16 sacc;
-#pragma unroll
-            for (int e = 0; e < 16; ++e) sacc[e] = 0.f;
-#pragma unroll
-            for (int kk = 0; kk < NKK; ++kk) {
-                const bf16x8 kf = *(lds_frag_p)(kaddr[kk] + PAR * K_BYTES + T * 32 * KROW);
-                sacc = mfma_32x32x16<false>(kf, qf[kk], sacc);
-            }
-            __builtin_amdgcn_sched_group_barrier(0x100, UV_ATT_AHEAD, 0);
-#pragma unroll
-            for (int i_ = 0; i_ < 8 - UV_ATT_AHEAD; ++i_) {
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-            }
-            __builtin_amdgcn_sched_group_barrier(0x008, UV_ATT_AHEAD, 0);
-            __builtin_amdgcn_sched_barrier(0);
+            f32x16 sacc = attn_qk_half(kaddr, qf, PAR * K_BYTES + T * 32 * KROW);
             // visibility of the half's 16 accumulator rows: register e holds key kv0 + 32 T + 8 h + (e & 3) + 4 ((e >> 2) & 1) + 16 (e >> 3)
             // (perm23 of the accumulator row); visible iff it is below L
             unsigned vis = 0xffffu;
@@ -220,54 +157,9 @@ __global__ __launch_bounds__(256, 2) void flash_attn_bs4_kernel(AttnBsArgs p) {
                     sacc[e] = ok ? sacc[e] : UV_WIN_UNSET;
                 }
             }
-            float mt = sacc[0];
-#pragma unroll
-            for (int e = 1; e < 16; ++e) mt = fmaxf(mt, sacc[e]);
-            {
-                const unsigned u = __builtin_bit_cast(unsigned, mt);
-                const auto sw = __builtin_amdgcn_permlane32_swap(u, u, false, false);
-                mt = fmaxf(__builtin_bit_cast(float, (unsigned)sw[0]), __builtin_bit_cast(float, (unsigned)sw[1]));
-            }
-            const float grow = (mt - m_run) * p.scale_log2;      // ~1e30 scale at the first tile, 0 while a ragged half holds no key
-            if (__any(grow > UV_ATT_DEFER)) {
-                const float m_new = fmaxf(m_run, mt);
-                const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * p.scale_log2);
-                l_run *= alpha;
-#pragma unroll
-                for (int d = 0; d < ND; ++d)
-#pragma unroll
-                    for (int e = 0; e < 16; ++e) oacc[d][e] *= alpha;
-                m_run = m_new;
-            }
-            const float mneg = -m_run * p.scale_log2;
-            float psum = 0.f;
             bf16x8 pf[2];
-#pragma unroll
-            for (int s2 = 0; s2 < 2; ++s2)
-#pragma unroll
-                for (int jj = 0; jj < 8; ++jj) {
-                    float pv = __builtin_amdgcn_exp2f(__builtin_fmaf(sacc[8 * s2 + jj], p.scale_log2, mneg));
-                    if constexpr (DYN) pv = ((vis >> (8 * s2 + jj)) & 1u) ? pv : 0.f;      // a masked element's P is selected, not computed
-                    psum += pv;
-                    pf[s2][jj] = (__bf16)pv;
-                }
-            l_run += psum;
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int d = 0; d < ND; ++d)
-#pragma unroll
-                for (int s2 = 0; s2 < 2; ++s2) {
-                    const bf16x8 vf = *(lds_frag_p)(vaddr[T][s2] + PAR * V_BYTES + d * 32 * 128);
-                    oacc[d] = mfma_32x32x16<false>(vf, pf[s2], oacc[d]);
-                }
-            __builtin_amdgcn_sched_group_barrier(0x100, UV_ATT_AHEAD, 1);
-#pragma unroll
-            for (int i_ = 0; i_ < 8 - UV_ATT_AHEAD; ++i_) {
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 1);
-                __builtin_amdgcn_sched_group_barrier(0x100, 1, 1);
-            }
-            __builtin_amdgcn_sched_group_barrier(0x008, UV_ATT_AHEAD, 1);
-            __builtin_amdgcn_sched_barrier(0);
+            attn_softmax_half<DYN>(sacc, vis, p.scale_log2, m_run, l_run, oacc, pf);      // generic form: a masked element's P is selected to 0
+            attn_pv_half(vaddr[T], PAR * V_BYTES, pf, oacc);
         }
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
@@ -296,7 +188,7 @@ __global__ __launch_bounds__(256, 2) void flash_attn_bs4_kernel(AttnBsArgs p) {
 
     const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
     const float inv = 1.0f / l_tot;
-    const int lane_e = bs_lane_here();
+    const int lane_e = attn_lane_here();
     if ((p.ldo & 7) == 0) {
         // O through LDS: wave-private images over the K / V^T buffers (free: the last tile ended on a barrier that every wave took)
         attn_store_lds(smem + wave_u * (32 * 144), p.out + (long)q0w * p.ldo + hcol, p.ldo, L - q0w, lane_e, oacc, inv);
@@ -321,17 +213,10 @@ extern "C" int uv_flash_attn_bs_plan(int batch, int L, int H, int head_dim, char
 static int attn_bs_launch(const char* name, const void* q, long ldq, const void* k, long ldk, const void* vt, long ldvt, void* out, long ldo,
                           int batch, int L, int H, int head_dim, float softmax_scale, const int* tile_idx, const int* tile_cnt, int mask_heads,
                           int mask_samples, void* stream) {
-    UV_CHECK_ARG(q && k && vt && out && tile_idx && tile_cnt, "%s: null pointer", name);
-    UV_CHECK_ARG(head_dim == 128, "%s: head_dim %d unsupported (128 only)", name, head_dim);
-    UV_CHECK_ARG(L > 0 && L <= (1 << 30) && H > 0 && batch > 0, "%s: bad shape B=%d L=%d H=%d", name, batch, L, H);
+    UV_CHECK_ARG(tile_idx && tile_cnt, "%s: null pointer", name);
+    if (attn_self_check_shape(name, q, k, vt, out, batch, L, H, head_dim)) return -1;
     UV_CHECK_ARG(mask_heads == 1 || mask_heads == H, "%s: mask_heads=%d must be 1 (one mask for all heads) or H=%d", name, mask_heads, H);
-    UV_CHECK_ARG(ldq % 8 == 0 && ldk % 8 == 0 && ldvt % 8 == 0 && ldo % 4 == 0, "%s: leading dimensions must be multiples of 8 elements", name);
-    UV_CHECK_ARG(ldvt >= (long)(batch - 1) * L + (long)((L + 63) / 64) * 64,
-                 "%s: ldvt=%ld must cover (batch-1)*L + L rounded up to 64 (batch=%d L=%d)", name, ldvt, batch, L);
-    UV_CHECK_ARG(batch == 1 || L % 8 == 0, "%s: batch > 1 needs L %% 8 == 0 (L=%d)", name, L);
-    // the LDS-DMA pieces are addressed with 32-bit lane offsets from a uniform base
-    UV_CHECK_ARG(128 * ldvt < (1L << 30) && 64 * ldk < (1L << 30), "%s: ldk=%ld / ldvt=%ld too large for 32-bit piece offsets", name, ldk, ldvt);
-    UV_CHECK_ARG((((uintptr_t)q | (uintptr_t)k | (uintptr_t)vt | (uintptr_t)out) & 15) == 0, "%s: pointers must be 16-byte aligned", name);
+    if (attn_self_check_layout(name, q, k, vt, out, ldq, ldk, ldvt, ldo, batch, L)) return -1;
     UV_CHECK_ARG((((uintptr_t)tile_idx | (uintptr_t)tile_cnt) & 3) == 0, "%s: tile_idx / tile_cnt must be 4-byte aligned", name);
     const AttnPlan plan = plan_attn_bs(batch, L, H);
     AttnBsArgs a;

@@ -6,8 +6,9 @@
 //
 // S^T = K.Q^T runs on the block-scaled matrix instruction v_mfma_scale_f32_32x32x64_f8f6f4: two instructions per 32-key half (head-dim
 // elements 0..63, then 64..127, into the same accumulator: every S element is ONE chain) in place of eight 32x32x16 bf16 ones, on 128-byte K rows.
-// The instruction's C/D layout is the 32x32 one of the bf16 form, so the rest of a tile is flash_attn_fwd12_kernel's: masking with the true key
-// index, the deferred reference maximum reconsidered per 32-key half, exp2, P as the B operand of O^T = V^T.P^T in bf16, O through LDS.
+// The instruction's C/D layout is the 32x32 one of the bf16 form, so the rest of a tile is the bf16 kernels' own code (attn_args.h): masking with the
+// true key index (attn_mask_ragged), the deferred reference maximum reconsidered per 32-key half, exp2 and P in bf16 as the B operand of
+// O^T = V^T.P^T (attn_softmax_half), O through LDS (attn_store_lds).
 //
 // Operand lane map of the instruction with 8-bit elements, MEASURED with exact integer data (one-hot e4m3 codes against per-lane scale bytes;
 // tests/test_attn_mxqk.py keeps it pinned through the kernel): lane l = (row / column r = l & 31, half h = l >> 5) holds K-index bytes
@@ -193,45 +194,10 @@ __device__ __forceinline__ void mxqk_body(AttnMxArgs p, char* smem) {
                 for (int e = 0; e < 16; ++e) sacc[e] = 0.f;
                 sacc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(kf[0], qf[0], sacc, 0, 0, 0, ksc, 0, qsc);
                 sacc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(kf[1], qf[1], sacc, 0, 0, 2, ksc, 2, qsc);
-                if (masked) {
-#pragma unroll
-                    for (int e = 0; e < 16; ++e) {
-                        const int i = 32 * T + (e & 3) + 8 * (e >> 2) + 4 * h;
-                        if (kv0 + perm23(i) >= p.Lk) sacc[e] = -INFINITY;
-                    }
-                }
-                // ---- online softmax of the half (flash_attn_fwd12_kernel's, operation for operation)
-                float mt = sacc[0];
-#pragma unroll
-                for (int e = 1; e < 16; ++e) mt = fmaxf(mt, sacc[e]);
-                {
-                    const unsigned u = __builtin_bit_cast(unsigned, mt);
-                    const auto sw = __builtin_amdgcn_permlane32_swap(u, u, false, false);
-                    mt = fmaxf(__builtin_bit_cast(float, (unsigned)sw[0]), __builtin_bit_cast(float, (unsigned)sw[1]));
-                }
-                const float grow = (mt - m_run) * p.scale_log2;
-                if (__any(grow > UV_ATT_DEFER)) {
-                    const float m_new = fmaxf(m_run, mt);
-                    const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * p.scale_log2);
-                    l_run *= alpha;
-#pragma unroll
-                    for (int d = 0; d < ND; ++d)
-#pragma unroll
-                        for (int e = 0; e < 16; ++e) oacc[d][e] *= alpha;
-                    m_run = m_new;
-                }
-                const float mneg = -m_run * p.scale_log2;
-                float psum = 0.f;
+                if (masked) attn_mask_ragged(sacc, kv0, T, h, p.Lk);
+                // ---- online softmax of the half: the bf16 kernels' (attn_args.h)
                 bf16x8 pf[2];
-#pragma unroll
-                for (int s2 = 0; s2 < 2; ++s2)
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) {
-                        const float pv = __builtin_amdgcn_exp2f(__builtin_fmaf(sacc[8 * s2 + j], p.scale_log2, mneg));
-                        psum += pv;
-                        pf[s2][j] = (__bf16)pv;
-                    }
-                l_run += psum;
+                attn_softmax_half<false>(sacc, 0u, p.scale_log2, m_run, l_run, oacc, pf);
                 // ---- O^T += V^T . P^T
 #pragma unroll
                 for (int d = 0; d < ND; ++d)
@@ -251,33 +217,8 @@ __device__ __forceinline__ void mxqk_body(AttnMxArgs p, char* smem) {
     const float inv = 1.0f / l_tot;
     const int q = q0w + r;
     if ((p.ldo & 7) == 0) {
-        // O through LDS as in flash_attn_fwd12_kernel: wave-private images of 32 rows x (128 + 16) bytes over the stages (free: the last tile
-        // ended on a barrier every wave took), two passes of two d-blocks; every store instruction writes 8 whole 128-byte lines
-        constexpr int RS = 144;
-        char* const img = smem + wave_u * (32 * RS);
-        const int srow = lane >> 3, chunk = lane & 7;
-#pragma unroll
-        for (int half = 0; half < 2; ++half) {
-#pragma unroll
-            for (int dd = 0; dd < 2; ++dd)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const int d = 2 * half + dd;
-                    u32x2 o = {pack16_2<false>(oacc[d][4 * g + 0] * inv, oacc[d][4 * g + 1] * inv),
-                               pack16_2<false>(oacc[d][4 * g + 2] * inv, oacc[d][4 * g + 3] * inv)};
-                    *(u32x2*)(img + r * RS + 64 * dd + 16 * g + 8 * h) = o;
-                }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // wave-private image: no barrier
-            u32x4 v[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) v[i] = *(const u32x4*)(img + (8 * i + srow) * RS + chunk * 16);
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the second pass overwrites the image
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int row = 8 * i + srow;
-                if (q0w + row < p.Lq) *(u32x4*)(p.out + (long)(q0w + row) * p.ldo + hcol + 64 * half + chunk * 8) = v[i];
-            }
-        }
+        // O through LDS: wave-private images over the stages (free: the last tile ended on a barrier every wave took)
+        attn_store_lds(smem + wave_u * (32 * 144), p.out + (long)q0w * p.ldo + hcol, p.ldo, p.Lq - q0w, lane, oacc, inv);
     } else if (q < p.Lq) {
         attn_store_direct<false, ND>(p.out + (long)q * p.ldo + hcol + 4 * h, oacc, inv);
     }

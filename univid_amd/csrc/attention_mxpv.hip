@@ -198,7 +198,7 @@ __device__ __forceinline__ void mxpv_body(AttnMxPvArgs p, char* smem) {
                 for (int e = 0; e < 16; ++e) sacc[T][e] = 0.f;
                 sacc[T] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(kf[0], qf[0], sacc[T], 0, 0, 0, ksc, 0, qsc);
                 sacc[T] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(kf[1], qf[1], sacc[T], 0, 0, 2, ksc, 2, qsc);
-                if (masked) {
+                if (masked) {      // its own copy of attn_mask_ragged (attn_args.h): through the shared one flash_attn_mxpv4_kernel takes 248 registers for 244
 #pragma unroll
                     for (int e = 0; e < 16; ++e) {
                         const int i = 32 * T + (e & 3) + 8 * (e >> 2) + 4 * h;
@@ -266,8 +266,8 @@ __device__ __forceinline__ void mxpv_body(AttnMxPvArgs p, char* smem) {
     const float inv = 1.0f / l_tot;
     const int q = q0w + r;
     if ((p.ldo & 7) == 0) {
-        // O through LDS as in flash_attn_fwd12_kernel: wave-private images of 32 rows x (128 + 16) bytes over the stages (free: the last tile
-        // ended on a barrier every wave took), two passes of two d-blocks; every store instruction writes 8 whole 128-byte lines
+        // O through LDS: its own copy of attn_store_lds (attn_args.h) over the stages (free: the last tile ended on a barrier every wave took).
+        // Through the shared one flash_attn_mxpv12_kernel measured 2 086 - 2 095 us for 2 051 - 2 054 (L = 11 440, B 2; profiles/attn_shared_pieces.md)
         constexpr int RS = 144;
         char* const img = smem + wave_u * (32 * RS);
         const int srow = lane >> 3, chunk = lane & 7;

@@ -15,14 +15,11 @@
 //   edge      everything else: per-element mask with the TRUE key index (kv0 + perm23(i) in the K.Q^T accumulator layout) against the lane's
 //             query; lanes of padded query rows (q >= L) are duplicates of row L - 1, mask included
 // EMPTY ROWS IN AN EDGE HALF: a lane's query can have no visible key in a 32-key half while its reference maximum is still unset (left = 100:
-// the wave's last query sees nothing of the first tile its first query needs). The dense kernels' -INFINITY scheme would compute -inf - -inf
-// there. Here the "unset" maximum and a masked score are the FINITE sentinel UV_WIN_UNSET, and P of a masked element is SELECTED to 0 by the
-// visibility bit, not computed: such a lane gets mt = unset, grow = 0 (no move of its own), alpha = exp2(0) = 1 exactly if a neighbour moves,
-// P = 0, l += 0, and its maximum stays unset until its first visible key (then alpha = exp2(-1e30 scale) = 0 on l = 0, O = 0 - what the dense
-// kernels compute from -inf).
-// Everything else is flash_attn_fwd12_kernel's arithmetic operation for operation (32-key halves, UV_ATT_DEFER, order within a tile, bf16
-// rounding of P, 1 / l): a window that covers every key reproduces the dense launch bit for bit, and a query's bits depend on its 32-query unit
-// only, never on the query-block cut, the form or the other queries of the launch.
+// the wave's last query sees nothing of the first tile its first query needs). The "unset" maximum and a masked score are therefore the FINITE
+// sentinel UV_WIN_UNSET, and P of a masked element is SELECTED to 0 by its visibility bit (attn_args.h: UV_WIN_UNSET, attn_softmax_half<true>).
+// The online softmax of a half is the dense kernels' own code (attn_args.h: attn_softmax_half; the staging and the O stores too) and the QK^T / P.V
+// loops around it are attn_qk_half's / attn_pv_half's statements: a window that covers every key reproduces the dense launch bit for bit, and a
+// query's bits depend on its 32-query unit only, never on the query-block cut, the form or the other queries of the launch.
 //
 // One body in two forms (plan_attn_win, attn_args.h, decides):
 //   flash_attn_win12_kernel  a workgroup's key span >= 2048: flash_attn_fwd12_kernel's 12-wave workgroup - 12 / 8 unit query blocks, loader-only
@@ -36,16 +33,6 @@
 #include "attn_args.h"
 #include <stdio.h>
 #include <type_traits>
-
-#define UV_WIN_UNSET (-1.0e30f)
-
-// The lane id, produced HERE (two VALU instructions, volatile: not hoisted): the rare branches and the epilogue derive their lane constants from it
-// instead of keeping them - or the lane id itself - in registers across the tile loops, where they were spilled.
-__device__ __forceinline__ int win_lane_here() {
-    int l;
-    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
-    return l;
-}
 
 template <int NW>
 __device__ __forceinline__ void win_body(AttnWinArgs p, char* smem) {
@@ -113,62 +100,13 @@ __device__ __forceinline__ void win_body(AttnWinArgs p, char* smem) {
     AttnQNorm<NKK, 0> qnorm;
     attn_load_q<NKK, 0>(p, qf, qnorm, qm, hcol, h);
 
-    // ---- staging (flash_attn_fwd12_kernel's): the 32 one-KiB pieces of a tile (K pieces 0..15 = 4 LDS rows each, V^T pieces 0..15 = 8 rows
-    // each) are dealt round-robin over the waves. K pieces of equal pc & 3 share the swizzle key and the row permutation bits, V^T pieces of
-    // equal parity the swizzle key: at 12 waves (K w, w + 12; V^T w - 4, w + 8) and at 4 (K and V^T w, w + 4, w + 8, w + 12) ONE lane offset
-    // per operand serves all of a wave's pieces; the piece's row / column step goes into the uniform base.
-    const int s4 = lane >> 4, s8 = lane >> 3;
-    unsigned koff, voff;
-    {
-        const int p3 = wave_u & 3;
-        const int c = (lane & 15) ^ ((4 * p3 + s4) & 15);
-        const int swap2 = ((p3 & 1) << 1) | (p3 >> 1);
-        koff = (unsigned)((s4 + 4 * swap2) * (int)p.ldk + c * 8) * 2u;
-        const int cv = (lane & 7) ^ ((4 * (wave_u & 1) + (s8 >> 1)) & 7);
-        voff = (unsigned)(s8 * (int)p.ldvt + cv * 8) * 2u;
-    }
+    // ---- staging: AttnStage (attn_args.h) with this kernel's running base pointers; the ragged last tile clamps its K rows to L - 1
+    const unsigned smem_a = (unsigned)(uintptr_t)(lds_void_a*)smem;
+    AttnStage<NW> stage(smem_a, wave_u, lane, p.ldk, p.ldvt);
     const long kstep = (long)UV_ATT_KV * p.ldk * 2;
-    const long k16 = 16 * p.ldk * 2, v8 = 8 * p.ldvt * 2;
     const char* kbase = (const char*)(p.k + hcol) + t_lo * kstep;                          // tile t_lo; += kstep per tile
     const char* vbase = (const char*)(p.vt + hcol * p.ldvt) + (long)t_lo * 2 * UV_ATT_KV;  // += 128 B per tile
-    const unsigned smem_a = (unsigned)(uintptr_t)(lds_void_a*)smem;
-    auto fetch_v = [&](const char* vb_t, int buf) {
-        if constexpr (NW == 12) {
-            const int vq0 = wave_u - 4, vq1 = wave_u + 8;
-            if (wave_u >= 4) glds16_sbase(vb_t + vq0 * v8, voff, smem_a + V_OFF + buf * V_BYTES + vq0 * 1024);
-            if (wave_u < 8) glds16_sbase(vb_t + vq1 * v8, voff, smem_a + V_OFF + buf * V_BYTES + vq1 * 1024);
-        } else {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) glds16_sbase(vb_t + (wave_u + 4 * i) * v8, voff, smem_a + V_OFF + buf * V_BYTES + (wave_u + 4 * i) * 1024);
-        }
-    };
-    auto fetch_full = [&](const char* kb_t, const char* vb_t, int buf) {
-        if constexpr (NW == 12) {
-            glds16_sbase(kb_t + (wave_u >> 2) * k16, koff, smem_a + buf * K_BYTES + wave_u * 1024);
-            if (wave_u < 4) glds16_sbase(kb_t + 3 * k16, koff, smem_a + buf * K_BYTES + (wave_u + 12) * 1024);
-        } else {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) glds16_sbase(kb_t + i * k16, koff, smem_a + buf * K_BYTES + (wave_u + 4 * i) * 1024);
-        }
-        fetch_v(vb_t, buf);
-    };
-    // the ragged last tile: K rows clamped to L - 1 in the lane offset (the row inside the tile is 16 (pc >> 2) + the lane's row of its 16)
-    auto fetch_clamped = [&](int kv0, const char* kb_t, const char* vb_t, int buf) {
-        const int last = L - 1 - kv0;
-        const int p3 = wave_u & 3;
-        const int ln = win_lane_here();
-        const int r4 = ln >> 4;
-        const int krl = r4 + 4 * (((p3 & 1) << 1) | (p3 >> 1));
-        const unsigned c16 = (unsigned)(((ln & 15) ^ ((4 * p3 + r4) & 15)) << 4);
-#pragma unroll
-        for (int i = 0; i < (NW == 12 ? 2 : 4); ++i) {
-            const int pc = wave_u + NW * i;
-            if (pc < 16) glds16_sbase(kb_t, (unsigned)(min(16 * (pc >> 2) + krl, last) * (int)p.ldk) * 2u + c16, smem_a + buf * K_BYTES + pc * 1024);
-        }
-        fetch_v(vb_t, buf);
-    };
 
-    typedef const __attribute__((address_space(3))) bf16x8* lds_frag_p;
     unsigned kaddr[NKK];
     unsigned vaddr[2][2];
     attn_frag_addrs(smem_a, V_OFF, r, h, kaddr, vaddr);
@@ -181,14 +119,14 @@ __device__ __forceinline__ void win_body(AttnWinArgs p, char* smem) {
     float m_run = UV_WIN_UNSET, l_run = 0.f;
 
     const int nt_full = L / UV_ATT_KV;
-    if (t_lo < nt_full) fetch_full(kbase, vbase, 0);
-    else fetch_clamped(t_lo * UV_ATT_KV, kbase, vbase, 0);
+    if (t_lo < nt_full) stage.full(kbase, vbase, 0);
+    else stage.clamped(kbase, vbase, L - 1 - t_lo * UV_ATT_KV, 0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #pragma unroll
     for (int kk = 0; kk < NKK; ++kk) asm volatile("" : "+v"(qf[kk]), "+v"(kaddr[kk]));      // every prologue load has landed before the loops
 #pragma unroll
     for (int i = 0; i < 4; ++i) asm volatile("" : "+v"(vaddr[i >> 1][i & 1]));
-    asm volatile("" : "+v"(koff), "+v"(voff));
+    asm volatile("" : "+v"(stage.koff), "+v"(stage.voff));
     __syncthreads();
 
     if (!compute_wave) {
@@ -197,8 +135,8 @@ __device__ __forceinline__ void win_body(AttnWinArgs p, char* smem) {
             kbase += kstep;
             const int nbuf = ((t - t_lo) & 1) ^ 1;
             if (t < t_hi) {
-                if (t + 1 < nt_full) fetch_full(kbase, vbase, nbuf);
-                else fetch_clamped((t + 1) * UV_ATT_KV, kbase, vbase, nbuf);
+                if (t + 1 < nt_full) stage.full(kbase, vbase, nbuf);
+                else stage.clamped(kbase, vbase, L - 1 - (t + 1) * UV_ATT_KV, nbuf);
             }
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();
@@ -215,16 +153,19 @@ __device__ __forceinline__ void win_body(AttnWinArgs p, char* smem) {
         vbase += 2 * UV_ATT_KV;
         kbase += kstep;
         if constexpr (!DYN) {
-            fetch_full(kbase, vbase, PAR ^ 1);
+            stage.full(kbase, vbase, PAR ^ 1);
         } else if (t < t_hi) {
-            if (t + 1 < nt_full) fetch_full(kbase, vbase, PAR ^ 1);
-            else fetch_clamped(kv0 + UV_ATT_KV, kbase, vbase, PAR ^ 1);
+            if (t + 1 < nt_full) stage.full(kbase, vbase, PAR ^ 1);
+            else stage.clamped(kbase, vbase, L - 1 - kv0 - UV_ATT_KV, PAR ^ 1);
         }
         const bool active = !DYN || (t >= w_lo && t <= w_hi);
         const bool edge = DYN && !(t >= i_lo && t <= i_hi);
         if (active) {
 #pragma unroll
             for (int T = 0; T < 2; ++T) {
+                // its own copies of attn_qk_half / attn_pv_half and their attn_reads_ahead ladders (attn_args.h), the same statements: through the
+                // shared ones flash_attn_win12_kernel measured 0.6 - 0.9 % slower on whole sequences, outside the run-to-run spread
+                // (profiles/attn_shared_pieces.md)
                 f32x16 sacc;
 #pragma unroll
                 for (int e = 0; e < 16; ++e) sacc[e] = 0.f;
@@ -255,38 +196,8 @@ __device__ __forceinline__ void win_body(AttnWinArgs p, char* smem) {
                         sacc[e] = ok ? sacc[e] : UV_WIN_UNSET;
                     }
                 }
-                float mt = sacc[0];
-#pragma unroll
-                for (int e = 1; e < 16; ++e) mt = fmaxf(mt, sacc[e]);
-                {
-                    const unsigned u = __builtin_bit_cast(unsigned, mt);
-                    const auto sw = __builtin_amdgcn_permlane32_swap(u, u, false, false);
-                    mt = fmaxf(__builtin_bit_cast(float, (unsigned)sw[0]), __builtin_bit_cast(float, (unsigned)sw[1]));
-                }
-                const float grow = (mt - m_run) * p.scale_log2;      // 0 while both are unset, ~1e30 scale at the first visible key
-                if (__any(grow > UV_ATT_DEFER)) {
-                    const float m_new = fmaxf(m_run, mt);
-                    const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * p.scale_log2);
-                    l_run *= alpha;
-#pragma unroll
-                    for (int d = 0; d < ND; ++d)
-#pragma unroll
-                        for (int e = 0; e < 16; ++e) oacc[d][e] *= alpha;
-                    m_run = m_new;
-                }
-                const float mneg = -m_run * p.scale_log2;
-                float psum = 0.f;
                 bf16x8 pf[2];
-#pragma unroll
-                for (int s2 = 0; s2 < 2; ++s2)
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) {
-                        float pv = __builtin_amdgcn_exp2f(__builtin_fmaf(sacc[8 * s2 + j], p.scale_log2, mneg));
-                        if constexpr (DYN) pv = ((vis >> (8 * s2 + j)) & 1u) ? pv : 0.f;      // a masked element's P is selected, not computed
-                        psum += pv;
-                        pf[s2][j] = (__bf16)pv;
-                    }
-                l_run += psum;
+                attn_softmax_half<DYN>(sacc, vis, p.scale_log2, m_run, l_run, oacc, pf);      // generic form: a masked element's P is selected to 0
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int d = 0; d < ND; ++d)
@@ -330,7 +241,7 @@ __device__ __forceinline__ void win_body(AttnWinArgs p, char* smem) {
 
     const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
     const float inv = 1.0f / l_tot;
-    const int lane_e = win_lane_here();
+    const int lane_e = attn_lane_here();
     if ((p.ldo & 7) == 0) {
         // O through LDS: wave-private images over the K / V^T buffers (free: the last tile ended on a barrier that every wave took)
         attn_store_lds(smem + wave_u * (32 * 144), p.out + (long)q0w * p.ldo + hcol, p.ldo, L - q0w, lane_e, oacc, inv);
@@ -376,17 +287,9 @@ extern "C" int uv_flash_attn_win_plan(int batch, int L, int H, int head_dim, int
 extern "C" int uv_flash_attn_win_bf16(const void* q, long ldq, const void* k, long ldk, const void* vt, long ldvt, void* out, long ldo, int batch,
                                       int L, int H, int head_dim, float softmax_scale, int win_left, int win_right, void* stream) {
     const char* name = "uv_flash_attn_win_bf16";
-    UV_CHECK_ARG(q && k && vt && out, "%s: null pointer", name);
-    UV_CHECK_ARG(head_dim == 128, "%s: head_dim %d unsupported (128 only)", name, head_dim);
-    UV_CHECK_ARG(L > 0 && L <= (1 << 30) && H > 0 && batch > 0, "%s: bad shape B=%d L=%d H=%d", name, batch, L, H);
+    if (attn_self_check_shape(name, q, k, vt, out, batch, L, H, head_dim)) return -1;
     UV_CHECK_ARG(win_left >= -1 && win_right >= -1, "%s: window (%d, %d): each side >= 0, or -1 = unbounded", name, win_left, win_right);
-    UV_CHECK_ARG(ldq % 8 == 0 && ldk % 8 == 0 && ldvt % 8 == 0 && ldo % 4 == 0, "%s: leading dimensions must be multiples of 8 elements", name);
-    UV_CHECK_ARG(ldvt >= (long)(batch - 1) * L + (long)((L + 63) / 64) * 64,
-                 "%s: ldvt=%ld must cover (batch-1)*L + L rounded up to 64 (batch=%d L=%d)", name, ldvt, batch, L);
-    UV_CHECK_ARG(batch == 1 || L % 8 == 0, "%s: batch > 1 needs L %% 8 == 0 (L=%d)", name, L);
-    // the LDS-DMA pieces are addressed with 32-bit lane offsets from a uniform base (the dense entry falls back to flash_attn_fwd_kernel there)
-    UV_CHECK_ARG(128 * ldvt < (1L << 30) && 64 * ldk < (1L << 30), "%s: ldk=%ld / ldvt=%ld too large for 32-bit piece offsets", name, ldk, ldvt);
-    UV_CHECK_ARG((((uintptr_t)q | (uintptr_t)k | (uintptr_t)vt | (uintptr_t)out) & 15) == 0, "%s: pointers must be 16-byte aligned", name);
+    if (attn_self_check_layout(name, q, k, vt, out, ldq, ldk, ldvt, ldo, batch, L)) return -1;
     AttnWinArgs a;
     a.q = (const bf16_t*)q; a.k = (const bf16_t*)k; a.vt = (const bf16_t*)vt; a.out = (bf16_t*)out;
     a.ldq = ldq; a.ldk = ldk; a.ldvt = ldvt; a.ldo = ldo;

@@ -1,6 +1,7 @@
-// The flash-attention kernels' shared host and device pieces (attention.hip; attention_mx.hip; attention_mxpv.hip; tools/diag/attn_pw4.hip): the argument block and constants,
-// plan_attn - the ONE place that decides which kernel serves a call, on what query-block cut and on what grid -, and the device code the
-// kernels have in common.
+// The flash-attention kernels' shared host and device pieces (attention.hip; attention_win.hip; attention_bs.hip; attention_mx.hip; attention_mxpv.hip;
+// tools/diag/attn_pw4.hip): the argument block and constants, plan_attn - the ONE place that decides which kernel serves a call, on what
+// query-block cut and on what grid -, and the device code the kernels have in common: the per-wave QK^T / softmax / P.V of a 32-key half, the
+// ragged-tile mask, the staging of the 64 KiB layout and the O stores are defined here.
 #pragma once
 #include "common.h"
 
@@ -155,6 +156,29 @@ static inline AttnPlan plan_attn_bs(int batch, int L, int H) {
     return AttnPlan{ATT_BS4, qb, 0, qb * H * batch, 256};
 }
 
+// The argument checks the self-attention entries (uv_flash_attn_win_bf16, uv_flash_attn_bs_bf16 / _lists_bf16) have in common, in two parts:
+// each entry's own check (the window's sides; mask_heads) stands between them, where it always stood - the order of the refusals is part of
+// the entries' behaviour.
+static inline int attn_self_check_shape(const char* name, const void* q, const void* k, const void* vt, const void* out, int batch, int L, int H,
+                                        int head_dim) {
+    UV_CHECK_ARG(q && k && vt && out, "%s: null pointer", name);
+    UV_CHECK_ARG(head_dim == 128, "%s: head_dim %d unsupported (128 only)", name, head_dim);
+    UV_CHECK_ARG(L > 0 && L <= (1 << 30) && H > 0 && batch > 0, "%s: bad shape B=%d L=%d H=%d", name, batch, L, H);
+    return 0;
+}
+
+static inline int attn_self_check_layout(const char* name, const void* q, const void* k, const void* vt, const void* out, long ldq, long ldk,
+                                         long ldvt, long ldo, int batch, int L) {
+    UV_CHECK_ARG(ldq % 8 == 0 && ldk % 8 == 0 && ldvt % 8 == 0 && ldo % 4 == 0, "%s: leading dimensions must be multiples of 8 elements", name);
+    UV_CHECK_ARG(ldvt >= (long)(batch - 1) * L + (long)((L + 63) / 64) * 64,
+                 "%s: ldvt=%ld must cover (batch-1)*L + L rounded up to 64 (batch=%d L=%d)", name, ldvt, batch, L);
+    UV_CHECK_ARG(batch == 1 || L % 8 == 0, "%s: batch > 1 needs L %% 8 == 0 (L=%d)", name, L);
+    // the LDS-DMA pieces are addressed with 32-bit lane offsets from a uniform base (the dense entry falls back to flash_attn_fwd_kernel there)
+    UV_CHECK_ARG(128 * ldvt < (1L << 30) && 64 * ldk < (1L << 30), "%s: ldk=%ld / ldvt=%ld too large for 32-bit piece offsets", name, ldk, ldvt);
+    UV_CHECK_ARG((((uintptr_t)q | (uintptr_t)k | (uintptr_t)vt | (uintptr_t)out) & 15) == 0, "%s: pointers must be 16-byte aligned", name);
+    return 0;
+}
+
 // ---- device code the kernels share
 typedef __attribute__((address_space(3))) void lds_void_a;
 
@@ -258,9 +282,179 @@ __device__ __forceinline__ void attn_frag_addrs(unsigned smem_a, unsigned v_off,
         for (int s2 = 0; s2 < 2; ++s2) vaddr[T][s2] = smem_a + v_off + r * 128 + (((4 * T + 2 * s2 + h) ^ v_key) << 4);
 }
 
-// O rows of one wave through a wave-private LDS image (flash_attn_fwd12_kernel's epilogue, for kernels written after it): 32 rows x (128 + 16)
-// bytes at img, two passes of two d-blocks; every store instruction writes 8 whole 128-byte lines. ldo % 8 == 0. The caller owns the LDS
-// (every reader of what it held has passed a barrier).
+// The lane id, produced HERE (two VALU instructions, volatile: not hoisted): the rare branches and the epilogues derive their lane constants from it
+// instead of keeping them - or the lane id itself - in registers across the tile loops, where they were spilled.
+__device__ __forceinline__ int attn_lane_here() {
+    int l;
+    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
+    return l;
+}
+
+// The windowed and block-sparse kernels' "unset" reference maximum and masked score. A lane's query can have no visible key in a 32-key half
+// while its maximum is still unset; the dense kernels' -INFINITY would compute -inf - -inf there. With this FINITE sentinel and P of a masked
+// element SELECTED to 0 (attn_softmax_half<true>) such a lane gets mt = unset, grow = 0 (no move of its own), alpha = exp2(0) = 1 exactly if a
+// neighbour moves, P = 0, l += 0; at its first visible key alpha = exp2(-1e30 scale) = 0 on l = 0, O = 0 - what the dense kernels compute from -inf.
+#define UV_WIN_UNSET (-1.0e30f)
+
+// ---- one 32-key half of a staged tile, per wave (fwd3 / fwd12 / bs; the softmax also win and mxqk): S^T = K.Q^T, online softmax, O^T += V^T.P^T.
+// A kernel that measured worse with one of these keeps its own copy and says so at the copy (win_body: QK^T and P.V; mxpv_body: mask and O store).
+typedef const __attribute__((address_space(3))) bf16x8* lds_frag_p;
+
+// The 8 fragment reads of a half go UV_ATT_AHEAD ahead of the 8 MFMAs that consume them (ID = the sync id of the group).
+template <int ID>
+__device__ __forceinline__ void attn_reads_ahead() {
+    __builtin_amdgcn_sched_group_barrier(0x100, UV_ATT_AHEAD, ID);
+#pragma unroll
+    for (int i = 0; i < 8 - UV_ATT_AHEAD; ++i) {
+        __builtin_amdgcn_sched_group_barrier(0x008, 1, ID);
+        __builtin_amdgcn_sched_group_barrier(0x100, 1, ID);
+    }
+    __builtin_amdgcn_sched_group_barrier(0x008, UV_ATT_AHEAD, ID);
+    __builtin_amdgcn_sched_barrier(0);
+}
+
+// S^T of a half: off = buffer parity * K bytes + T * 32 K rows (an instruction immediate when the parity is a compile-time constant).
+__device__ __forceinline__ f32x16 attn_qk_half(const unsigned (&kaddr)[8], const bf16x8 (&qf)[8], int off) {
+    f32x16 sacc;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) sacc[e] = 0.f;
+#pragma unroll
+    for (int kk = 0; kk < 8; ++kk) {
+        const bf16x8 kf = *(lds_frag_p)(kaddr[kk] + off);
+        sacc = mfma_32x32x16<false>(kf, qf[kk], sacc);
+    }
+    attn_reads_ahead<0>();
+    return sacc;
+}
+
+// The ragged last tile of the dense kernels: accumulator register e of half T holds key kv0 + perm23(32 T + (e & 3) + 8 (e >> 2) + 4 h).
+__device__ __forceinline__ void attn_mask_ragged(f32x16& sacc, int kv0, int T, int h, int Lk) {
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+        const int i = 32 * T + (e & 3) + 8 * (e >> 2) + 4 * h;
+        if (kv0 + perm23(i) >= Lk) sacc[e] = -INFINITY;
+    }
+}
+
+// Online softmax of a half (query on the lane; masked scores already replaced by the caller: -INFINITY dense, UV_WIN_UNSET win / bs). The row
+// maximum meets the other half-wave's by v_permlane32_swap (one VALU op, no ds_bpermute round trip). The reference maximum m_run moves only when
+// some row's maximum outgrows it by more than 2^UV_ATT_DEFER in the exponent domain (then P <= 2^UV_ATT_DEFER instead of <= 1 until the next move;
+// P, l and O share one scale and bf16 / f32 relative precision is scale-invariant): with the exact running maximum about half of all tiles of a
+// long sequence still see a new maximum in SOME row of the wave and pay the O rescale. SELECT: P of an element whose vis bit is clear is
+// selected to 0, not computed (else vis is ignored). pf = P in bf16, the B operand of attn_pv_half.
+template <bool SELECT>
+__device__ __forceinline__ void attn_softmax_half(const f32x16& sacc, unsigned vis, float scale_log2, float& m_run, float& l_run,
+                                                  f32x16 (&oacc)[4], bf16x8 (&pf)[2]) {
+    float mt = sacc[0];
+#pragma unroll
+    for (int e = 1; e < 16; ++e) mt = fmaxf(mt, sacc[e]);
+    {
+        const unsigned u = __builtin_bit_cast(unsigned, mt);
+        const auto sw = __builtin_amdgcn_permlane32_swap(u, u, false, false);
+        mt = fmaxf(__builtin_bit_cast(float, (unsigned)sw[0]), __builtin_bit_cast(float, (unsigned)sw[1]));
+    }
+    const float grow = (mt - m_run) * scale_log2;      // +inf on the first tile (m_run = -inf); win / bs: 0 while both are unset
+    if (__any(grow > UV_ATT_DEFER)) {
+        const float m_new = fmaxf(m_run, mt);
+        const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * scale_log2);
+        l_run *= alpha;
+#pragma unroll
+        for (int d = 0; d < 4; ++d)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) oacc[d][e] *= alpha;
+        m_run = m_new;
+    }
+    const float mneg = -m_run * scale_log2;
+    float psum = 0.f;
+#pragma unroll
+    for (int s2 = 0; s2 < 2; ++s2)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            float pv = __builtin_amdgcn_exp2f(__builtin_fmaf(sacc[8 * s2 + j], scale_log2, mneg));
+            if constexpr (SELECT) pv = ((vis >> (8 * s2 + j)) & 1u) ? pv : 0.f;
+            psum += pv;
+            pf[s2][j] = (__bf16)pv;
+        }
+    l_run += psum;
+}
+
+// O^T += V^T . P^T of a half: vaddr = the half's two fragment addresses, off = buffer parity * V^T bytes (0 with a single V^T buffer).
+__device__ __forceinline__ void attn_pv_half(const unsigned (&vaddr)[2], int off, const bf16x8 (&pf)[2], f32x16 (&oacc)[4]) {
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int d = 0; d < 4; ++d)
+#pragma unroll
+        for (int s2 = 0; s2 < 2; ++s2) {
+            const bf16x8 vf = *(lds_frag_p)(vaddr[s2] + off + d * 32 * 128);
+            oacc[d] = mfma_32x32x16<false>(vf, pf[s2], oacc[d]);
+        }
+    attn_reads_ahead<1>();
+}
+
+// ---- staging of the 64 KiB layout (K and V^T both double-buffered; fwd12 / win / bs): the 32 one-KiB pieces of a tile (K pieces 0..15 = 4 LDS
+// rows each, V^T pieces 0..15 = 8 rows each) are dealt round-robin over the NW waves. K pieces of equal pc & 3 share the swizzle key and the row
+// permutation bits, V^T pieces of equal parity the swizzle key: at 12 waves (K w, w + 12 (w < 4); V^T w - 4 (w >= 4), w + 8 (w < 8)) and at 4
+// (K and V^T w, w + 4, w + 8, w + 12) ONE lane offset per operand serves all of a wave's pieces; the piece's row / column step goes into the
+// uniform base. kb_t / vb_t = the tile's first key row of the head / first key column (the kernels keep their own base pointers).
+template <int NW>
+struct AttnStage {
+    static_assert(NW == 12 || NW == 4, "two forms");
+    static constexpr int K_BYTES = UV_ATT_KV * 256, V_BYTES = 128 * 128, V_OFF = 2 * K_BYTES;
+    unsigned koff, voff;      // lane offsets in bytes, relative to the tile's first key row / key column
+    long k16, v8;             // 16 K rows / 8 V^T rows in bytes
+    unsigned smem_a;          // LDS byte address of K buffer 0
+    int wave;
+    int ldk;                  // K's leading dimension in elements: clamped() builds its row offsets from it
+
+    __device__ __forceinline__ AttnStage(unsigned smem_a_, int wave_u, int lane, long ldk_, long ldvt) : k16(16 * ldk_ * 2), v8(8 * ldvt * 2),
+                                                                                                       smem_a(smem_a_), wave(wave_u), ldk((int)ldk_) {
+        const int s4 = lane >> 4, s8 = lane >> 3, p3 = wave_u & 3;
+        const int c = (lane & 15) ^ ((4 * p3 + s4) & 15);
+        const int swap2 = ((p3 & 1) << 1) | (p3 >> 1);
+        koff = (unsigned)((s4 + 4 * swap2) * (int)ldk_ + c * 8) * 2u;
+        const int cv = (lane & 7) ^ ((4 * (wave_u & 1) + (s8 >> 1)) & 7);
+        voff = (unsigned)(s8 * (int)ldvt + cv * 8) * 2u;
+    }
+    __device__ __forceinline__ void v(const char* vb_t, int buf) const {
+        if constexpr (NW == 12) {
+            const int vq0 = wave - 4, vq1 = wave + 8;
+            if (wave >= 4) glds16_sbase(vb_t + vq0 * v8, voff, smem_a + V_OFF + buf * V_BYTES + vq0 * 1024);
+            if (wave < 8) glds16_sbase(vb_t + vq1 * v8, voff, smem_a + V_OFF + buf * V_BYTES + vq1 * 1024);
+        } else {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) glds16_sbase(vb_t + (wave + 4 * i) * v8, voff, smem_a + V_OFF + buf * V_BYTES + (wave + 4 * i) * 1024);
+        }
+    }
+    __device__ __forceinline__ void full(const char* kb_t, const char* vb_t, int buf) const {
+        if constexpr (NW == 12) {
+            glds16_sbase(kb_t + (wave >> 2) * k16, koff, smem_a + buf * K_BYTES + wave * 1024);
+            if (wave < 4) glds16_sbase(kb_t + 3 * k16, koff, smem_a + buf * K_BYTES + (wave + 12) * 1024);
+        } else {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) glds16_sbase(kb_t + i * k16, koff, smem_a + buf * K_BYTES + (wave + 4 * i) * 1024);
+        }
+        v(vb_t, buf);
+    }
+    // the ragged last tile: K rows clamped to last_row (the last key's row inside the tile) in the lane offset; the row inside the tile is
+    // 16 (pc >> 2) + the lane's row of its 16. Rare: its lane constants come from attn_lane_here(), not from registers kept across the tile loops.
+    __device__ __forceinline__ void clamped(const char* kb_t, const char* vb_t, int last_row, int buf) const {
+        const int p3 = wave & 3;
+        const int ln = attn_lane_here();
+        const int r4 = ln >> 4;
+        const int krl = r4 + 4 * (((p3 & 1) << 1) | (p3 >> 1));
+        const unsigned c16 = (unsigned)(((ln & 15) ^ ((4 * p3 + r4) & 15)) << 4);
+#pragma unroll
+        for (int i = 0; i < (NW == 12 ? 2 : 4); ++i) {
+            const int pc = wave + NW * i;
+            if (pc < 16) glds16_sbase(kb_t, (unsigned)(min(16 * (pc >> 2) + krl, last_row) * ldk) * 2u + c16, smem_a + buf * K_BYTES + pc * 1024);
+        }
+        v(vb_t, buf);
+    }
+};
+
+// O rows of one wave through a wave-private LDS image: 32 rows x (128 + 16) bytes at img, two passes of two d-blocks; every store instruction
+// writes 8 whole 128-byte lines (directly from the MFMA layout it touches 32 rows with 16 bytes each; self-attention at the DiT shape 2.724 ->
+// 2.711 ms in a same-device A/B, bit-identical). ldo % 8 == 0. The caller owns the LDS (every reader of what it held has passed a barrier).
 __device__ __forceinline__ void attn_store_lds(char* img, bf16_t* out0, long ldo, int rows, int lane, const f32x16 (&oacc)[4], float inv) {
     constexpr int RS = 144;
     const int r = lane & 31, h = lane >> 5, srow = lane >> 3, chunk = lane & 7;
