@@ -180,9 +180,19 @@ def _check_slots(model: nn.Module):
                                  f"slot holds at most {LORA_MAX_SLOT} columns (univid_amd.wan.model.LORA_MAX_SLOT)")
 
 
+_MX_REFUSAL = {      # attach-time side of the refusals of univid_amd.wan.modes.validate_modes; mx_covered states the Linears
+    "ffn_precision": "an un-merged adapter (merge=False) on ffn.0 / ffn.2 cannot be combined with ffn_precision 'mxfp8' (the MXFP8 GEMM "
+                     "has no adapter slot). Merge the adapter (merge=True: the merged weights are re-quantised) or call "
+                     "set_ffn_precision('bf16') first. Un-merged adapters on the attention projections work in both modes.",
+    "proj_precision": "an un-merged adapter (merge=False) on self_attn.q / k / v / o or cross_attn.q / o cannot be combined with "
+                      "proj_precision 'mxfp8' (the MXFP8 GEMM has no adapter slot). Merge the adapter (merge=True: the merged weights are "
+                      "re-quantised) or call set_proj_precision('bf16') first. Un-merged adapters on cross_attn.k / v work in both modes."}
+
+
 def attach_adapter_(model: nn.Module, name: str, factors, cfg: dict, weight: float = 1.0):
     """Attaches the adapter UN-MERGED under `name`: every targeted nn.Linear gets its bf16 factors and scaling (`lin._uv_lora[name]`);
     the fp32 weights are not touched. Everything is validated before the first module changes. Returns the module paths."""
+    from .wan.modes import mx_covered
     _refuse_unsupported(cfg, "attached")
     if cfg.get("fan_in_fan_out", False):
         raise NotImplementedError("fan_in_fan_out adapters are not supported un-merged (nn.Linear layers never need it)")
@@ -200,16 +210,9 @@ def attach_adapter_(model: nn.Module, name: str, factors, cfg: dict, weight: flo
         if name in getattr(lin, "_uv_lora", {}):
             raise RuntimeError(f"an adapter named {name!r} is already attached to {path!r}")
         own = _owner(model, path)
-        if getattr(own, "ffn_precision", "bf16") == "mxfp8" and hasattr(own, "ffn") and any(lin is own.ffn[i] for i in (0, 2)):
-            raise NotImplementedError(
-                f"{path!r}: an un-merged adapter (merge=False) on ffn.0 / ffn.2 cannot be combined with ffn_precision 'mxfp8' (the MXFP8 GEMM "
-                f"has no adapter slot). Merge the adapter (merge=True: the merged weights are re-quantised) or call "
-                f"set_ffn_precision('bf16') first. Un-merged adapters on the attention projections work in both modes.")
-        if getattr(own, "proj_precision", "bf16") == "mxfp8" and any(lin is getattr(own, n, None) for n in getattr(own, "_mx_proj", ())):
-            raise NotImplementedError(
-                f"{path!r}: an un-merged adapter (merge=False) on self_attn.q / k / v / o or cross_attn.q / o cannot be combined with "
-                f"proj_precision 'mxfp8' (the MXFP8 GEMM has no adapter slot). Merge the adapter (merge=True: the merged weights are "
-                f"re-quantised) or call set_proj_precision('bf16') first. Un-merged adapters on cross_attn.k / v work in both modes.")
+        for mode, covered in mx_covered(own).items():       # an MXFP8 GEMM mode that is on refuses an adapter on a Linear it covers
+            if getattr(own, mode, "bf16") == "mxfp8" and any(lin is c for c in covered):
+                raise NotImplementedError(f"{path!r}: " + _MX_REFUSAL[mode])
         todo.append((path, lin, a, b, module_scaling(cfg, path, a.shape[0])))
     for path, lin, a, b, s in todo:
         dev = lin.weight.device

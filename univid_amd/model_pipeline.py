@@ -29,6 +29,7 @@ from typing import Any, Callable, List, Optional, Tuple
 import torch
 
 from .lora import LoRAManager
+from .wan.modes import MODE_DEFAULTS, apply_requested
 from .wan.textimage2video import TI2VConfig, WanTI2V, set_vae_precision
 
 
@@ -376,27 +377,15 @@ class CrossAttentionFusionPipeline:
             self._check_gpu("cross_attn_gpu")
             context_projector = ContextProjector(config).to(f"cuda:{config.cross_attn_gpu}").eval()
         self.context_projector = context_projector
+        # the DiT's opt-in settings as the config holds them, read once: for the constructor of a WanTI2V built here and for an injected one
+        self._dit_modes = {name: getattr(config, name, default) for name, default in MODE_DEFAULTS.items()}
         if wan_pipeline is None:
             wan_pipeline = self._initialize_wan22(wan_config)
         self.wan_pipeline = wan_pipeline
         self.dit_model = wan_pipeline.model
         # a pipeline built here got the config's mode in its constructor; an INJECTED one keeps the mode it came with unless the config asks
         # for another than the default
-        ffn_precision = getattr(config, "ffn_precision", "bf16")
-        if ffn_precision != "bf16" and hasattr(self.dit_model, "set_ffn_precision") and ffn_precision != self.dit_model.ffn_precision:
-            self.dit_model.set_ffn_precision(ffn_precision)
-        attn_precision = getattr(config, "attn_precision", "bf16")
-        if attn_precision != "bf16" and hasattr(self.dit_model, "set_attn_precision") and attn_precision != self.dit_model.attn_precision:
-            self.dit_model.set_attn_precision(attn_precision)
-        attn_window = getattr(config, "attn_window", None)
-        if attn_window is not None and hasattr(self.dit_model, "set_attn_window") and tuple(attn_window) != tuple(self.dit_model.window_size):
-            self.dit_model.set_attn_window(attn_window)
-        attn_block_mask = getattr(config, "attn_block_mask", None)
-        if attn_block_mask is not None and hasattr(self.dit_model, "set_attn_block_mask"):
-            self.dit_model.set_attn_block_mask(attn_block_mask)
-        proj_precision = getattr(config, "proj_precision", "bf16")
-        if proj_precision != "bf16" and hasattr(self.dit_model, "set_proj_precision") and proj_precision != self.dit_model.proj_precision:
-            self.dit_model.set_proj_precision(proj_precision)
+        apply_requested(self.dit_model, self._dit_modes, injected=True)
         set_vae_precision(getattr(wan_pipeline, "vae", None), getattr(config, "vae_precision", None))
         self.vae_model = wan_pipeline.vae
         self.text_encoder = wan_pipeline.text_encoder
@@ -425,11 +414,7 @@ class CrossAttentionFusionPipeline:
         self._check_gpu("wan_gpu")
         try:
             return WanTI2V(config=wan_config, checkpoint_dir=path, device_id=self.config.wan_gpu, rank=0, t5_fsdp=False, dit_fsdp=False,
-                           use_sp=False, ffn_precision=getattr(self.config, "ffn_precision", "bf16"),
-                           attn_precision=getattr(self.config, "attn_precision", "bf16"),
-                           proj_precision=getattr(self.config, "proj_precision", "bf16"),
-                           vae_precision=getattr(self.config, "vae_precision", None), attn_window=getattr(self.config, "attn_window", None),
-                           attn_block_mask=getattr(self.config, "attn_block_mask", None))
+                           use_sp=False, vae_precision=getattr(self.config, "vae_precision", None), **self._dit_modes)
         except Exception as e:
             raise RuntimeError(f"Wan2.2 initialization failed: {e}") from e
 

@@ -27,7 +27,8 @@ import torch
 import torch.nn as nn
 
 from .. import _lib
-from .attention import TopKBlockMask, topk_attention
+from .attention import topk_attention
+from .modes import ATTN_PRECISIONS, FFN_PRECISIONS, MODE_DEFAULTS, PROJ_PRECISIONS, AttnBlockMask, AttnTopKMask, validate_modes  # noqa: F401
 from .._lib import (EPI_BF16, EPI_BF16_T, EPI_F32_FROM_BF16, EPI_GATE_RESID_F32, EPI_GELU_BF16, EPI_RESID_F32)
 
 __all__ = ["WanModel"]
@@ -68,9 +69,6 @@ class _Prepared:
         self.b = None if lin.bias is None else lin.bias.detach().to(BF16).contiguous()
 
 
-FFN_PRECISIONS = ("bf16", "mxfp8")
-
-
 class _PreparedMx:
     """OCP MXFP8 operand of one nn.Linear for uv_gemm_mxfp8_nt: e4m3fn codes [N, K] and e8m0 scales [N, K / 32] (uint8 both), quantised
     by uv_mx_quant_bf16 from the bf16 copy the bf16 path reads - which is not kept - and the bf16 bias."""
@@ -83,197 +81,6 @@ class _PreparedMx:
         self.s = torch.empty(N, K // 32, dtype=torch.uint8, device=p.w.device)
         _lib.mx_quant(p.w, self.w, self.s)
         self.b = p.b
-
-
-ATTN_PRECISIONS = ("bf16", "mxfp8_qk", "mxfp8_qk_pv")
-
-
-def _check_attn_precision(mode, head_dim):
-    """set_attn_precision's guards, on one self-attention's geometry: raises before any state changes."""
-    if mode not in ATTN_PRECISIONS:
-        raise ValueError(f"attn_precision {mode!r}: one of {ATTN_PRECISIONS}")
-    if mode != "bf16" and head_dim != 128:
-        raise ValueError(f"attn_precision {mode!r} needs head_dim 128 (one MX scale dword per head and row, two 64-element steps of the "
-                         f"block-scaled matrix instruction); this model has head_dim {head_dim}")
-
-
-def _check_attn_window(window, head_dim=128, attn_precision="bf16"):
-    """set_attn_window's guards, on one self-attention's geometry: raises before any state changes. Returns the window as the kernels take
-    it - (left, right), each >= 0 or -1 = unbounded (flash-attn's window_size) - or None for global attention (None or (-1, -1))."""
-    if window is None:
-        return None
-    try:
-        ok = len(window) == 2 and all(int(w) == w and not isinstance(w, bool) for w in window)
-    except (TypeError, ValueError):
-        ok = False
-    if not ok or min(int(w) for w in window) < -1:
-        raise ValueError(f"window_size {window!r}: (left, right), two integers, each >= 0 or -1 for unbounded")
-    window = (int(window[0]), int(window[1]))
-    if window == (-1, -1):
-        return None
-    if head_dim != 128:
-        raise NotImplementedError(f"window_size {window}: the windowed attention kernels are built for head_dim 128 (this model has {head_dim})")
-    if attn_precision != "bf16":
-        raise NotImplementedError(f"window_size {window} with attn_precision {attn_precision!r}: the windowed attention kernels are bf16 only "
-                                  f"- set_attn_precision('bf16') or set_attn_window(None) first")
-    return window
-
-
-class AttnBlockMask:
-    """set_attn_block_mask's spec as the self-attention launches resolve it: the PreparedBlockMask of a forward's patch grid. spec: a
-    PreparedBlockMask or a bool tensor (one fixed L: a forward at another L raises), or a callable f(F, H, W, num_heads) -> bool mask
-    [ceil(L / 128), ceil(L / 64)] or [num_heads, ...] with L = F H W, evaluated and prepared ONCE per distinct (grid, device) and cached.
-    Preparing builds lists on the CPU and uploads them, which a HIP-graph capture cannot hold: a forward inside a capture whose grid was
-    not prepared raises (WanTI2V's eager warm-up forward prepares it before it captures; `prepare(grid, device)` does so by hand)."""
-
-    def __init__(self, spec, num_heads):
-        self.spec, self.num_heads, self._cache = spec, int(num_heads), {}
-
-    def prepared(self):
-        """{(grid or L, device): PreparedBlockMask} of what was prepared so far (tools report the densities)."""
-        return dict(self._cache)
-
-    def prepare(self, grid, device):
-        return self.resolve(tuple(int(g) for g in grid), math.prod(int(g) for g in grid), torch.device(device))
-
-    def resolve(self, grid, L, device):
-        spec = self.spec
-        if isinstance(spec, _lib.PreparedBlockMask):
-            if spec.L != L:
-                raise ValueError(f"attn_block_mask was prepared for L = {spec.L}; this forward has L = {L} (patch grid {tuple(grid)})")
-            if spec.device != device:
-                raise ValueError(f"attn_block_mask lives on {spec.device}; this forward runs on {device}")
-            return spec
-        key = (L, device) if torch.is_tensor(spec) else (tuple(grid), device)
-        bm = self._cache.get(key)
-        if bm is None:
-            if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
-                raise RuntimeError(f"attn_block_mask: patch grid {tuple(grid)} (L = {L}) was not prepared before this HIP-graph capture - "
-                                   f"run one eager forward at this grid, or AttnBlockMask.prepare(grid, device), first")
-            mask = spec if torch.is_tensor(spec) else spec(int(grid[0]), int(grid[1]), int(grid[2]), self.num_heads)
-            bm = _lib.prepare_block_mask(mask, L, device)      # (a tensor of another L's shape is refused here, naming the shape)
-            if bm.heads not in (1, self.num_heads):
-                raise ValueError(f"attn_block_mask: a per-head mask needs {self.num_heads} heads, got {bm.heads}")
-            self._cache[key] = bm
-        return bm
-
-
-class AttnTopKMask:
-    """set_attn_block_mask's resolver of a TopKBlockMask (univid_amd.wan.attention): per patch grid the count of non-kept tiles a query
-    block lists and the static keep mask on the device. keep's tensor / callable forms resolve and cache exactly as AttnBlockMask's specs
-    do - a tensor belongs to one L, a callable is evaluated once per distinct (grid, device), and uploading inside a HIP-graph capture is
-    refused (WanTI2V's eager warm-up forward prepares it; `prepare(grid, device)` does so by hand). Without a keep mask nothing is
-    uploaded and every grid resolves anywhere. The lists themselves are built on the device in every forward."""
-
-    class Plan:
-        """One grid's resolved spec: top_k (int), keep (uint8 [1 or H, nqb, nkb] on the device, or None), mask (the expanded bool keep mask
-        on the CPU, or None), L."""
-        __slots__ = ("top_k", "keep", "mask", "L")
-
-        def __init__(self, top_k, keep, mask, L):
-            self.top_k, self.keep, self.mask, self.L = top_k, keep, mask, L
-
-    def __init__(self, spec, num_heads):
-        self.spec, self.num_heads, self._cache = spec, int(num_heads), {}
-
-    def prepared(self):
-        """{(grid or L, device): Plan} of what was resolved so far."""
-        return dict(self._cache)
-
-    def prepare(self, grid, device):
-        return self.resolve(tuple(int(g) for g in grid), math.prod(int(g) for g in grid), torch.device(device))
-
-    def resolve(self, grid, L, device):
-        spec = self.spec
-        key = (tuple(grid), device) if callable(spec.keep) else (L, device)
-        plan = self._cache.get(key)
-        if plan is None:
-            nkb = -(-L // _lib.BS_K_BLOCK)
-            if nkb > _lib.BS_SELECT_MAX_TILES:
-                raise NotImplementedError(f"attn_block_mask: L = {L} has {nkb} key tiles; the top-k selection kernel sorts at most "
-                                          f"{_lib.BS_SELECT_MAX_TILES} (L <= {_lib.BS_SELECT_MAX_TILES * _lib.BS_K_BLOCK})")
-            keep = mask = None
-            if spec.keep is not None:
-                if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
-                    raise RuntimeError(f"attn_block_mask: the keep mask of patch grid {tuple(grid)} (L = {L}) was not prepared before this "
-                                       f"HIP-graph capture - run one eager forward at this grid, or AttnTopKMask.prepare(grid, device), first")
-                m = spec.keep if torch.is_tensor(spec.keep) else spec.keep(int(grid[0]), int(grid[1]), int(grid[2]), self.num_heads)
-                keep, mask = _lib.prepare_keep_mask(m, L, device, spec.q_block, spec.k_block)
-                if mask.shape[0] not in (1, self.num_heads):
-                    raise ValueError(f"attn_block_mask: a per-head keep mask needs {self.num_heads} heads, got {mask.shape[0]}")
-            plan = self._cache[key] = AttnTopKMask.Plan(spec.count(L), keep, mask, L)
-        return plan
-
-
-def _check_attn_block_mask(spec, head_dim=128, attn_precision="bf16", attn_window=None, num_heads=None):
-    """set_attn_block_mask's guards, on one self-attention's geometry: raises before any state changes. Returns None (global attention) or
-    the AttnBlockMask that resolves the spec."""
-    if spec is None:
-        return None
-    if isinstance(spec, (AttnBlockMask, AttnTopKMask)):
-        resolver, spec = spec, spec.spec
-    else:
-        resolver = None
-    topk = isinstance(spec, TopKBlockMask)
-    if topk:
-        heads = spec.keep.shape[0] if torch.is_tensor(spec.keep) and spec.keep.dim() == 3 else 1
-    elif torch.is_tensor(spec):
-        if spec.dtype != torch.bool or spec.dim() not in (2, 3):
-            raise TypeError(f"attn_block_mask: a tensor spec must be torch.bool [nqb, nkb] or [num_heads, nqb, nkb], got {spec.dtype} "
-                            f"{tuple(spec.shape)}")
-        heads = spec.shape[0] if spec.dim() == 3 else 1
-    elif isinstance(spec, _lib.PreparedBlockMask):
-        heads = spec.heads
-    elif callable(spec):
-        heads = 1
-    else:
-        raise TypeError(f"attn_block_mask: None, a bool tensor, a PreparedBlockMask or a callable f(F, H, W, num_heads), got {type(spec).__name__}")
-    if num_heads is not None and heads not in (1, num_heads):
-        raise ValueError(f"attn_block_mask: a per-head mask needs {num_heads} heads (or one mask for all), got {heads}")
-    if head_dim != 128:
-        raise NotImplementedError(f"attn_block_mask: the block-sparse attention kernel is built for head_dim 128 (this model has {head_dim})")
-    if attn_precision != "bf16":
-        raise NotImplementedError(f"attn_block_mask with attn_precision {attn_precision!r}: the block-sparse attention kernel is bf16 only "
-                                  f"- set_attn_precision('bf16') or set_attn_block_mask(None) first")
-    if attn_window is not None:
-        raise NotImplementedError(f"attn_block_mask with window_size {tuple(attn_window)}: one or the other - set_attn_window(None) first, "
-                                  f"or fold the window into the mask")
-    if resolver is not None:
-        return resolver
-    return (AttnTopKMask if topk else AttnBlockMask)(spec, num_heads if num_heads is not None else heads)
-
-
-def _check_ffn_precision(mode, dim, ffn_dim, ffn):
-    """Everything that can refuse a mode, before any state changes."""
-    if mode not in FFN_PRECISIONS:
-        raise ValueError(f"ffn_precision {mode!r}: one of {FFN_PRECISIONS}")
-    if mode == "mxfp8":
-        if dim % 256 or ffn_dim % 256:
-            raise ValueError(f"ffn_precision 'mxfp8' needs dim and ffn_dim to be multiples of 256 (dim {dim}, ffn_dim {ffn_dim}): "
-                             "uv_gemm_mxfp8_nt takes N % 256 == 0 and K % 128 == 0")
-        if any(getattr(ffn[i], "_uv_lora", None) for i in (0, 2)):
-            raise NotImplementedError(
-                "ffn_precision 'mxfp8' and an un-merged LoRA adapter (merge=False) on ffn.0 / ffn.2 cannot be combined: the MXFP8 GEMM has no "
-                "adapter slot. Detach the adapter or merge it (merge=True: the merged weights are re-quantised), or keep ffn_precision 'bf16'. "
-                "Un-merged adapters on the attention projections work in both modes.")
-
-
-PROJ_PRECISIONS = ("bf16", "mxfp8")
-
-
-def _check_proj_precision(mode, dim, attns):
-    """set_proj_precision's guards on one block's geometry and its attention modules: raises before any state changes."""
-    if mode not in PROJ_PRECISIONS:
-        raise ValueError(f"proj_precision {mode!r}: one of {PROJ_PRECISIONS}")
-    if mode == "mxfp8":
-        if dim % 256:
-            raise ValueError(f"proj_precision 'mxfp8' needs dim to be a multiple of 256 (dim {dim}): uv_gemm_mxfp8_nt takes N % 256 == 0 and "
-                             "K % 128 == 0, uv_layernorm_mod_mx C % 256 == 0")
-        if any(getattr(getattr(a, n), "_uv_lora", None) for a in attns for n in a._mx_proj):
-            raise NotImplementedError(
-                "proj_precision 'mxfp8' and an un-merged LoRA adapter (merge=False) on self_attn.q / k / v / o or cross_attn.q / o cannot be "
-                "combined: the MXFP8 GEMM has no adapter slot. Detach the adapter or merge it (merge=True: the merged weights are "
-                "re-quantised), or keep proj_precision 'bf16'. Un-merged adapters on cross_attn.k / v work in both modes.")
 
 
 def _mx_act(t, M, K):
@@ -405,7 +212,7 @@ class WanSelfAttention(nn.Module):
         if not qk_norm:
             raise NotImplementedError("only the TI2V-5B setting (qk_norm) is built")
         # (left, right) of flash-attn's window_size, or None = global attention (WanModel.set_attn_window): instance state
-        self.attn_window = _check_attn_window(window_size, self.head_dim)
+        self.attn_window = self._validate({"attn_window": window_size})["attn_window"]
         self.window_size = self.attn_window or (-1, -1)
         self.attn_block_mask = None      # an AttnBlockMask, or None = global attention (WanModel.set_attn_block_mask): instance state
         self.q = nn.Linear(dim, dim)
@@ -423,11 +230,15 @@ class WanSelfAttention(nn.Module):
     _groups = {"qkv": ("q", "k", "v"), "o": ("o",)}      # projections by the activation they read (one LoRA slot each)
     _mx_proj = ("q", "k", "v", "o")                      # the projections proj_precision "mxfp8" puts on uv_gemm_mxfp8_nt
 
+    def _validate(self, cand):
+        """validate_modes of the settings `cand` on this module alone (its constructor's window, its projections' mode when it prepares)."""
+        return validate_modes(cand, dim=self.dim, head_dim=self.head_dim, num_heads=self.num_heads, attns=(self,))
+
     def prepare(self):
         self._prep, self._slots = {}, {}
         mx = self.proj_precision == "mxfp8"
         if mx:
-            _check_proj_precision("mxfp8", self.dim, (self,))
+            self._validate({"proj_precision": "mxfp8"})
         for g, names in self._groups.items():
             if mx and all(n in self._mx_proj for n in names):       # codes + scales; the bf16 operand copies are not kept, no slot
                 self._prep.update({n: _PreparedMx(getattr(self, n)) for n in names})
@@ -733,50 +544,60 @@ class WanAttentionBlock(nn.Module):
         self.cross_attn.prepare()
         self._prepare_ffn()
 
+    def _validated(self, changes):
+        """This block's settings with `changes` ({setting: value}) laid over them, through validate_modes: raises, or returns the complete
+        normalised candidate. Changes nothing."""
+        sa = self.self_attn
+        now = {k: getattr(sa if k.startswith("attn_") else self, k) for k in MODE_DEFAULTS}      # attn_*: the self-attention holds them
+        return validate_modes({**now, **changes}, dim=self.dim, ffn_dim=self.ffn_dim, head_dim=sa.head_dim, num_heads=sa.num_heads,
+                              block=self, attns=(sa, self.cross_attn))
+
+    def _apply_modes(self, changes):
+        """Every block-level setter: validates the candidate, then - and only then - writes the settings and all their mirrors, and drops
+        what was prepared under the old value of a changed one. After construction nothing else writes these attributes. The cross-
+        attention's window, mask and attn_precision never move; the model's prepared-weights generation is the model-level setters' to move."""
+        new = self._validated(changes)
+        sa = self.self_attn
+        sa.attn_precision, sa.attn_window, sa.attn_block_mask = new["attn_precision"], new["attn_window"], new["attn_block_mask"]
+        sa.window_size = self.window_size = new["attn_window"] or (-1, -1)       # (no prepared weight depends on the three above)
+        self.ffn_precision = new["ffn_precision"]
+        if "ffn_precision" in changes:
+            self._prep = None                    # the FFN operands are re-prepared on the next forward
+        self.proj_precision = sa.proj_precision = self.cross_attn.proj_precision = new["proj_precision"]
+        if "proj_precision" in changes:
+            for a in (sa, self.cross_attn):
+                a._prep, a._kv_cache = None, {}  # the projections' operands likewise, and no K / V^T of the other mode is served
+
     def set_ffn_precision(self, mode):
         """"bf16" (default: the reference's arithmetic) or "mxfp8": ffn.0 / ffn.2 on the block-scaled matrix instructions with OCP MXFP8
         operands (uv_gemm_mxfp8_nt) - a labelled fast mode, narrower than the reference. The FFN operands are re-prepared on the next forward."""
-        _check_ffn_precision(mode, self.dim, self.ffn_dim, self.ffn)
-        self.ffn_precision = mode
-        self._prep = None
+        self._apply_modes({"ffn_precision": mode})
 
     def set_attn_precision(self, mode):
         """"bf16" (default), "mxfp8_qk": this block's self-attention with MXFP8 q / k, or "mxfp8_qk_pv": with an MXFP8 P.V as well
         (WanModel.set_attn_precision states the modes). No prepared weight depends on it."""
-        _check_attn_precision(mode, self.self_attn.head_dim)
-        _check_attn_window(self.self_attn.attn_window, self.self_attn.head_dim, mode)
-        _check_attn_block_mask(self.self_attn.attn_block_mask, self.self_attn.head_dim, mode)
-        self.self_attn.attn_precision = mode
+        self._apply_modes({"attn_precision": mode})
 
     def set_attn_window(self, window_size):
         """(left, right) as flash-attn's window_size, or None / (-1, -1) for global attention: this block's self-attention
         (WanModel.set_attn_window states the mode). No prepared weight depends on it."""
-        w = _check_attn_window(window_size, self.self_attn.head_dim, self.self_attn.attn_precision)
-        _check_attn_block_mask(self.self_attn.attn_block_mask, attn_window=w)
-        self.self_attn.attn_window = w
-        self.self_attn.window_size = self.window_size = w or (-1, -1)
+        self._apply_modes({"attn_window": window_size})
 
     def set_attn_block_mask(self, spec):
         """None (global attention), a bool tensor / PreparedBlockMask of one fixed L, a callable f(F, H, W, num_heads) -> bool mask, or an
         AttnBlockMask that resolves one of them: this block's self-attention (WanModel.set_attn_block_mask states the mode). No prepared
         weight depends on it."""
-        a = self.self_attn
-        a.attn_block_mask = _check_attn_block_mask(spec, a.head_dim, a.attn_precision, a.attn_window, a.num_heads)
+        self._apply_modes({"attn_block_mask": spec})
 
     def set_proj_precision(self, mode):
         """"bf16" (default: the reference's arithmetic) or "mxfp8": this block's self-attention q / k / v / o and cross-attention q / o on
         uv_gemm_mxfp8_nt, fed by uv_layernorm_mod_mx (WanModel.set_proj_precision states the mode). The projections' operands are
         re-prepared on the next forward."""
-        _check_proj_precision(mode, self.dim, (self.self_attn, self.cross_attn))
-        self.proj_precision = mode
-        for a in (self.self_attn, self.cross_attn):
-            a.proj_precision = mode
-            a._prep = None
-            a._kv_cache = {}
+        self._apply_modes({"proj_precision": mode})
 
     def _prepare_ffn(self):
         if self.ffn_precision == "mxfp8":
-            _check_ffn_precision("mxfp8", self.dim, self.ffn_dim, self.ffn)
+            self._validated({})      # (an adapter attached by hand since the mode was set)
             self._prep, self._slots = {"ffn0": _PreparedMx(self.ffn[0]), "ffn2": _PreparedMx(self.ffn[2])}, {"ffn0": None, "ffn2": None}
             return
         p0, s0 = _prepare_group({"ffn0": self.ffn[0]})
@@ -1052,7 +873,8 @@ class WanModel(nn.Module):
         self.text_len, self.in_dim, self.dim, self.ffn_dim = text_len, in_dim, dim, ffn_dim
         self.freq_dim, self.text_dim, self.out_dim = freq_dim, text_dim, out_dim
         self.num_heads, self.num_layers = num_heads, num_layers
-        self.attn_window = _check_attn_window(window_size, dim // num_heads)      # None = global attention; set_attn_window
+        self.attn_window = validate_modes({"attn_window": window_size}, dim=dim, ffn_dim=ffn_dim, head_dim=dim // num_heads,
+                                          num_heads=num_heads)["attn_window"]     # None = global attention; set_attn_window
         window_size = self.attn_window or (-1, -1)
         self.window_size, self.qk_norm, self.cross_attn_norm, self.eps = window_size, qk_norm, cross_attn_norm, eps
         self.config = dict(model_type=model_type, patch_size=self.patch_size, text_len=text_len, in_dim=in_dim, dim=dim,
@@ -1145,6 +967,24 @@ class WanModel(nn.Module):
         for b in self.blocks:
             b.cross_attn._kv_cache = {}
 
+    def _apply_modes(self, changes):
+        """Every model-level setter. Every guard first: each block validates its OWN settings (its own setters may have set it apart) with
+        `changes` laid over them - a model without blocks its own geometry -, and nothing has changed when one refuses. Then every block
+        gets the same normalised values (a mask: one resolver, one cache), the model's mirrors follow and invalidate() moves the generation."""
+        new = None
+        for b in self.blocks:
+            new = b._validated(changes if new is None else {k: new[k] for k in changes})
+        if new is None:
+            new = validate_modes({**{k: getattr(self, k) for k in MODE_DEFAULTS}, **changes}, dim=self.dim, ffn_dim=self.ffn_dim, head_dim=self.dim // self.num_heads,
+                                 num_heads=self.num_heads)
+        changes = {k: new[k] for k in changes}
+        for b in self.blocks:
+            b._apply_modes(changes)
+        for k, v in changes.items():
+            setattr(self, k, v)
+        self.window_size = self.config["window_size"] = self.attn_window or (-1, -1)
+        self.invalidate()
+
     def set_ffn_precision(self, mode):
         """Arithmetic of every block's ffn.0 / ffn.2: "bf16" (default; like for like with the reference) or "mxfp8" - OCP MXFP8 operands
         (e4m3 elements, one power-of-two scale per 32 K elements, activations and weights alike) on the block-scaled matrix instructions,
@@ -1153,14 +993,7 @@ class WanModel(nn.Module):
         Merged LoRA works (weights are re-quantised after invalidate()); an un-merged adapter on ffn.0 / ffn.2 raises NotImplementedError
         here - and attaching one while the mode is "mxfp8" raises in LoRAManager - before any state changes. Calls invalidate(): the
         prepared-weights generation moves on, so captured HIP graphs (WanTI2V) re-capture."""
-        for b in self.blocks:
-            _check_ffn_precision(mode, b.dim, b.ffn_dim, b.ffn)
-        if not len(self.blocks):
-            _check_ffn_precision(mode, 256, 256, {0: None, 2: None})
-        self.ffn_precision = mode
-        for b in self.blocks:
-            b.ffn_precision = mode
-        self.invalidate()
+        self._apply_modes({"ffn_precision": mode})
 
     def set_attn_precision(self, mode):
         """Arithmetic of S = Q K^T in every block's SELF-attention: "bf16" (default; like for like with the reference) or "mxfp8_qk" - q and k
@@ -1172,17 +1005,7 @@ class WanModel(nn.Module):
         and its price: include/univid_hip.h, README); refused by the sequence-parallel forward likewise.
         Needs head_dim 128 (ValueError otherwise, before any state changes). Independent of set_ffn_precision; the two combine.
         Calls invalidate(): the prepared-weights generation moves on, so captured HIP graphs (WanTI2V) re-capture."""
-        _check_attn_precision(mode, self.blocks[0].self_attn.head_dim if len(self.blocks) else 128)
-        _check_attn_window(self.attn_window, attn_precision=mode)
-        _check_attn_block_mask(self.attn_block_mask, attn_precision=mode)
-        for b in self.blocks:
-            _check_attn_precision(mode, b.self_attn.head_dim)
-            _check_attn_window(b.self_attn.attn_window, b.self_attn.head_dim, mode)
-            _check_attn_block_mask(b.self_attn.attn_block_mask, b.self_attn.head_dim, mode)
-        self.attn_precision = mode
-        for b in self.blocks:
-            b.set_attn_precision(mode)
-        self.invalidate()
+        self._apply_modes({"attn_precision": mode})
 
     def set_attn_window(self, window_size):
         """Sliding-window / causal SELF-attention in every block: window_size = (left, right) as flash-attn's (the reference's
@@ -1194,16 +1017,7 @@ class WanModel(nn.Module):
         window is set); the sequence-parallel forward and the reference-signature WanSelfAttention.forward on padded samples raise
         NotImplementedError while a window is set. Independent of ffn_precision / proj_precision and of un-merged LoRA. Every guard runs
         before any state changes. Calls invalidate(): the prepared-weights generation moves on, so captured HIP graphs (WanTI2V) re-capture."""
-        w = _check_attn_window(window_size, self.dim // self.num_heads, self.attn_precision)
-        _check_attn_block_mask(self.attn_block_mask, attn_window=w)
-        for b in self.blocks:
-            _check_attn_window(window_size, b.self_attn.head_dim, b.self_attn.attn_precision)
-            _check_attn_block_mask(b.self_attn.attn_block_mask, attn_window=w)
-        self.attn_window = w
-        self.window_size = self.config["window_size"] = w or (-1, -1)
-        for b in self.blocks:
-            b.set_attn_window(w)
-        self.invalidate()
+        self._apply_modes({"attn_window": window_size})
 
     def set_attn_block_mask(self, spec):
         """Block-sparse SELF-attention in every block (uv_flash_attn_bs_bf16): token i of head h attends token j of its sample iff
@@ -1222,14 +1036,7 @@ class WanModel(nn.Module):
         WanSelfAttention.forward on padded samples raise NotImplementedError while a mask is set. Independent of ffn_precision /
         proj_precision and of un-merged and per-sample LoRA. Every guard runs before any state changes. Calls invalidate(): the
         prepared-weights generation moves on, so captured HIP graphs (WanTI2V) re-capture."""
-        r = _check_attn_block_mask(spec, self.dim // self.num_heads, self.attn_precision, self.attn_window, self.num_heads)
-        for b in self.blocks:
-            a = b.self_attn
-            _check_attn_block_mask(r, a.head_dim, a.attn_precision, a.attn_window, a.num_heads)
-        self.attn_block_mask = r
-        for b in self.blocks:
-            b.set_attn_block_mask(r)      # one resolver: every block shares its cache
-        self.invalidate()
+        self._apply_modes({"attn_block_mask": spec})
 
     def set_proj_precision(self, mode):
         """Arithmetic of the attention projections of every block: "bf16" (default; like for like with the reference) or "mxfp8" - the
@@ -1243,14 +1050,7 @@ class WanModel(nn.Module):
         NotImplementedError in the mode. Every guard runs before any state changes. Independent of set_ffn_precision and
         set_attn_precision; all combinations are legal. Calls invalidate(): the prepared-weights generation moves on, so cached
         cross-attention K / V^T and captured HIP graphs (WanTI2V) of the other mode can never be replayed."""
-        if not len(self.blocks):
-            _check_proj_precision(mode, self.dim, ())
-        for b in self.blocks:
-            _check_proj_precision(mode, b.dim, (b.self_attn, b.cross_attn))
-        self.proj_precision = mode
-        for b in self.blocks:
-            b.set_proj_precision(mode)
-        self.invalidate()
+        self._apply_modes({"proj_precision": mode})
 
     def prepare(self):
         """Materialise the bf16 operand copies autocast would create on every call of the reference."""

@@ -24,6 +24,7 @@ from .fm_solvers import FlowDPMSolverMultistepScheduler, get_sampling_sigmas, re
 from .fm_solvers_unipc import FlowUniPCMultistepScheduler
 from .. import _lib
 from .model import WanModel, _ensure_prepared
+from .modes import apply_requested
 
 
 def masks_like(tensor, zero=False, generator=None, p=0.2):
@@ -269,25 +270,10 @@ class WanTI2V:
             from .checkpoint import load_wan_model
             model = load_wan_model(checkpoint_dir)
         self.model = model.eval().requires_grad_(False).to(self.device)
-        if ffn_precision is not None and ffn_precision != self.model.ffn_precision:
-            # "bf16" | "mxfp8" (WanModel.set_ffn_precision): the opt-in MXFP8 mode of the FFN projections; None keeps the mode the model
-            # came with ("bf16" unless it was switched). The runners' key carries the model's prepared-weights generation, so a later
-            # switch on self.model re-captures
-            self.model.set_ffn_precision(ffn_precision)
-        if attn_precision is not None and attn_precision != self.model.attn_precision:
-            # "bf16" | "mxfp8_qk" | "mxfp8_qk_pv" (WanModel.set_attn_precision): the opt-in MXFP8 modes of the self-attention, passed on like ffn_precision
-            self.model.set_attn_precision(attn_precision)
-        if attn_window is not None and tuple(attn_window) != tuple(self.model.window_size):
-            # (left, right) as flash-attn's window_size (WanModel.set_attn_window): opt-in sliding-window / causal self-attention, passed on like
-            # attn_precision; None keeps what the model came with (its checkpoint's config.json, global attention unless it says otherwise)
-            self.model.set_attn_window(attn_window)
-        if attn_block_mask is not None:
-            # a bool mask / PreparedBlockMask / callable f(F, H, W, num_heads) / TopKBlockMask (WanModel.set_attn_block_mask): opt-in block-sparse self-attention,
-            # passed on like attn_window; None keeps the model as it came (global attention)
-            self.model.set_attn_block_mask(attn_block_mask)
-        if proj_precision is not None and proj_precision != self.model.proj_precision:
-            # "bf16" | "mxfp8" (WanModel.set_proj_precision): the opt-in MXFP8 mode of the attention projections, passed on like ffn_precision
-            self.model.set_proj_precision(proj_precision)
+        # the DiT's opt-in settings (WanModel.set_ffn_precision / set_attn_precision / set_attn_window / set_attn_block_mask /
+        # set_proj_precision state them): None keeps the mode the model came with, a later switch on self.model re-captures
+        apply_requested(self.model, dict(ffn_precision=ffn_precision, attn_precision=attn_precision, attn_window=attn_window,
+                                         attn_block_mask=attn_block_mask, proj_precision=proj_precision))
         if checkpoint_dir is not None:
             # textimage2video.py:88-103: the VAE and the text encoder come from the same directory. Each is loaded when its
             # file is there and no instance was injected; a missing file leaves the stage to be injected (vae= / text_encoder=)
