@@ -463,6 +463,24 @@ int uv_unipc_predictor(const float* x, const float* m0, const float* m_prev, flo
 int uv_dpmpp_update(const float* x, const float* m0, const float* m1, float* out, float r, float c, float inv_r0, int order,
                     long n, void* stream);
 
+/* ---- step cache (WanTI2V.denoise(step_cache=): skipped steps forecast the block stack's residual) ------------- */
+/* ctl: 4 floats in DEVICE memory, [have, k, c1, c2], read by the kernels on every launch (a captured graph serves every step; the host
+ * writes the table before each replay). have = number of valid difference buffers before this launch (0 .. order + 1). order in
+ * {0, 1, 2}: only d0 .. d[order] exist, the others are NULL and never touched. All tensors fp32, n contiguous elements, n > 0; 16-byte
+ * loads / stores when every buffer is 16-byte aligned, element by element otherwise. Every operation below is one fp32 rounding.
+ * update, after the blocks of a computed step (k = steps since the last computed one): r = x_out - x_in;
+ *   order >= 1 and have >= 1: n1 = (r - d0) / k;  order >= 2 and have >= 2: n2 = (n1 - d1) / k;
+ *   then d0 = r, d1 = n1, d2 = n2 where formed; a buffer that was not formed is not written. x_out and x_in are only read. */
+int uv_step_cache_update(const float* x_out, const float* x_in, float* d0, float* d1, float* d2, const float* ctl, long n, int order,
+                         void* stream);
+/* apply, instead of the blocks of a skipped step (x holds x_in): rh = d0; have >= 2: rh = rh + d1 * c1; have >= 3: rh = rh + d2 * c2;
+ *   x = x + rh in place. k is not read. */
+int uv_step_cache_apply(float* x, const float* d0, const float* d1, const float* d2, const float* ctl, long n, int order, void* stream);
+/* out[i] = (sum_j |rows[i+1][j] - rows[i][j]|) / (sum_j |rows[i][j]|), i < n_rows - 1: rows fp32 [n_rows, K] contiguous, n_rows >= 2.
+ * Both sums in fp64 in a fixed order (one workgroup per pair, no atomics: the same bits on every launch), the fp64 quotient rounded to
+ * fp32 once. A zero row gives inf or NaN. */
+int uv_rows_rel_l1(const float* rows, float* out, int n_rows, int K, void* stream);
+
 /* ---- VAE (fp32, channels-last [T, H, W, C]) -------------------------------------------------------------------- */
 /* Causal 3D / 2D convolution as implicit GEMM on the exact-f32 MFMA. Replaces CausalConv3d (vae2_2.py:17-42) and the
  * Resample convolutions (vae2_2.py:86-108, 153-155). in: input ring [Tin, Hin, Win, ld_in]; w: [Cout, kt*kh*kw*Cin]

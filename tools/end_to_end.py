@@ -16,7 +16,10 @@ f32-grade bf16x6 / f16x3 modes - at the bench size (49 frames of 704 x 1280) and
     --attn-topk K[,B,A,R,C]   with --window-ab: one more side, the self-attention under TopKBlockMask(K, keep) - K an int or a fraction of the
                          key tiles, keep = video_block_mask(frames=(B, A), rows=R, cols=C) when given - with lists built on the device per
                          forward, sample and head; the other sides may then be left out
-    --attn-ab ROUNDS   instead of the table: ms per denoise step with the self-attention in bf16, mxfp8_qk and mxfp8_qk_pv, alternating in one process"""
+    --attn-ab ROUNDS   instead of the table: ms per denoise step with the self-attention in bf16, mxfp8_qk and mxfp8_qk_pv, alternating in one process
+    --step-cache-ab ROUNDS --step-cache SPEC   instead of the table: ms per GENERATION of the denoise loop plain and under the step cache SPEC
+                       (comma-separated key=value of StepCache: order, interval | rel_l1_thresh, first_steps, last_steps - "interval=3,order=1"),
+                       alternating in one process; the plan's computed fraction and the time of the skipping forward on its own"""
 import os, sys, time, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from univid_amd import _lib
@@ -131,6 +134,46 @@ if "--window-ab" in sys.argv:
             print(f"{k} / global = {med[k] / med[None]:.4f}, gain {med[None] - med[k]:.2f} ms/step (global spread {max(ms[None]) - min(ms[None]):.2f} ms)"
                   + ("" if spec is None or k != f"video_block_mask{vm}" else f"; densities {[round(b.density, 4) for b in resolvers[k].prepared().values()]}"),
                   flush=True)
+    sys.exit(0)
+if "--step-cache-ab" in sys.argv:
+    # --step-cache-ab ROUNDS --step-cache SPEC: the denoise loop alone (t2v, decode=False) at the first FRAMES entry, plain and under the step
+    # cache SPEC, alternating round by round in THIS process (both runners stay captured: a 2-step warm-up of each side is not timed), the
+    # first round dropped; ms per GENERATION, the plan's computed fraction, and the skipping forward on its own (replays of its capture).
+    import statistics
+    from univid_amd.wan.step_cache import StepCache
+    spec = dict(kv.split("=") for kv in sys.argv[sys.argv.index("--step-cache") + 1].split(","))
+    num = {"rel_l1_thresh": float}
+    pol = StepCache(int(spec.pop("order", 1)), **{k: num.get(k, int)(v) for k, v in spec.items()})
+    rounds, F = int(sys.argv[sys.argv.index("--step-cache-ab") + 1]), frames[0]
+    pipe = WanTI2V(model=m, vae=None, device=dev)
+    gen = lambda n, sc: pipe.t2v("", size=(1280, 704), frame_num=F, sampling_steps=n, seed=7, prompt_embeds=pe, negative_prompt_embeds=ne, decode=False,
+                                 step_cache=sc)
+    ms = {"plain": [], "cached": []}
+    with torch.no_grad():
+        for side, sc in (("plain", False), ("cached", StepCache(pol.order, schedule=[True, False], last_steps=0))):      # captures; the cached side runs a skip too
+            gen(2, sc)
+        for rnd in range(rounds + 1):
+            for side, sc in (("plain", False), ("cached", pol)):
+                lat, t = clock(lambda: gen(steps, sc))
+                assert bool(torch.isfinite(lat).all())
+                if side == "cached":
+                    plan = pipe.last_step_plan
+                if rnd:
+                    ms[side].append(t * 1e3)
+                print(f"round {rnd}: {side} {t * 1e3:.1f} ms", flush=True)
+        runner = pipe._runner
+        assert runner.cache is not None and len(pipe._runners) == 2
+        skip = []
+        for _ in range(5):
+            _, t = clock(lambda: [runner.graph_skip.replay() for _ in range(20)])
+            skip.append(t / 20 * 1e3)
+    med = {k: statistics.median(v) for k, v in ms.items()}
+    n_c = sum(plan)
+    for k, v in ms.items():
+        print(f"{F} frames, {steps} steps, {k}: median {med[k]:.1f} ms per generation (min {min(v):.1f} max {max(v):.1f}, {len(v)} rounds)", flush=True)
+    print(f"{pol}: {n_c} of {steps} steps computed (fraction {n_c / steps:.3f}); cached / plain = {med['cached'] / med['plain']:.4f}; skipping forward "
+          f"alone: median {statistics.median(skip):.3f} ms (min {min(skip):.3f} max {max(skip):.3f}); a skipped step in the loop = (cached - computed "
+          f"fraction x plain) / skipped steps = {(med['cached'] - n_c / steps * med['plain']) / max(1, steps - n_c):.3f} ms", flush=True)
     sys.exit(0)
 if "--attn-ab" in sys.argv:
     # --attn-ab ROUNDS: the denoise loop alone (t2v, decode=False) at the first FRAMES entry with the self-attention in "bf16", "mxfp8_qk" and "mxfp8_qk_pv",

@@ -87,6 +87,9 @@ SIGNATURES = {
     "uv_unipc_corrector": [_P, _P, _P, _P, _P, _F, _F, _F, _F, _F, _F, _I, _L, _P],
     "uv_unipc_predictor": [_P, _P, _P, _P, _F, _F, _F, _F, _I, _L, _P],
     "uv_dpmpp_update": [_P, _P, _P, _P, _F, _F, _F, _I, _L, _P],
+    "uv_step_cache_update": [_P, _P, _P, _P, _P, _P, _L, _I, _P],
+    "uv_step_cache_apply": [_P, _P, _P, _P, _P, _L, _I, _P],
+    "uv_rows_rel_l1": [_P, _P, _I, _I, _P],
     "uv_conv3d_f32": [_P, _L, _I, _I, _I, _P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I,
                       _P, _L, _P],
     "uv_conv3d_bf16x6": [_P, _L, _I, _I, _I, _P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I,
@@ -1051,6 +1054,49 @@ def dpmpp_update(x, m0, m1, out, r, c, inv_r0, order):
     n = out.numel()
     _check("dpmpp_update", (x, "x", F32, n), (m0, "m0", F32, n), (m1, "m1", F32, n, None, order != 2), (out, "out", F32, n))
     call("uv_dpmpp_update", ptr(x), ptr(m0), ptr(m1), ptr(out), r, c, inv_r0, order, out.numel(), stream_ptr())
+    return out
+
+
+# -- step cache: contiguous f32 buffers of n elements; ctl = [have, k, c1, c2] f32 in device memory; d1 / d2 only where order has them --
+STEP_CACHE_GRID_ELEMS = 2048 * 256 * 4      # elements one pass of the largest grid covers (csrc/step_cache.hip: SC_MAX_BLOCKS x SC_THREADS x 4)
+
+
+def _step_cache_args(fn, d0, d1, d2, ctl, n, order):
+    if order not in (0, 1, 2):
+        raise UnividHipError(f"{fn}: order must be 0, 1 or 2, got {order!r}")
+    if n <= 0:
+        raise UnividHipError(f"{fn}: n must be positive, got {n}")
+    return ((d0, "d0", F32, n), (d1, "d1", F32, n, None, order < 1), (d2, "d2", F32, n, None, order < 2), (ctl, "ctl", F32, 4))
+
+
+def step_cache_update(x_out, x_in, d0, d1, d2, ctl, order, n=None):
+    """After the blocks of a computed step: r = x_out - x_in, the first / second backward differences over k steps where `have` and
+    `order` allow them, then d0 = r, d1 = n1, d2 = n2 (include/univid_hip.h: uv_step_cache_update). Buffers beyond `order` are not
+    touched (pass None)."""
+    n = x_out.numel() if n is None else int(n)
+    _check("step_cache_update", (x_out, "x_out", F32, n), (x_in, "x_in", F32, n), *_step_cache_args("step_cache_update", d0, d1, d2, ctl, n, order))
+    call("uv_step_cache_update", ptr(x_out), ptr(x_in), ptr(d0), ptr(d1 if order >= 1 else None), ptr(d2 if order >= 2 else None), ptr(ctl), n,
+         int(order), stream_ptr())
+    return d0
+
+
+def step_cache_apply(x, d0, d1, d2, ctl, order, n=None):
+    """Instead of the blocks of a skipped step: x += d0 + d1 * c1 + d2 * c2, each term while `have` covers it (include/univid_hip.h:
+    uv_step_cache_apply). Buffers beyond `order` are not touched (pass None)."""
+    n = x.numel() if n is None else int(n)
+    _check("step_cache_apply", (x, "x", F32, n), *_step_cache_args("step_cache_apply", d0, d1, d2, ctl, n, order))
+    call("uv_step_cache_apply", ptr(x), ptr(d0), ptr(d1 if order >= 1 else None), ptr(d2 if order >= 2 else None), ptr(ctl), n, int(order),
+         stream_ptr())
+    return x
+
+
+def rows_rel_l1(rows, out):
+    """out[i] = sum|rows[i + 1] - rows[i]| / sum|rows[i]|: rows f32 [n_rows, K] contiguous, out f32 [n_rows - 1]; fp64 sums in a fixed order."""
+    if rows.dim() != 2 or rows.shape[0] < 2 or rows.shape[1] < 1:
+        raise UnividHipError(f"rows_rel_l1: at least two rows of at least one column are expected, got shape {tuple(rows.shape)}")
+    n_rows, K = rows.shape
+    _check("rows_rel_l1", (rows, "rows", F32, n_rows * K), (out, "out", F32, n_rows - 1))
+    call("uv_rows_rel_l1", ptr(rows), ptr(out), n_rows, K, stream_ptr())
     return out
 
 

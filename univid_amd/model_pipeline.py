@@ -30,7 +30,7 @@ import torch
 
 from .lora import LoRAManager
 from .wan.modes import MODE_DEFAULTS, apply_requested
-from .wan.textimage2video import TI2VConfig, WanTI2V, set_vae_precision
+from .wan.textimage2video import TI2VConfig, WanTI2V, _step_cache_policy, set_vae_precision
 
 
 @dataclass
@@ -60,6 +60,7 @@ class CrossAttentionConfig:
     attn_precision: str = "bf16"  # "mxfp8_qk" / "mxfp8_qk_pv": the DiT's self-attention q / k (and P.V) as MXFP8 (WanModel.set_attn_precision), opt-in experimental modes
     attn_window: Optional[Tuple[int, int]] = None  # (left, right) tokens as flash-attn's window_size: sliding-window / causal DiT self-attention (WanModel.set_attn_window), opt-in, changes the model's function; None = what the checkpoint says (global)
     attn_block_mask: Any = None  # a bool block mask / PreparedBlockMask / callable f(F, H, W, num_heads) / TopKBlockMask: block-sparse DiT self-attention (WanModel.set_attn_block_mask), opt-in, changes the model's function; None = global
+    step_cache: Any = None  # a univid_amd.wan.step_cache.StepCache: skipped sampler steps forecast the DiT blocks' residual (WanTI2V.denoise(step_cache=)), opt-in, changes the function computed; not a model mode; None = every step is computed
     guidance_strength: float = 1.0
     bagel_cross_attn_layers: List[int] = None
     freeze_bagel: bool = True
@@ -387,6 +388,9 @@ class CrossAttentionFusionPipeline:
         # for another than the default
         apply_requested(self.dit_model, self._dit_modes, injected=True)
         set_vae_precision(getattr(wan_pipeline, "vae", None), getattr(config, "vae_precision", None))
+        # the loop's step cache is the pipeline's setting, not a model mode: by the same rule, None leaves an injected pipeline's own alone
+        if getattr(config, "step_cache", None) is not None and hasattr(wan_pipeline, "step_cache"):
+            wan_pipeline.step_cache = _step_cache_policy(config.step_cache)
         self.vae_model = wan_pipeline.vae
         self.text_encoder = wan_pipeline.text_encoder
         # native_text_weight=False: the reference's closures on the model's generic path (kept as the comparison the tests and bench use)
@@ -414,7 +418,8 @@ class CrossAttentionFusionPipeline:
         self._check_gpu("wan_gpu")
         try:
             return WanTI2V(config=wan_config, checkpoint_dir=path, device_id=self.config.wan_gpu, rank=0, t5_fsdp=False, dit_fsdp=False,
-                           use_sp=False, vae_precision=getattr(self.config, "vae_precision", None), **self._dit_modes)
+                           use_sp=False, vae_precision=getattr(self.config, "vae_precision", None), step_cache=getattr(self.config, "step_cache", None),
+                           **self._dit_modes)
         except Exception as e:
             raise RuntimeError(f"Wan2.2 initialization failed: {e}") from e
 

@@ -1254,7 +1254,7 @@ class WanModel(nn.Module):
         _, F0, H0, W0 = x[0].shape
         return len({tuple(u.shape) for u in x}) == 1 and ((F0 // pt) * (H0 // ph) * (W0 // pw)) % 8 == 0 and self.text_len % 8 == 0
 
-    def forward(self, x, t, context, seq_len, y=None, *, t_rows=None, context_kv=None):
+    def forward(self, x, t, context, seq_len, y=None, *, t_rows=None, context_kv=None, step_cache=None):
         r"""Same contract as the reference (model.py:410-497).
 
         x: List[Tensor[C_in, F, H, W]] fp32; t: Tensor[B] or Tensor[B, seq_len]; context: List[Tensor[L<=text_len,
@@ -1272,6 +1272,14 @@ class WanModel(nn.Module):
         fills them), which this forward's cross-attention launches read. `context` is then not read (None will do), nothing is embedded
         or cached, and set_text_weight is not consulted: the weights are whatever the caller put into the buffers. One stacked group
         only, and no re-assigned cross-attention forward (a closure takes the context, not its K / V^T).
+
+        step_cache (extension, keyword-only): `(state, "compute" | "skip")` with a univid_amd.wan.step_cache.StepCacheState, whose control
+        table the caller has set for this step (StepCacheState.advance). "compute": the forward is the plain one - its output is bit-identical
+        - and in addition copies the residual stream after the patch embedding (x_in) into the state and, after the last block, updates the
+        state's residual r = x_out - x_in and its backward differences (uv_step_cache_update). "skip": neither the context nor any block is
+        touched; the stream becomes x_in + the forecast residual (uv_step_cache_apply) and the head and unpatchify run as always. This
+        computes a DIFFERENT function of the same weights (README). The caller allocates the state's buffers (StepCacheState.buffers) before
+        the first step; this forward only checks them, so nothing is allocated inside a capture. One stacked group only and no sequence parallelism (NotImplementedError otherwise).
         """
         if self.model_type == "i2v":
             assert y is not None
@@ -1282,6 +1290,16 @@ class WanModel(nn.Module):
                 raise ValueError("context_kv= needs samples of one shape (a single stacked group)")
             if any("forward" in b.cross_attn.__dict__ for b in self.blocks):
                 raise NotImplementedError("context_kv= with a re-assigned cross_attn.forward: the closure takes the context, not its K / V^T")
+        skip = False
+        if step_cache is not None:
+            sc_state, sc_kind = step_cache
+            if sc_kind not in ("compute", "skip"):
+                raise ValueError(f'step_cache: the second entry must be "compute" or "skip", got {sc_kind!r}')
+            if self.sp is not None and self.sp.size > 1:
+                raise NotImplementedError("step_cache= is not built for sequence-parallel forwards (the cache holds the whole residual stream)")
+            if not self._stacks(x):
+                raise NotImplementedError("step_cache= needs samples of one shape that run as a single stacked group (token count % 8 == 0)")
+            skip = sc_kind == "skip"
         aw = self._adapter_weights
         if aw is not None:
             if len(aw) != len(x):
@@ -1295,7 +1313,7 @@ class WanModel(nn.Module):
             x = [torch.cat([u, v], dim=0) for u, v in zip(x, y)]
         if t_rows is None and t.dim() == 1:  # one timestep per sample (model.py:460-461)
             t = t.view(-1, 1).expand(-1, seq_len)
-        ctx_all, ctx_gen = self._embedded_context(context) if context_kv is None else (None, None)
+        ctx_all, ctx_gen = self._embedded_context(context) if (context_kv is None and not skip) else (None, None)
         fr = _freqs_device(self.freqs, dev)
         pt, ph, pw = self.patch_size
         C = self.dim
@@ -1332,7 +1350,7 @@ class WanModel(nn.Module):
                 # (i2v: two timesteps per sample - the samples of a twin pair must also agree token by token)
                 twin_t = tid is None or (B > 1 and bool(torch.equal(inv.view(B, L), inv[:L].expand(B, L))))
             e_rows, e0_rows = self._time_rows(tvals.contiguous())
-            ctx = None if context_kv is not None else ctx_all[idx[0]] if B == 1 else torch.cat([ctx_all[i] for i in idx], 0)
+            ctx = None if (context_kv is not None or skip) else ctx_all[idx[0]] if B == 1 else torch.cat([ctx_all[i] for i in idx], 0)
             kv_key = None if ctx_gen is None else (ctx_gen, tuple(idx))
             par = self.sp if (self.sp is not None and self.sp.size > 1) else None
             if par is None:
@@ -1356,11 +1374,20 @@ class WanModel(nn.Module):
                     (tid is None or twin_t))
             # UniVid's dynamic text weight (set_text_weight): the hooked blocks read the row-scaled context, and compute their K / V^T
             # of it in this forward (it changes from forward to forward while the schedule runs; the cache holds the plain one)
-            tw = self._text_weight if context_kv is None else None
+            tw = self._text_weight if (context_kv is None and not skip) else None
             if tw is not None and len(tw[0]) != len(xs_in):
                 raise ValueError(f"set_text_weight was given {len(tw[0])} weight(s); this forward has {len(xs_in)} sample(s)")
             ctx_w = self.weighted_context(ctx_all, idx, tw) if (tw is not None and any(tw[0][i] != 1.0 for i in idx)) else None
-            for li, blk in enumerate(self.blocks):
+            if step_cache is not None:
+                sc = sc_state
+                if not sc.holds(B * n, C, dev):
+                    raise RuntimeError(f"step_cache: the state holds no buffers for a [{B * n}, {C}] stream on {dev}: call "
+                                       f"StepCacheState.buffers(rows, C, device) before the first step")
+                if skip:      # the forecast residual instead of the block stack
+                    _lib.step_cache_apply(xs, sc.d[0], sc.d[1], sc.d[2], sc.ctl, sc.order)
+                else:
+                    sc.x_in.copy_(xs)
+            for li, blk in enumerate(() if skip else self.blocks):
                 hooked = ctx_w is not None and (tw[2] is None or li in tw[2])
                 if par is None or n:
                     blk._run(xs, n, e0_rows, tid, (Fp, Hp, Wp), fr, ctx_w if hooked else ctx, first_block=(li == 0), batch=B, sp=sp_arg,
@@ -1368,6 +1395,8 @@ class WanModel(nn.Module):
                              kv=None if context_kv is None else context_kv[li])
                 else:   # a rank without tokens still takes part in the self-attention exchanges
                     blk.self_attn._self_attn_sp(xs.new_empty(0, C).to(BF16), 0, (Fp, Hp, Wp), fr, xs, None, None, B, sp_arg)
+            if step_cache is not None and not skip:
+                _lib.step_cache_update(xs, sc.x_in, sc.d[0], sc.d[1], sc.d[2], sc.ctl, sc.order)
             yh = self.head._run(xs, B * n, e_rows, tid) if B * n else xs.new_empty(0, self.head.head.out_features)
             for j, i in enumerate(idx):
                 out = torch.empty(self.out_dim, Fp * pt, Hp * ph, Wp * pw, dtype=torch.float32, device=dev)

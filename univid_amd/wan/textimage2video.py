@@ -115,8 +115,12 @@ class _GraphedPair:
     differs from what its buffers hold. So one capture per (latent shape, mode, prepared weights) serves every prompt and every text-weight
     schedule: no recapture (0.4 s at 49 frames, 1 s at 121), and once the schedule has reached w = 1 (after
     int(total_sampling_steps * ratio) forwards) a step is the plain replay, bit for bit.
+
+    step_cache_order (None: no step cache - nothing about the runner changes): the runner owns a StepCacheState and holds TWO captures over
+    the same static latent and timestep table, the computing forward (with the x_in copy and the update) and the skipping forward (apply
+    instead of the blocks); `__call__(..., step=(i, compute))` writes the state's control table like `tvals` and replays one of them.
     """
-    def __init__(self, model, latent, context, context_null, seq_len, i2v_mask, key=None):
+    def __init__(self, model, latent, context, context_null, seq_len, i2v_mask, key=None, step_cache_order=None):
         from . import model as _m
         dev = latent.device
         self.key = key
@@ -149,8 +153,14 @@ class _GraphedPair:
             self.apply()
             self.lat.copy_(latent)
             pair = [self.lat, self.lat]
+            kw = dict(t_rows=(self.tvals, tid, True), context_kv=self.kv)
+            self.cache = self.graph_skip = self.out_skip = None
+            if step_cache_order is not None:
+                from .step_cache import StepCacheState
+                self.cache = StepCacheState(step_cache_order).buffers(2 * L, model.dim, model.patch_embedding.weight.device)
+                kw["step_cache"] = (self.cache, "compute")
             # eager warm-up on the capture inputs: weight preparation, scratch buffers, function attributes
-            model(pair, None, None, L, t_rows=(self.tvals, tid, True), context_kv=self.kv)
+            model(pair, None, None, L, **kw)
             torch.cuda.synchronize(dev)
             self.graph = torch.cuda.CUDAGraph()
             # scratch the forward caches per stream (V^T tiles): tensors born during the capture live in THIS graph's memory pool and
@@ -159,9 +169,21 @@ class _GraphedPair:
             snap = _m.scratch_snapshot()
             try:
                 with torch.cuda.graph(self.graph):
-                    self.out = model(pair, None, None, L, t_rows=(self.tvals, tid, True), context_kv=self.kv)
+                    self.out = model(pair, None, None, L, **kw)
             finally:
                 self.scratch = _m.scratch_take_new(snap)
+            if self.cache is not None:
+                # the skipping forward (patch embedding, apply, head): its own capture and pool, the same static inputs
+                kw["step_cache"] = (self.cache, "skip")
+                model(pair, None, None, L, **kw)
+                torch.cuda.synchronize(dev)
+                self.graph_skip = torch.cuda.CUDAGraph()
+                snap = _m.scratch_snapshot()
+                try:
+                    with torch.cuda.graph(self.graph_skip):
+                        self.out_skip = model(pair, None, None, L, **kw)
+                finally:
+                    self.scratch += _m.scratch_take_new(snap)
 
     def __del__(self):
         # the graph (and its memory pool) must not be destroyed under a replay that is still running: a generation returns without
@@ -215,13 +237,29 @@ class _GraphedPair:
                 self.state[li] = w if hooked else plain
         return len(stale)
 
-    def __call__(self, latent, t, text_weight=None):
+    def __call__(self, latent, t, text_weight=None, step=None):
+        """step (a runner with a step cache only): (index of the sampler step, True = computed | False = skipped)."""
+        if (step is None) != (self.cache is None):
+            raise ValueError("_GraphedPair: step= goes with a runner that was captured with a step cache, and only with one")
+        compute = step is None or bool(step[1])
         with torch.cuda.device(self.dev):
-            self.apply(text_weight)
+            if compute:
+                self.apply(text_weight)      # (a skipped step reads no context)
             self.lat.copy_(latent)
             self.tvals[-1:].fill_(t)         # the value travels as a kernel argument (no host buffer to race with); row 0 stays 0 for i2v
-            self.graph.replay()
-        return self.out[0], self.out[1]      # static outputs: consumed by the sampler update before the next replay
+            if step is not None:
+                self.cache.advance(step[0], compute)
+            (self.graph if compute else self.graph_skip).replay()
+        out = self.out if compute else self.out_skip
+        return out[0], out[1]                # static outputs: consumed by the sampler update before the next replay
+
+
+def _step_cache_policy(value):
+    """step_cache= as WanTI2V and denoise take it: a StepCache, or None."""
+    from .step_cache import StepCache
+    if value is not None and not isinstance(value, StepCache):
+        raise TypeError(f"step_cache: a univid_amd.wan.step_cache.StepCache (or None) is expected, got {type(value).__name__}")
+    return value
 
 
 def set_vae_precision(vae, precision):
@@ -236,7 +274,7 @@ class WanTI2V:
     def __init__(self, config=TI2VConfig, checkpoint_dir=None, device_id=0, rank=0, t5_fsdp=False, dit_fsdp=False,
                  use_sp=False, t5_cpu=False, init_on_cpu=True, convert_model_dtype=False, *, model: WanModel = None,
                  vae=None, text_encoder: Optional[Callable] = None, device=None, ffn_precision=None, attn_precision=None, proj_precision=None,
-                 vae_precision=None, attn_window=None, attn_block_mask=None):
+                 vae_precision=None, attn_window=None, attn_block_mask=None, step_cache=None):
         if t5_fsdp or dit_fsdp:
             raise NotImplementedError("FSDP is not part of this build (UniVid passes False, models/model_pipeline.py:2205-2207; "
                                       "the fp32 masters + bf16 operands of the 5B DiT are 30 GB of a 288 GB GPU)")
@@ -260,6 +298,11 @@ class WanTI2V:
         self.max_graph_runners = 2
         self._progress, self._steps_issued = None, 0
         self.max_steps_in_flight = 4       # sampler steps the host may queue ahead of the GPU (WanTI2V._steps)
+        # the step cache of denoise (univid_amd.wan.step_cache.StepCache | None = off): the pipeline's default, opt-in - a cached generation
+        # computes a different function of the same weights (README); `last_step_plan`: the plan the last cached denoise ran (None: it ran plain)
+        self.step_cache = _step_cache_policy(step_cache)
+        self.last_step_plan = None
+        self._step_state = None            # the eager loop's StepCacheState (a graph runner owns its own)
         self.text_weight_schedule = None   # object with next_pair() / rows(text_len) / layers: UniVid's dynamic text weight, native
         self.sample_neg_prompt = config.sample_neg_prompt
         self.text_encoder = text_encoder
@@ -299,7 +342,7 @@ class WanTI2V:
             self.sp_size = self.model.sp.size
 
     def _runner_for(self, key, make):
-        """The cached runner of `key` = (latent shape, i2v, prepared-weights generation, text_len), moved to the most-recently-used end, or
+        """The cached runner of `key` = (latent shape, i2v, prepared-weights generation, text_len[, ("step_cache", order)]), moved to the most-recently-used end, or
         `make()` stored under it. Returns (runner, fresh). Before a capture: runners of other prepared weights / another text_len are
         dropped (they can never be asked for again; the generation of a per-sample adapter setting that can come back is kept) and the least recently used ones go until there is room - their graphs' pools are
         freed BEFORE the new capture allocates its own. A `make()` that raises leaves nothing behind under `key`."""
@@ -307,7 +350,7 @@ class WanTI2V:
         fresh = runner is None
         if fresh:
             alive = getattr(getattr(self, "model", None), "generation_alive", lambda g: False)    # (a per-sample adapter setting that can come back)
-            for stale in [k for k in self._runners if k[2:] != key[2:] and not (k[3:] == key[3:] and alive(k[2]))]:
+            for stale in [k for k in self._runners if k[2:4] != key[2:4] and not (k[3:4] == key[3:4] and alive(k[2]))]:
                 del self._runners[stale]
             while len(self._runners) >= max(1, self.max_graph_runners):
                 self._runners.popitem(last=False)
@@ -345,7 +388,7 @@ class WanTI2V:
     def generate(self, input_prompt, img=None, size=(1280, 704), max_area=704 * 1280, frame_num=81, shift=5.0,
                  sample_solver="unipc", sampling_steps=50, guide_scale=5.0, n_prompt="", seed=-1, offload_model=True,
                  **kw):
-        """textimage2video.py:162-237. Keyword extensions of t2v / i2v (prompt_embeds=, noise=, decode=, adapter_weights=) pass through."""
+        """textimage2video.py:162-237. Keyword extensions of t2v / i2v (prompt_embeds=, noise=, decode=, adapter_weights=, step_cache=) pass through."""
         if img is not None:
             return self.i2v(input_prompt=input_prompt, img=img, max_area=max_area, frame_num=frame_num, shift=shift,
                             sample_solver=sample_solver, sampling_steps=sampling_steps, guide_scale=guide_scale,
@@ -356,23 +399,26 @@ class WanTI2V:
 
     # ---- the hot loop ----------------------------------------------------------------------------------------
     def denoise(self, noise, context, context_null, sampling_steps, shift, guide_scale, z=None, record=None, graph=None,
-                sample_solver="unipc", adapter_weights=None):
+                sample_solver="unipc", adapter_weights=None, step_cache=None):
         """adapter_weights: strengths of the un-merged adapters for THIS call - one {adapter name: weight} dict for both branches of the
         CFG pair, or a (cond, uncond) pair of dicts (a style adapter on the conditional branch only: ({"style": 1.0}, {"style": 0.0})).
         Installed with WanModel.set_adapter_weights for the length of the call - on the stacked pair eager or replayed from a HIP graph
         (a repeated request with the same weights replays its capture), one branch per rank under CFG parallelism - and the previous
-        setting is restored afterwards. None: the model's setting as it is. See _denoise for the other arguments."""
+        setting is restored afterwards. None: the model's setting as it is.
+        step_cache: a univid_amd.wan.step_cache.StepCache for THIS call, False = off in this call, None = the pipeline's setting
+        (WanTI2V(step_cache=) / self.step_cache). See _denoise for it and the other arguments."""
+        step_cache = self.step_cache if step_cache is None else None if step_cache is False else _step_cache_policy(step_cache)
         # the loop owns its context tensors for its duration: step-constant context work is computed once (WanModel.context_cached)
         cached = self.model.context_cached() if hasattr(self.model, "context_cached") else contextlib.nullcontext()
         if adapter_weights is None:
             with cached:
-                return self._denoise(noise, context, context_null, sampling_steps, shift, guide_scale, z, record, graph, sample_solver)
+                return self._denoise(noise, context, context_null, sampling_steps, shift, guide_scale, z, record, graph, sample_solver, step_cache)
         per_sample = self._adapter_rows(adapter_weights)
         previous = self.model.adapter_weights()
         self.model.set_adapter_weights(per_sample)          # validates before anything changes
         try:
             with cached:
-                return self._denoise(noise, context, context_null, sampling_steps, shift, guide_scale, z, record, graph, sample_solver)
+                return self._denoise(noise, context, context_null, sampling_steps, shift, guide_scale, z, record, graph, sample_solver, step_cache)
         finally:
             self.model.set_adapter_weights(previous)
 
@@ -400,7 +446,7 @@ class WanTI2V:
         return [cond, uncond]
 
     def _denoise(self, noise, context, context_null, sampling_steps, shift, guide_scale, z=None, record=None, graph=None,
-                 sample_solver="unipc"):
+                 sample_solver="unipc", step_cache=None):
         """Steps of t2v (:356-394) / i2v (:548-601) on a given noise latent [C, f, h, w] (fp32, on device).
 
         z: first-frame latent [C, 1, h, w] switches on the i2v masking (mask2 zero on frame 0, :550-551, :598).
@@ -412,6 +458,13 @@ class WanTI2V:
             host: 3 instead of 495 entry-point calls and 1 ms instead of 229 ms of process CPU time per step; off whenever a hook or a
             parallel mode owns the forward. Results are bit-identical either way (same kernels, same order).
         sample_solver: 'unipc' (:335-342) or 'dpm++' (:343-351), as in the reference.
+        step_cache: a StepCache (None: the plain loop, untouched). The steps its plan skips do not run the DiT's blocks: the pair's residual
+            stream becomes x_in + a forecast of the blocks' residual from the computed steps (WanModel.forward(step_cache=)). The plan is
+            fixed BEFORE the first step - the steps whose native text-weight pair is not (1, 1) are forced to be computed, and the
+            rel_l1_thresh rule reads its time-embedding distances in ONE device -> host copy here, the only synchronisation the cache adds
+            - so the loop keeps running ahead of the GPU. Kept as self.last_step_plan. Eager and graph (two captures per runner) give the
+            same bits. Needs the plain path: NotImplementedError under CFG parallelism, sequence parallelism, a re-assigned forward or a
+            token count that does not stack, before anything runs.
         Returns the final latent.
         """
         dev = self.device
@@ -445,6 +498,15 @@ class WanTI2V:
             graph = plain and graph_by_default(n_tok)
         elif graph and not plain:
             raise NotImplementedError("graph=True needs the plain single-process forward (no text-weight hook, CFG pair or SP mode)")
+        cache = None
+        if step_cache is not None:
+            if not plain:
+                raise NotImplementedError("step_cache= needs the plain single-process loop: no CFG parallelism, no sequence parallelism and no "
+                                          "re-assigned forward on the DiT or a cross-attention")
+            if not (hasattr(self.model, "_stacks") and self.model._stacks([latent, latent])):
+                raise NotImplementedError("step_cache= needs the CFG pair as one stacked forward (token count and text_len % 8 == 0)")
+            cache = self._plan_steps(step_cache, timesteps, tws)
+        self.last_step_plan = None if cache is None else cache[0]
         runner = None
         if graph:
             # one captured graph per (latent shape, mode, contexts, prepared weights): generations that repeat them replay it
@@ -452,18 +514,54 @@ class WanTI2V:
             # one captured graph per (latent shape, mode, prepared weights); the prompt travels through the runner's own context buffers,
             # recomputed in place at the start of every call (_GraphedPair.refresh): no recapture for a new prompt, nothing to go stale
             key = (tuple(latent.shape), i2v, self.model._prep_gen, self.model.text_len)
+            order = None
+            if cache is not None:      # a runner of its own: the computing capture carries the x_in copy and the update
+                order = step_cache.order
+                key += (("step_cache", order),)
             runner, fresh = self._runner_for(key, lambda: _GraphedPair(self.model, latent, context, context_null, seq_len,
-                                                                       base_mask if i2v else None, key))
+                                                                       base_mask if i2v else None, key, step_cache_order=order))
             if not fresh:
                 runner.refresh(context, context_null)
+        if cache is not None:
+            state = runner.cache if runner is not None else self._eager_step_state(step_cache.order, 2 * n_tok)
+            state.reset()              # `have` is 0 at the start of every denoise
+            cache += (state,)
         try:
-            return self._steps(sched, timesteps, latent, context, context_null, guide_scale, z, mask2, base_mask, seq_len, record, runner, tws)
+            return self._steps(sched, timesteps, latent, context, context_null, guide_scale, z, mask2, base_mask, seq_len, record, runner, tws,
+                               cache)
         finally:
             if tws is not None and hasattr(self.model, "set_text_weight"):
                 self.model.set_text_weight(None)
 
-    def _steps(self, sched, timesteps, latent, context, context_null, guide_scale, z, mask2, base_mask, seq_len, record, runner, tws):
+    def _plan_steps(self, policy, timesteps, tws):
+        """(plan, pairs): the step cache's plan for this denoise and - with a native text-weight schedule - the (cond, uncond) weights of
+        every step, drawn here because the steps whose pair is not (1, 1) are forced (the schedule's counter ends where the loop would
+        leave it). The rel_l1_thresh rule's distances: ONE _time_rows call over all timesteps, one uv_rows_rel_l1 launch, one copy to the host."""
+        n = len(timesteps)
+        pairs = None if tws is None else [tws.next_pair() for _ in range(n)]
+        forced = () if pairs is None else [i for i, (wc, wu) in enumerate(pairs) if wc != 1.0 or wu != 1.0]
+        distances = None
+        if policy.needs_distances:
+            distances = [0.0] * n
+            if n >= 2:
+                with torch.cuda.device(self.device):
+                    tv = torch.tensor([float(t) for t in timesteps], dtype=torch.float32).to(self.device)
+                    e, e0 = self.model._time_rows(tv)
+                    out = torch.empty(n - 1, dtype=torch.float32, device=self.device)
+                    _lib.rows_rel_l1((e0 if policy.indicator == "e0" else e).contiguous(), out)
+                    distances[1:] = out.tolist()          # the one synchronisation of a cached denoise
+        return policy.plan(n, distances, forced), pairs
+
+    def _eager_step_state(self, order, rows):
+        from .step_cache import StepCacheState
+        if self._step_state is None or self._step_state.order != order:
+            self._step_state = StepCacheState(order)
+        return self._step_state.buffers(rows, self.model.dim, self.model.patch_embedding.weight.device)      # (the device the forward names)
+
+    def _steps(self, sched, timesteps, latent, context, context_null, guide_scale, z, mask2, base_mask, seq_len, record, runner, tws,
+               cache=None):
         dev = self.device
+        plan, pairs, state = cache if cache is not None else (None, None, None)
         i2v = z is not None
         # The host runs ahead of the GPU (nothing in a step synchronises). Unbounded, it runs into the HIP runtime's launch queue: from about
         # the 23rd queued graph replay on, the launch call blocks by SPINNING (measured at L = 11 440: a 50-step generation burned 13.7 s of
@@ -472,17 +570,17 @@ class WanTI2V:
         # fill + one 8-byte asynchronous copy) and the host, when it is that far ahead, naps in 1-ms slices reading that counter as plain
         # memory - no HIP call in the wait (hipEventSynchronize, blocking flag or not, and a hipEventQuery poll both kept a core busy:
         # measured). The GPU never starves: the queue still holds the other steps' work.
-        for t in timesteps:
+        for i, t in enumerate(timesteps):
             self._throttle()
             tw = None
             if tws is not None:
                 # UniVid's dynamic text weight, native (model_pipeline.py:1699-1810, 1844-1886): the wrapper's counter advances once per
                 # DiT forward, the cond forward first (:1856-1864, textimage2video.py:380-385) - the stacked CFG pair carries both values
-                wc, wu = tws.next_pair()
+                wc, wu = tws.next_pair() if pairs is None else pairs[i]
                 if wc != 1.0 or wu != 1.0:
                     tw = ((wc, wu), tws.rows(self.model.text_len), tws.layers)
             if runner is not None:
-                cond, uncond = runner(latent, float(t), tw)
+                cond, uncond = runner(latent, float(t), tw) if plan is None else runner(latent, float(t), tw, step=(i, plan[i]))
                 res = sched.step_cfg(cond.unsqueeze(0), uncond.unsqueeze(0), guide_scale, t, latent.unsqueeze(0),
                                      want_noise_pred=record is not None)
                 if record is not None:
@@ -518,8 +616,12 @@ class WanTI2V:
                 uncond = self.model([latent], t=tvec, context=context_null, seq_len=seq_len)[0]
             else:
                 # cond + uncond as one stacked pass (bit-identical per sample, better occupancy)
+                sc = {}
+                if plan is not None:
+                    state.advance(i, plan[i])
+                    sc["step_cache"] = (state, "compute" if plan[i] else "skip")
                 cond, uncond = self.model([latent, latent], t=torch.cat([tvec, tvec]), context=[context[0], context_null[0]],
-                                          seq_len=seq_len)
+                                          seq_len=seq_len, **sc)
             res = sched.step_cfg(cond.unsqueeze(0), uncond.unsqueeze(0), guide_scale, t, latent.unsqueeze(0),
                                  want_noise_pred=record is not None)
             if record is not None:
@@ -565,7 +667,7 @@ class WanTI2V:
 
     def t2v(self, input_prompt, size=(1280, 704), frame_num=121, shift=5.0, sample_solver="unipc", sampling_steps=50,
             guide_scale=5.0, n_prompt="", seed=-1, offload_model=True, *, prompt_embeds=None, negative_prompt_embeds=None,
-            noise=None, decode=True, adapter_weights=None):
+            noise=None, decode=True, adapter_weights=None, step_cache=None):
         """textimage2video.py:239-411. Returns the video [3, N, H, W] in [-1, 1] (or the latent if decode=False)."""
         F = frame_num
         z_dim = self.model.in_dim
@@ -579,7 +681,7 @@ class WanTI2V:
             noise = self._noise(target_shape, seed)
         with torch.no_grad():
             x0 = self.denoise(noise, context, context_null, sampling_steps, shift, guide_scale, sample_solver=sample_solver,
-                              adapter_weights=adapter_weights)
+                              adapter_weights=adapter_weights, step_cache=step_cache)
             if not decode:
                 return x0
             if self.vae is None:
@@ -588,7 +690,7 @@ class WanTI2V:
 
     def i2v(self, input_prompt, img, max_area=704 * 1280, frame_num=121, shift=5.0, sample_solver="unipc",
             sampling_steps=40, guide_scale=5.0, n_prompt="", seed=-1, offload_model=True, *, prompt_embeds=None,
-            negative_prompt_embeds=None, noise=None, decode=True, adapter_weights=None):
+            negative_prompt_embeds=None, noise=None, decode=True, adapter_weights=None, step_cache=None):
         """textimage2video.py:413-619. `img` is a PIL image, or a float tensor [3, H, W] in [-1, 1] that already has
         the output size (the PIL resize/crop of :462-477 is host-side image I/O)."""
         if self.vae is None:
@@ -622,5 +724,5 @@ class WanTI2V:
         with torch.no_grad():
             z = self.vae.encode([img_t])[0]
             x0 = self.denoise(noise, context, context_null, sampling_steps, shift, guide_scale, z=z, sample_solver=sample_solver,
-                              adapter_weights=adapter_weights)
+                              adapter_weights=adapter_weights, step_cache=step_cache)
             return self.vae.decode([x0])[0] if decode else x0
